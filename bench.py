@@ -6,9 +6,12 @@
 N = 1 (the default, what the driver's BENCH run executes)
     `value` = BASELINE.json configs[1]: one 48 kHz x 10 s utterance per step (2001 frames), Harvest + CheapTrick +
     D4C, 5 ms hop, fft_size 2048, inputs and outputs resident in HBM, `--streams` (12) independent jobs in flight.
-    The timed region is `repeats` back-to-back blocks of K steps inside ONE barrier + synchronize bracket, with
-    `repeats` chosen so that the region lasts >= --min-wall seconds (K = 20 steps are 20 ms of GPU time: too short
-    for any sampler).  After the timed region the run checks itself (`parity_in_run`): every in-flight slot's
+    The timed region is K = --steps steps inside ONE barrier + synchronize bracket and `ms_per_step` is its wall time
+    over K; --min-wall S > 0 instead repeats the K steps until the region lasts >= S seconds (`repeats`).
+    --dump-outputs DIR writes the last timed step's results (tpos, f0, sp, ap, nf) to DIR/<name>.npy as float64
+    (a fixed, seeded sample of the spectral rows past 64 MB); the inputs depend on the arguments alone, so two builds
+    run with the same arguments can be compared output for output.
+    After the timed region the run checks itself (`parity_in_run`): every in-flight slot's
     (f0, sp, ap) must be bit-identical to a serial single-context run, and that run must agree with the CPU
     reference computed for `cpu_baseline` to the contract's 1e-4 -- otherwise the process exits non-zero.
     Beside `value` the line carries `value_single_job` (1 / latency of a lone job) and a `configs` object with one
@@ -33,12 +36,8 @@ import os
 import sys
 import time
 
-# The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): with
-# more independent jobs in flight than queues, jobs that share a queue run one after the other.  Must be set
-# before the runtime initialises (measured on configs[1] in round 1: 8 jobs on 16 queues 0.925 ms per job, 6 jobs on
-# the default 4 queues 0.98 ms, 8 jobs on 4 queues 1.05 ms; with round 2's kernels, frames/s at 16 queues: 6 jobs
-# 2.77 M, 8: 3.08 M, 10: 3.04 M, 12: 3.19 M, 14: 3.16 M, 16: 3.07 M -- the default).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The number of hardware queues the HIP runtime spreads a process's streams over is left to the machine's environment:
+# the GPUs are shared, and a process that opens more queues than the card's slots can destabilise it for everyone on it.
 # RCCL between processes (N > 1): this pool's host driver only supports dmabuf IPC; the boxes export the setting, a
 # launcher that scrubs the environment would otherwise fail in hipIpcGetMemHandle at the first collective
 # -- so the default is applied ONLY where the box exports nothing, and the line says which it was (`environment.hsa_ipc`)
@@ -310,6 +309,31 @@ def rel_err(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300))) if a.size else 0.0
 
 
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  The 3-d ones ([utterance][frame][bin]: sp, ap) are cut
+    to a seeded sample of their (utterance, frame) rows when the whole set would pass DUMP_BYTES; the sample depends on the
+    shapes alone (two builds run with the same arguments dump the same rows) and its flat row indices go to sample_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in host.values()) > DUMP_BYTES:
+        wide = [k for k, a in host.items() if a.ndim == 3]
+        rows = host[wide[0]].shape[0] * host[wide[0]].shape[1]
+        assert all(host[k].shape[0] * host[k].shape[1] == rows for k in wide)
+        room = DUMP_BYTES - 4096 - sum(a.nbytes for k, a in host.items() if k not in wide)     # (4 kB: the .npy headers)
+        keep = min(rows, room // (8 + 8 * sum(host[k].shape[2] for k in wide)))
+        pick = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        for k in wide:
+            host[k] = host[k].reshape(rows, -1)[pick]
+        host["sample_rows"] = pick.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(host)
+
+
 def visible_gpus():
     """devices this process would see, without creating a HIP context in it (the count is taken in a child: a parent that
     is about to become a launcher must not hold the runtime)"""
@@ -337,7 +361,7 @@ def spawn_ranks(args):
             import torch
             have = torch.cuda.device_count()
     else:
-        have = visible_gpus()                                   # about to exec the launcher: count in a child
+        have = visible_gpus()                                   # about to start the launcher: count in a child
     shared_ok = os.environ.get("WORLD_HIP_BENCH_BACKEND") == "gloo"
     if have is not None and have < (1 if shared_ok else args.gpus):
         raise SystemExit(f"bench.py: --gpus {args.gpus} asked for, {have} GPU(s) visible: not running (no CPU path, no fewer-GPU fallback)")
@@ -351,8 +375,11 @@ def spawn_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
     sys.stderr.write("bench.py: --gpus %d without a launcher: " % args.gpus + " ".join(cmd[1:8]) + " ...\n")
     sys.stderr.flush()
-    os.environ["WORLD_HIP_BENCH_SELF_SPAWNED"] = "1"
-    os.execv(sys.executable, cmd)
+    # the launcher runs as a child process (this one never initialised the runtime, but is not replaced either) and its
+    # exit status becomes ours
+    import subprocess
+    r = subprocess.run(cmd, env=dict(os.environ, WORLD_HIP_BENCH_SELF_SPAWNED="1"))
+    sys.exit(r.returncode if r.returncode >= 0 else 128 - r.returncode)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -363,8 +390,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1, help="N = 1: utterances per step of the headline leg")
     ap.add_argument("--seconds", type=float, default=10.0, help="N = 1: utterance length of the headline leg")
-    ap.add_argument("--min-wall", type=float, default=2.0,
-                    help="every timed region repeats its K steps until it has lasted this many seconds")
+    ap.add_argument("--min-wall", type=float, default=0.0,
+                    help="> 0: every timed region repeats its K steps until it has lasted this many seconds "
+                         "(default 0: exactly K timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the last timed step's results of the headline leg to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the configs[2] / [3]-share / [4] legs")
     ap.add_argument("--only-config", type=int, default=0,
@@ -388,8 +418,10 @@ def main():
                     help="independent analysis jobs in flight per GPU (each step is one job on its own HIP "
                          "stream with its own workspace; 1 = strictly one after the other)")
     args = ap.parse_args()
-    if args.gpus < 1:
-        raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.gpus < 1 or args.steps < 1:
+        raise SystemExit("bench.py: --gpus and --steps must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.only_config):
+        raise SystemExit("bench.py: --dump-outputs writes the headline leg of --gpus 1 (not with --gpus N > 1 or --only-config)")
     spawn_ranks(args)                                           # --gpus N > 1 without a launcher: become N ranks (never returns then)
 
     import numpy as np
@@ -899,6 +931,10 @@ def main():
     nsteps = args.steps * repeats
     frames_per_step = nf * B
     value = frames_per_step * nsteps / dt
+    if args.dump_outputs:
+        # what the last timed step's caller received: its slot's (tpos, f0, sp, ap, nf); nothing has run on that slot since
+        tpos_l, f0_l, sp_l, ap_l, nf_l = last[(counter[0] - 1) % S]
+        dump_outputs(args.dump_outputs, {"tpos": tpos_l, "f0": f0_l, "sp": sp_l, "ap": ap_l, "nf": nf_l})
 
     if args.inflight_only:
         torch.cuda.synchronize()

@@ -162,6 +162,35 @@ def high_rate_fixture(R):
     print("vowel192k_harvest.npz", os.path.getsize(os.path.join(OUT, "vowel192k_harvest.npz")) // 1024, "KiB")
 
 
+def helpers_fixture(R):
+    """The reference's host-arithmetic helpers on test_abi's sweep: 2000 (fs, length, frame period, CheapTrick floor) cases --
+    common rates and periods mostly, arbitrary ones otherwise -- and the option defaults (helpers.npz)"""
+    sys.path.insert(0, os.path.dirname(OUT))
+    from util import HELPER_ANSWERS, bind_option_helpers, option_defaults, option_helper_answers
+    L = bind_option_helpers(R.lib)
+    rng = np.random.default_rng(8)
+    rates = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 192000]
+    cases = []
+    for _ in range(2000):
+        fs = int(rng.choice(rates)) if rng.random() < 0.8 else int(rng.integers(4000, 200000))
+        n = int(rng.integers(1, 2_000_000))
+        fp = float(rng.choice([1.0, 2.5, 5.0, 10.0, 12.5])) if rng.random() < 0.8 else float(rng.uniform(0.5, 20.0))
+        cases.append((fs, n, fp, float(rng.uniform(20.0, 300.0))))
+    fs, n, fp, floor = (np.array(c) for c in zip(*cases))
+    answers = np.array([option_helper_answers(L, *c) for c in cases])
+    np.savez_compressed(os.path.join(OUT, "helpers.npz"), fs=fs, n=n, frame_period=fp, f0_floor=floor,
+                        **{k: answers[:, i] for i, k in enumerate(HELPER_ANSWERS)}, **option_defaults(L))
+    print("helpers.npz", os.path.getsize(os.path.join(OUT, "helpers.npz")) // 1024, "KiB")
+
+
+def chirp24k_fixture(R):
+    """24 kHz synthetic chirp, 0.8 s (Harvest's decimation ratio 3; test_oracle's port-against-reference case)"""
+    x = synth.chirp(24000, 0.8, seed=99).numpy()
+    q = np.round(x * 32768.0).astype(np.int16)
+    np.savez_compressed(os.path.join(OUT, "chirp24k_harvest.npz"), **analyse(R, q, 24000, "harvest", 71.0, 8))
+    print("chirp24k_harvest.npz", os.path.getsize(os.path.join(OUT, "chirp24k_harvest.npz")) // 1024, "KiB")
+
+
 def main():
     build()
     R = RefOracle()
@@ -175,6 +204,12 @@ def main():
         return
     if "--high-rate-only" in sys.argv:
         high_rate_fixture(R)
+        return
+    if "--helpers-only" in sys.argv:
+        helpers_fixture(R)
+        return
+    if "--chirp24k-only" in sys.argv:
+        chirp24k_fixture(R)
         return
     if "--codec-only" in sys.argv:
         codec_fixture(R)
@@ -193,6 +228,8 @@ def main():
     q16 = np.round(x * 32768.0).astype(np.int16)
     np.savez_compressed(os.path.join(OUT, "vowel16k_dio.npz"), **analyse(R, q16, 16000, "dio", 71.0, 6))
     high_rate_fixture(R)
+    chirp24k_fixture(R)
+    helpers_fixture(R)
     # primitive known answers
     import ctypes as C
     L = R.lib

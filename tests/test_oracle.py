@@ -65,15 +65,31 @@ def test_reference_reproduces_golden(ref_oracle, name):
     check_against_golden(ref_oracle, load_golden(name), rtol=1e-12)
 
 
-def test_port_matches_reference_fresh_signal(port_oracle, ref_oracle):
-    """A signal that is in no fixture: chirp at 24 kHz (decimation ratio 3)."""
+def test_port_matches_reference_fresh_signal(port_oracle):
+    """A signal in no other fixture: chirp at 24 kHz (decimation ratio 3).  Against the reference's outputs stored in
+    tests/golden/chirp24k_harvest.npz (F0 whole, spectral stages fed the reference's F0: every 8th row whole and every
+    row's checksum), and -- where the in-place build of the reference is present -- against the reference itself, whole."""
+    from oracle.loader import RefOracle, ref_available
     from world_amd import synth
-    x = synth.chirp(24000, 0.8, seed=99).numpy()
-    tp_r, f0_r = ref_oracle.harvest(x, 24000)
-    tp_p, f0_p = port_oracle.harvest(x, 24000)
-    assert np.array_equal(tp_r, tp_p)
-    assert np.sum((f0_r > 0) != (f0_p > 0)) == 0 and max_rel(f0_p[f0_r > 0], f0_r[f0_r > 0]) < 1e-9
-    fft = ref_oracle.cheaptrick_fft_size(24000)
-    assert max_rel(port_oracle.cheaptrick(x, 24000, tp_r, f0_r, fft_size=fft),
-                   ref_oracle.cheaptrick(x, 24000, tp_r, f0_r, fft_size=fft)) < 1e-7
-    assert max_rel(port_oracle.d4c(x, 24000, tp_r, f0_r, fft), ref_oracle.d4c(x, 24000, tp_r, f0_r, fft)) < 1e-7
+    g = load_golden("chirp24k_harvest")
+    x, fs = synth.chirp(24000, 0.8, seed=99).numpy(), 24000
+    assert np.array_equal(x, g["x"])
+    tp_p, f0_p = port_oracle.harvest(x, fs)
+
+    def check(tp_r, f0_r, fft):
+        assert np.array_equal(tp_r, tp_p)
+        assert np.sum((f0_r > 0) != (f0_p > 0)) == 0 and max_rel(f0_p[f0_r > 0], f0_r[f0_r > 0]) < 1e-9
+        return (port_oracle.cheaptrick(x, fs, tp_r, f0_r, fft_size=fft), port_oracle.d4c(x, fs, tp_r, f0_r, fft))
+
+    assert g["fft_size"] == port_oracle.cheaptrick_fft_size(fs)
+    sp, ap = check(g["tp"], g["f0"], g["fft_size"])
+    rows = g["rows"]
+    assert max_rel(sp[rows], g["sp_rows"]) < 1e-7 and max_rel(np.log(sp).sum(axis=1), g["sp_row_sums"]) < 1e-7
+    assert max_rel(ap[rows], g["ap_rows"]) < 1e-7 and max_rel(ap.sum(axis=1), g["ap_row_sums"]) < 1e-7
+    if ref_available():
+        ref = RefOracle()
+        tp_r, f0_r = ref.harvest(x, fs)
+        fft = ref.cheaptrick_fft_size(fs)
+        sp, ap = check(tp_r, f0_r, fft)
+        assert max_rel(sp, ref.cheaptrick(x, fs, tp_r, f0_r, fft_size=fft)) < 1e-7
+        assert max_rel(ap, ref.d4c(x, fs, tp_r, f0_r, fft)) < 1e-7

@@ -90,3 +90,47 @@ def synth_params(fs, nf, fft_size, seed=0):
     ap = np.clip(0.02 + 0.9 * (k[None, :] / (fs / 2.0)) ** 1.5 * (1.0 + 0.2 * np.sin(i / 9.0))[:, None], 0.0, 1.0)
     ap[f0 == 0.0] = 1.0 - 1e-12
     return f0, sp, ap
+
+
+# The host-arithmetic helpers of the reference's C API (frame counts, FFT sizes, floors, band counts, option defaults) for
+# test_abi's sweep; tests/golden/make_golden.py stores the unmodified reference's answers in helpers.npz.
+HELPER_ANSWERS = ("harvest_samples", "dio_samples", "init_q1", "init_f0_floor", "init_fft_size", "fft_size",
+                  "f0_floor_for_fft_size", "aperiodicities")
+OPTION_INITIALISERS = ("InitializeDioOption", "InitializeHarvestOption", "InitializeD4COption")
+
+
+def bind_option_helpers(L):
+    import ctypes
+    from world_amd.api import CheapTrickOption
+    L.GetSamplesForHarvest.argtypes = L.GetSamplesForDIO.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    L.GetFFTSizeForCheapTrick.argtypes = [ctypes.c_int, ctypes.POINTER(CheapTrickOption)]
+    L.GetF0FloorForCheapTrick.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.GetF0FloorForCheapTrick.restype = ctypes.c_double
+    L.InitializeCheapTrickOption.argtypes = [ctypes.c_int, ctypes.POINTER(CheapTrickOption)]
+    L.GetNumberOfAperiodicities.argtypes = [ctypes.c_int]
+    return L
+
+
+def option_helper_answers(L, fs, n, frame_period, f0_floor):
+    """One case of the sweep on a library bound by bind_option_helpers: the values of HELPER_ANSWERS, in order."""
+    import ctypes
+    from world_amd.api import CheapTrickOption
+    o = CheapTrickOption()
+    L.InitializeCheapTrickOption(fs, ctypes.byref(o))
+    init = (o.q1, o.f0_floor, o.fft_size)
+    o.f0_floor = f0_floor
+    size = L.GetFFTSizeForCheapTrick(fs, ctypes.byref(o))
+    return (L.GetSamplesForHarvest(fs, n, frame_period), L.GetSamplesForDIO(fs, n, frame_period), *init, size,
+            L.GetF0FloorForCheapTrick(fs, size), L.GetNumberOfAperiodicities(fs))
+
+
+def option_defaults(L):
+    """The bytes Initialize{Dio,Harvest,D4C}Option write, per initialiser."""
+    import ctypes
+    from world_amd.api import D4COption, DioOption, HarvestOption
+    out = {}
+    for cls, init in zip((DioOption, HarvestOption, D4COption), OPTION_INITIALISERS):
+        a = cls()
+        getattr(L, init)(ctypes.byref(a))
+        out[init] = np.frombuffer(bytes(a), dtype=np.uint8)
+    return out

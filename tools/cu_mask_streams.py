@@ -4,7 +4,6 @@ less to the jobs' narrow kernels than twelve streams that all see 256 CUs?  (pro
 than three kernels resident, a narrow kernel waits ~70 us for a wave slot behind another job's d4c_frame.)
     python tools/cu_mask_streams.py [seconds]"""
 import os as _os, sys as _sys
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
 import ctypes as C
 import sys

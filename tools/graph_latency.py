@@ -5,7 +5,6 @@ bit-identical.  Also replays S graphs on S streams (the bench's jobs-in-flight m
     python tools/graph_latency.py [seconds] [streams]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 from world_amd import synth
 from world_amd.api import WorldHip, cheaptrick_fft_size, frame_count

@@ -2,7 +2,6 @@
 with every slot's job replayed as ONE HIP graph instead of ~45 launches -- does the GPU schedule twelve graphs better
 than twelve streams of eager launches?   python tools/graph_streams.py [streams] [seconds]"""
 import os as _os, sys as _sys
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
 import sys
 import time
