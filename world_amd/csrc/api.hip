@@ -46,19 +46,27 @@ static thread_local std::string g_last_error;
 }
 
 // ---------------------------------------------------------------------------
+// A stage's workspace is written down once, as a carve: the function that takes its arrays from an Arena in order.  Run
+// against a counting arena (no base, no limit) the carve measures the workspace; the context's arena is grown to that
+// and the same carve then runs for real.
 struct Arena {
   char *base = nullptr;
   size_t cap = 0, used = 0;
   void reset() { used = 0; }
-  void skip_to(size_t offset) { used = (offset + 255) & ~size_t(255); }
   template <class T> T *take(size_t count) {
     size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
     if (used + bytes > cap) fail("workspace arena overflow (%zu + %zu > %zu)", used, bytes, cap);
-    T *p = reinterpret_cast<T *>(base + used);
+    T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
     used += bytes;
     return p;
   }
 };
+template <class Carve> static size_t measure(Carve carve) {
+  Arena count;
+  count.cap = SIZE_MAX;
+  carve(count);
+  return count.used;
+}
 
 struct HarvestBands {            // cached per (fs, f0_floor, f0_ceil)
   int fs = 0;
@@ -74,6 +82,22 @@ struct HarvestBands {            // cached per (fs, f0_floor, f0_ceil)
   std::vector<double> band_f0;
 };
 
+struct DioBands {                // cached per (fs, f0_floor, f0_ceil, channels, ratio)
+  int fs = 0, ratio = 0;
+  double f0_floor = 0, f0_ceil = 0, cpo = 0;
+  int nb = 0, cut = 0, max_ntap = 0;
+  double band_f0_first = 0;      // boundary_f0_list[0]
+  double *d_band_f0 = nullptr, *d_taps = nullptr, *d_lowcut = nullptr;
+  int *d_hal = nullptr, *d_off = nullptr;
+};
+
+struct CodecTables {             // the coders' tables of one (fs, fft_size) (reference src/codec.cpp)
+  int fs = 0, fft_size = 0;
+  int *d_knot_code = nullptr, *d_knot_dec = nullptr, *d_knot_ap = nullptr;
+  double *d_frac_code = nullptr, *d_frac_dec = nullptr, *d_frac_ap = nullptr;
+  double *d_wc_re = nullptr, *d_wc_im = nullptr, *d_wd_re = nullptr, *d_wd_im = nullptr;
+};
+
 }  // namespace world_hip
 
 // The small per-call host arrays (lengths, frame counts, row offsets: a few ints per utterance) depend only on the
@@ -83,7 +107,7 @@ struct HarvestBands {            // cached per (fs, f0_floor, f0_ceil)
 // (round 2 staged them through a ring of pinned buffers guarded by events; hipErrorStreamCaptureInvalidated).
 // Slabs are CHAINED, never replaced under a call: a stage uploads several arrays before it launches, and a pointer it
 // already holds must stay valid whatever the later uploads do (a full 4 MB slab used to be freed and
-// reallocated between two uploads of one call).  The whole set is dropped only at the START of a stage (CallScope), with
+// reallocated between two uploads of one call).  The whole set is dropped only at the START of a stage (open_uploads), with
 // the stream drained, once it holds more than kSmallBudget bytes -- a service fed ever-new length vectors then pays one
 // synchronisation per ~16 k distinct arrays instead of growing without bound.  Lookup is a hash of the content.
 struct SmallArrays {
@@ -119,12 +143,15 @@ struct WorldHipContext {
   double *d_ap_frac = nullptr;   // d4c_finish's per-bin interpolation weight and knot (D4cParams::ap_frac / ap_knot), for
   int *d_ap_knot = nullptr;      //   (ap_grid_fs, ap_grid_fft)
   int ap_grid_fs = 0, ap_grid_fft = 0;
-  void *dio_bands = nullptr;     // world_hip::DioBands (cached DIO filter tables)
+  world_hip::DioBands dio_bands;
   double *d_dc_remover = nullptr; // GetDCRemover(fft_size) of the synthesiser
   int dc_remover_len = 0;
   int *d_synth_need = nullptr;   // largest pulse count a synthesis call could not hold (0 = nothing was dropped)
   int synth_pulse_cap = 0;       // caller's capacity per utterance (0 = automatic)
-  void *codec_tables = nullptr;  // world_hip::CodecTableSet (cached interp1 / DCT tables of the coders)
+  std::vector<world_hip::CodecTables> codec_tables;
+  // the device arrays of tab and of the cached tables (bands, d_nuttall .. codec_tables, d_pk): allocated and freed by
+  // put_table / drop_table only, released together when the context goes
+  std::vector<void *> tables;
   SmallArrays small;             // the per-call host arrays, uploaded once per distinct content
   void *xchg_ready = nullptr, *xchg_done = nullptr;   // events of world_hip_allgather_blocks
   double *d_pk = nullptr;        // dense (tpos, f0) of world_hip_analyze_packed: [2][n_utt][f_stride], grow-only
@@ -169,7 +196,25 @@ static void ensure_arena(WorldHipContext *c, size_t bytes) {
   c->arena.cap = cap;
 }
 
-static size_t pad256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+// A cached device table of the context.  Freeing one frees memory a captured graph may point into: the generation moves.
+// The callers drain the stream around a group of replacements (a kernel may still read the old copy).
+template <class T> static void drop_table(WorldHipContext *c, T *&slot) {
+  if (!slot) return;
+  c->tables.erase(std::find(c->tables.begin(), c->tables.end(), static_cast<void *>(slot)));
+  devrt::dfree(slot);
+  slot = nullptr;
+  ++c->generation;
+}
+// `slot` := a fresh device array of n T, filled from `host` on the stream unless that is null
+template <class T> static void put_table(WorldHipContext *c, T *&slot, size_t n, const T *host = nullptr) {
+  drop_table(c, slot);
+  slot = static_cast<T *>(devrt::dmalloc(sizeof(T) * std::max<size_t>(n, 1)));
+  c->tables.push_back(slot);
+  if (host && n) devrt::h2d(slot, host, sizeof(T) * n, c->stream);
+}
+template <class T> static void put_table(WorldHipContext *c, T *&slot, const std::vector<T> &host) {
+  put_table(c, slot, host.size(), host.data());
+}
 
 // The randn() stream is a constant of the algorithm: its first `draws` values live in the device's
 // shared, fully verified table (rng.h / rng_fill.hip), generated once per process and extended on demand.
@@ -188,15 +233,13 @@ static void drop_small_arrays(WorldHipContext *c) {
 }
 // The start of a stage's upload section: the ONLY place the small arrays may be dropped -- no params struct of this
 // stage holds a pointer yet, and the kernels of earlier stages are waited for first.
-struct CallScope {
-  explicit CallScope(WorldHipContext *c, size_t) {
-    if (c->small.held > small_budget() && !devrt::is_capturing(c->stream)) {
-      devrt::sync(c->stream);
-      drop_small_arrays(c);
-      ++c->generation;
-    }
+static void open_uploads(WorldHipContext *c) {
+  if (c->small.held > small_budget() && !devrt::is_capturing(c->stream)) {
+    devrt::sync(c->stream);
+    drop_small_arrays(c);
+    ++c->generation;
   }
-};
+}
 
 static char *small_array(WorldHipContext *c, const void *data, size_t bytes) {
   SmallArrays &sa = c->small;
@@ -248,6 +291,23 @@ static void check_batch(int n_utt, int fs, const void *d_x, int x_stride, const 
   for (int u = 0; u < n_utt; ++u)
     if (x_length[u] <= 0 || x_length[u] > x_stride) fail("x_length[%d]=%d outside (0, x_stride=%d]", u, x_length[u], x_stride);
 }
+// the largest of n_frames[0 .. n_utt), every one checked against [0, f_stride]
+static int max_frame_count(const int *n_frames, int n_utt, int f_stride) {
+  int max_frames = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_frames[u] < 0 || n_frames[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
+    max_frames = std::max(max_frames, n_frames[u]);
+  }
+  return max_frames;
+}
+static BatchView batch_view(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
+                            const int *n_frames, int f_stride) {
+  BatchView b;
+  b.n_utt = n_utt; b.fs = fs; b.x_stride = x_stride; b.f_stride = f_stride; b.x = d_x;
+  b.x_len = upload(c, std::vector<int>(x_length, x_length + n_utt));
+  b.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  return b;
+}
 
 // Where a per-frame stage writes its rows: the dense [n_utt][f_stride][bins] array of the batched API (rows == nullptr),
 // or rows of packed records -- frame f of utterance u at row rows[u] + f, `stride` doubles apart (exchange.hip's layout,
@@ -275,10 +335,6 @@ static int record_cols(int fft_size, int wire) {
   return wire == 1 ? 2 + nb : 2 + 2 * nb;
 }
 
-static size_t cheaptrick_arena_bytes(int n_utt, int f_stride, int fft_size) {
-  (void)fft_size;       // the frame kernel keeps everything between x and the spectrogram in LDS: no per-frame scratch
-  return pad256(sizeof(unsigned) * (size_t)n_utt * f_stride) + 4 * pad256(sizeof(int) * n_utt);
-}
 // (d4c.cpp:350-351) fft_size_d4c, the transform of the frame kernel
 static int d4c_internal_fft(int fs) { return static_cast<int>(pow(2.0, 1.0 + static_cast<int>(log(4.0 * fs / kFloorF0D4C + 1) / kLog2))); }
 // workgroups per d4c_frame launch of the 16384-point shape (each parks its group delay in a slot of global memory,
@@ -286,12 +342,18 @@ static int d4c_internal_fft(int fs) { return static_cast<int>(pow(2.0, 1.0 + sta
 static int d4c_park_slots(int n_utt, int f_stride) {
   return static_cast<int>(std::min<size_t>((size_t)n_utt * f_stride, (size_t)std::max(n_utt, 2048)));
 }
-static size_t d4c_arena_bytes(int n_utt, int f_stride, int fs) {
-  const size_t fr = (size_t)n_utt * f_stride;
-  int lg = 0;
-  while ((1 << lg) < d4c_internal_fft(fs)) ++lg;
-  return 2 * pad256(sizeof(unsigned) * fr) + pad256(sizeof(double) * fr) + 6 * pad256(sizeof(int) * n_utt) + 512 +
-         pad256(sizeof(double) * fr * 16) + pad256(sizeof(double) * d4c_park_slot_doubles(lg) * d4c_park_slots(n_utt, f_stride));
+
+static void arena_reset(WorldHipContext *c) {
+  c->arena.reset();
+  c->prep_ct.valid = c->prep_d4c.valid = false;
+}
+// The start of every stage but CheapTrick and D4C: the arena grown to what `carve` measures and carved for real, the
+// prepared offsets voided (whatever they were computed for is overwritten), the upload section opened.
+template <class Carve> static void begin_stage(WorldHipContext *c, Carve carve) {
+  ensure_arena(c, measure(carve));
+  arena_reset(c);
+  carve(c->arena);
+  open_uploads(c);
 }
 
 // ---------------------------------------------------------------------------
@@ -300,10 +362,6 @@ static size_t d4c_arena_bytes(int n_utt, int f_stride, int fs) {
 // LoveTrain pass -- survive the other stage's calls, one prepare kernel can serve both (run_spectral_stages), and frame
 // ranges of the two stages can alternate while reusing them.  Any other stage's arena_reset() voids them.
 // ---------------------------------------------------------------------------
-static void arena_reset(WorldHipContext *c) {
-  c->arena.reset();
-  c->prep_ct.valid = c->prep_d4c.valid = false;
-}
 static uint64_t lengths_hash(const int *x_length, const int *n_frames, int n_utt) {
   const uint64_t a = SmallArrays::hash(x_length, sizeof(int) * n_utt), b = SmallArrays::hash(n_frames, sizeof(int) * n_utt);
   return a * 0x9E3779B97F4A7C15ull ^ b;
@@ -326,6 +384,46 @@ static void claim_prepared(WorldHipContext *c, WorldHipContext::PrepToken &mine,
   mine = want;
   mine.valid = true;
 }
+static void carve_cheaptrick(Arena &a, CtParams &p) {
+  // the frame kernel keeps everything between x and the spectrogram in LDS: no per-frame scratch
+  p.offsets = a.take<unsigned>((size_t)p.b.n_utt * p.b.f_stride);
+}
+static void carve_d4c(Arena &a, D4cParams &p) {
+  CtParams below;
+  below.b = p.b;
+  carve_cheaptrick(a, below);                                          // behind CheapTrick's part for this shape
+  const size_t fr = (size_t)p.b.n_utt * p.b.f_stride;
+  p.ap0 = a.take<double>(fr);
+  p.offsets1 = a.take<unsigned>(fr);
+  p.draws2 = a.take<unsigned>(fr);
+  p.draws1 = a.take<unsigned>(p.b.n_utt);
+  p.coarse = a.take<double>(fr * 16);
+  const size_t slot = d4c_park_slot_doubles(p.lg_d4c);
+  p.park_ws = slot ? a.take<double>(slot * p.park_slots) : nullptr;
+}
+// A call of CheapTrick and / or D4C: the arena grown to what the carves measure (D4C's includes CheapTrick's part), each
+// stage's arrays carved, and its claim on them made -- or, with skip_prepare, checked
+static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c, const int *x_length, const int *n_frames) {
+  ensure_arena(c, d4c ? measure([&](Arena &a) { carve_d4c(a, *d4c); }) : measure([&](Arena &a) { carve_cheaptrick(a, *ct); }));
+  const BatchView &b = ct ? ct->b : d4c->b;
+  WorldHipContext::PrepToken t;
+  t.n_utt = b.n_utt; t.fs = b.fs; t.f_stride = b.f_stride; t.x_stride = b.x_stride; t.x = b.x;
+  t.lengths_hash = lengths_hash(x_length, n_frames, b.n_utt);
+  if (ct) {
+    c->arena.reset();
+    carve_cheaptrick(c->arena, *ct);
+    t.fft = 1 << ct->lg_fft; t.f0 = ct->f0; t.tpos = ct->tpos; t.opt = ct->f0_floor;
+    t.lo = 0; t.hi = c->arena.used;
+    claim_prepared(c, c->prep_ct, c->prep_d4c, t, ct->skip_prepare != 0, "CheapTrick");
+  }
+  if (d4c) {
+    c->arena.reset();
+    carve_d4c(c->arena, *d4c);
+    t.fft = d4c->fft_out; t.f0 = d4c->f0; t.tpos = d4c->tpos; t.opt = d4c->threshold;
+    t.lo = reinterpret_cast<char *>(d4c->ap0) - c->arena.base; t.hi = c->arena.used;      // (ap0: D4C's first array)
+    claim_prepared(c, c->prep_d4c, c->prep_ct, t, d4c->skip_prepare != 0, "D4C");
+  }
+}
 
 // ---------------------------------------------------------------------------
 // CheapTrick
@@ -337,16 +435,9 @@ static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const do
   check_batch(n_utt, fs, d_x, x_stride, x_length);
   const int lg = ilog2_exact(opt->fft_size);
   if (lg < 7 || lg > 13) fail("CheapTrick fft_size %d unsupported (128..8192: one frame must fit LDS)", opt->fft_size);
-  int max_frames = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    if (n_frames[u] < 0 || n_frames[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
-    max_frames = std::max(max_frames, n_frames[u]);
-  }
-  *max_frames_out = max_frames;
+  const int max_frames = *max_frames_out = max_frame_count(n_frames, n_utt, f_stride);
   CtParams p;
-  p.b.n_utt = n_utt; p.b.fs = fs; p.b.x_stride = x_stride; p.b.f_stride = f_stride; p.b.x = d_x;
-  p.b.x_len = upload(c, std::vector<int>(x_length, x_length + n_utt));
-  p.b.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride);
   p.tpos = d_tpos; p.f0 = d_f0; p.spectrogram = d_sp;
   p.out_row = lay.rows ? upload(c, std::vector<int>(lay.rows, lay.rows + n_utt)) : nullptr;
   p.out_stride = lay.stride ? lay.stride : (size_t)(opt->fft_size / 2 + 1);
@@ -355,15 +446,6 @@ static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const do
   p.code_w_re = lay.code_w_re; p.code_w_im = lay.code_w_im;
   if (p.code_ndim > 0 && (lay.f32 || !lay.code_knot || p.code_ndim > opt->fft_size / 4 + 1)) fail("CheapTrick: bad coded-row layout");
   p.f0_floor = 3.0 * fs / (opt->fft_size - 3.0);                       // cheaptrick.cpp:196-198
-  c->arena.skip_to(0);
-  p.offsets = c->arena.take<unsigned>((size_t)n_utt * f_stride);
-  {
-    WorldHipContext::PrepToken t;
-    t.n_utt = n_utt; t.fs = fs; t.f_stride = f_stride; t.x_stride = x_stride; t.fft = opt->fft_size;
-    t.x = d_x; t.f0 = d_f0; t.tpos = d_tpos; t.opt = p.f0_floor; t.lengths_hash = lengths_hash(x_length, n_frames, n_utt);
-    t.lo = 0; t.hi = c->arena.used;
-    claim_prepared(c, c->prep_ct, c->prep_d4c, t, lay.skip_prepare, "CheapTrick");
-  }
   p.noise = ensure_noise(c, (size_t)max_frames * ct_max_draws_per_frame(opt->fft_size));
   p.tab = c->tab;
   p.q1 = opt->q1;
@@ -376,11 +458,11 @@ static void run_cheaptrick(WorldHipContext *c, int n_utt, int fs, const double *
                            const int *x_length, const int *n_frames, int f_stride, const double *d_tpos,
                            const double *d_f0, const CheapTrickOption *opt, double *d_sp,
                            const RowLayout &lay = RowLayout()) {
-  ensure_arena(c, cheaptrick_arena_bytes(n_utt, f_stride, opt->fft_size));
-  CallScope scope(c, 3 * sizeof(int) * n_utt + 256);
+  open_uploads(c);
   int max_frames = 0;
-  const CtParams p = setup_cheaptrick(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, opt, d_sp, lay,
-                                      &max_frames);
+  CtParams p = setup_cheaptrick(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, opt, d_sp, lay,
+                                &max_frames);
+  spectral_workspace(c, &p, nullptr, x_length, n_frames);
   launch_cheaptrick(p, max_frames, c->stream);
 }
 
@@ -392,12 +474,7 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
                            const D4COption *opt, double *d_ap, const RowLayout &lay, int *max_frames_out) {
   check_batch(n_utt, fs, d_x, x_stride, x_length);
   ilog2_exact(fft_size);
-  int max_frames = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    if (n_frames[u] < 0 || n_frames[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
-    max_frames = std::max(max_frames, n_frames[u]);
-  }
-  *max_frames_out = max_frames;
+  const int max_frames = *max_frames_out = max_frame_count(n_frames, n_utt, f_stride);
   // d4c.cpp:350-363 and :264-265
   const int fft_d4c = d4c_internal_fft(fs);
   const int fft_love = static_cast<int>(pow(2.0, 1.0 + static_cast<int>(log(3.0 * fs / 40.0 + 1) / kLog2)));
@@ -414,9 +491,7 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
       w[i] = 0.355768 - 0.487396 * cos(2.0 * kPi * t) + 0.144232 * cos(4.0 * kPi * t) - 0.012604 * cos(6.0 * kPi * t);
     }
     devrt::sync(c->stream);
-    if (c->d_nuttall) { devrt::dfree(c->d_nuttall); ++c->generation; }
-    c->d_nuttall = static_cast<double *>(devrt::dmalloc(sizeof(double) * wl));
-    devrt::h2d(c->d_nuttall, w.data(), sizeof(double) * wl, c->stream);
+    put_table(c, c->d_nuttall, w);
     devrt::sync(c->stream);
     c->nuttall_len = wl;
   }
@@ -441,19 +516,13 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
       frac[i] = (xi - x0) / (x1 - x0);
     }
     devrt::sync(c->stream);
-    if (c->d_ap_frac) { devrt::dfree(c->d_ap_frac); devrt::dfree(c->d_ap_knot); ++c->generation; }
-    c->d_ap_frac = static_cast<double *>(devrt::dmalloc(sizeof(double) * nb_out));
-    c->d_ap_knot = static_cast<int *>(devrt::dmalloc(sizeof(int) * nb_out));
-    devrt::h2d(c->d_ap_frac, frac.data(), sizeof(double) * nb_out, c->stream);
-    devrt::h2d(c->d_ap_knot, knot.data(), sizeof(int) * nb_out, c->stream);
+    put_table(c, c->d_ap_frac, frac);
+    put_table(c, c->d_ap_knot, knot);
     devrt::sync(c->stream);
     c->ap_grid_fs = fs; c->ap_grid_fft = fft_size;
   }
-  size_t fr = (size_t)n_utt * f_stride;
   D4cParams p;
-  p.b.n_utt = n_utt; p.b.fs = fs; p.b.x_stride = x_stride; p.b.f_stride = f_stride; p.b.x = d_x;
-  p.b.x_len = upload(c, std::vector<int>(x_length, x_length + n_utt));
-  p.b.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride);
   p.tpos = d_tpos; p.f0 = d_f0; p.aperiodicity = d_ap;
   p.out_row = lay.rows ? upload(c, std::vector<int>(lay.rows, lay.rows + n_utt)) : nullptr;
   p.out_stride = lay.stride ? lay.stride : (size_t)(fft_size / 2 + 1);
@@ -461,25 +530,7 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
   p.code_nap = lay.code_dims;
   if (p.code_nap > 0 && lay.f32) fail("D4C: bad coded-row layout");
   p.rec = lay.rec;
-  c->arena.skip_to(cheaptrick_arena_bytes(n_utt, f_stride, fft_size));      // behind CheapTrick's part for this shape
-  const size_t region_lo = c->arena.used;
-  p.ap0 = c->arena.take<double>(fr);
-  p.offsets1 = c->arena.take<unsigned>(fr);
-  p.draws2 = c->arena.take<unsigned>(fr);
-  p.draws1 = c->arena.take<unsigned>(n_utt);
-  p.coarse = c->arena.take<double>(fr * 16);
   p.park_slots = d4c_park_slots(n_utt, f_stride);
-  {
-    const size_t slot = d4c_park_slot_doubles(ilog2_exact(fft_d4c));
-    p.park_ws = slot ? c->arena.take<double>(slot * p.park_slots) : nullptr;
-  }
-  {
-    WorldHipContext::PrepToken t;
-    t.n_utt = n_utt; t.fs = fs; t.f_stride = f_stride; t.x_stride = x_stride; t.fft = fft_size;
-    t.x = d_x; t.f0 = d_f0; t.tpos = d_tpos; t.opt = opt->threshold; t.lengths_hash = lengths_hash(x_length, n_frames, n_utt);
-    t.lo = region_lo; t.hi = c->arena.used;
-    claim_prepared(c, c->prep_d4c, c->prep_ct, t, lay.skip_prepare, "D4C");
-  }
   p.noise = ensure_noise(c, (size_t)max_frames * d4c_max_draws_per_frame(fs));
   p.nuttall = c->d_nuttall;
   p.ap_frac = c->d_ap_frac; p.ap_knot = c->d_ap_knot;
@@ -501,11 +552,11 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
 static void run_d4c(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
                     const int *n_frames, int f_stride, const double *d_tpos, const double *d_f0, int fft_size,
                     const D4COption *opt, double *d_ap, const RowLayout &lay = RowLayout()) {
-  ensure_arena(c, cheaptrick_arena_bytes(n_utt, f_stride, fft_size) + d4c_arena_bytes(n_utt, f_stride, fs));
-  CallScope scope(c, 3 * sizeof(int) * n_utt + 256);
+  open_uploads(c);
   int max_frames = 0;
-  const D4cParams p = setup_d4c(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, fft_size, opt, d_ap,
-                                lay, &max_frames);
+  D4cParams p = setup_d4c(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, fft_size, opt, d_ap,
+                          lay, &max_frames);
+  spectral_workspace(c, nullptr, &p, x_length, n_frames);
   launch_d4c(p, max_frames, c->stream);
 }
 
@@ -537,25 +588,20 @@ static void prepare_bands(WorldHipContext *c, int fs, double f0_floor, double f0
     }
   }
   devrt::sync(c->stream);
-  ++c->generation;
-  if (hb.d_band_f0) { devrt::dfree(hb.d_band_f0); devrt::dfree(hb.d_taps); devrt::dfree(hb.d_half); devrt::dfree(hb.d_off); }
-  hb.d_band_f0 = static_cast<double *>(devrt::dmalloc(sizeof(double) * nch));
-  hb.d_taps = static_cast<double *>(devrt::dmalloc(sizeof(double) * taps.size()));
-  hb.d_half = static_cast<int *>(devrt::dmalloc(sizeof(int) * nch));
-  hb.d_off = static_cast<int *>(devrt::dmalloc(sizeof(int) * nch));
-  devrt::h2d(hb.d_band_f0, fb.data(), sizeof(double) * nch, c->stream);
-  devrt::h2d(hb.d_taps, taps.data(), sizeof(double) * taps.size(), c->stream);
-  devrt::h2d(hb.d_half, half.data(), sizeof(int) * nch, c->stream);
-  devrt::h2d(hb.d_off, off.data(), sizeof(int) * nch, c->stream);
+  put_table(c, hb.d_band_f0, fb);
+  put_table(c, hb.d_taps, taps);
+  put_table(c, hb.d_half, half);
+  put_table(c, hb.d_off, off);
   devrt::sync(c->stream);
   hb.fs = fs; hb.f0_floor = f0_floor; hb.f0_ceil = f0_ceil; hb.nch = nch; hb.max_half = max_half;
   hb.band_f0 = fb;
-  if (hb.d_spec) { devrt::dfree(hb.d_spec); hb.d_spec = nullptr; }
   hb.fft_seg = getenv("WORLD_HIP_HARVEST_FIR") ? 0 : hv_fft_segment(max_half);
   if (hb.fft_seg > 0) {
-    hb.d_spec = static_cast<double2 *>(devrt::dmalloc(sizeof(double2) * (size_t)nch * kBandFftBins));
+    put_table(c, hb.d_spec, (size_t)nch * kBandFftBins);
     launch_band_spectra(hb.d_taps, hb.d_off, hb.d_half, nch, hb.d_spec, c->tab, c->stream);
     devrt::sync(c->stream);
+  } else {
+    drop_table(c, hb.d_spec);
   }
   // GetMainWindow's angles for every window half length hv_refine can meet (harvest.cpp:446-456), d = 2/(2hw+1):
   //   [hw][6]        sin/cos(pi d), sin/cos(pi WAVE d), 2 / window length in seconds, pi d
@@ -612,9 +658,7 @@ static void prepare_bands(WorldHipContext *c, int fs, double f0_floor, double f0
       }
     }
   }
-  if (hb.d_win_tab) devrt::dfree(hb.d_win_tab);
-  hb.d_win_tab = static_cast<double *>(devrt::dmalloc(sizeof(double) * wt.size()));
-  devrt::h2d(hb.d_win_tab, wt.data(), sizeof(double) * wt.size(), c->stream);
+  put_table(c, hb.d_win_tab, wt);
   devrt::sync(c->stream);
   hb.win_tab_len = hw_max + 1;
 }
@@ -688,67 +732,44 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   p.ev_u0 = 0;
   const size_t E = p.ev_group;
   const size_t cand_elems = B * p.fb_stride * p.maxc;
-  size_t need = 0;
-  need += 5 * pad256(sizeof(int) * B) + pad256(sizeof(double) * B * ((max_y + 4095) / 4096) * 4) +
-          pad256(sizeof(double) * B * ((max_y + 4095) / 4096 + (max_x + 2 * p.lag + 2 * kDecPad) / kDecSpan + 1)) +
-          pad256(sizeof(double) * B * p.nch * 4);
-  need += pad256(sizeof(double) * B * p.m_stride);
-  need += pad256(sizeof(double) * B * p.y_stride);
-  need += pad256(sizeof(double) * E * p.nch * 4 * p.ev_cap);
-  need += pad256(sizeof(int) * E * p.nch * 4);
-  if (!direct_lists) {
-    need += pad256(sizeof(double) * E * p.nch * 4 * p.nseg * p.seg_cap);
-    need += pad256(sizeof(int) * E * p.nch * 4 * p.nseg);
-  }
-  need += pad256(sizeof(double2) * B * p.nblk * kBandFftBins);
-  need += pad256(sizeof(double) * B * p.nch * p.fb_stride);
-  need += 4 * pad256(sizeof(double) * cand_elems);
-  need += pad256(sizeof(int) * B);
-  need += 4 * pad256(sizeof(double) * B * p.fb_stride);
-  need += pad256(sizeof(int) * B * 6 * p.sec_cap) + pad256(sizeof(int) * B * 2) + pad256(sizeof(double) * B * p.sec_cap);
-  need += pad256(sizeof(double) * B * p.ext_cap);
-  ensure_arena(c, need);
-  arena_reset(c);
-  CallScope scope(c, 5 * sizeof(int) * n_utt + 512);
-
-  p.b.n_utt = n_utt; p.b.fs = fs; p.b.x_stride = x_stride; p.b.f_stride = f_stride; p.b.x = d_x;
-  p.b.x_len = upload(c, xl);
-  p.b.n_frames = upload(c, nfr);
+  p.nyq_slices = (max_y + 4095) / 4096;                                // kMeanSlice of harvest.hip
+  // launch_harvest's grids: spans of the decimation sweeps (harvest.hip), or the 4096-sample slices at ratio 1
+  p.mean_parts = p.ratio == 1 ? p.nyq_slices : (max_x + 2 * p.lag + 2 * kDecPad + kDecSpan - 1) / kDecSpan;
+  begin_stage(c, [&](Arena &a) {
+    p.nyq = a.take<double>(B * p.nyq_slices * 4);
+    p.mean_part = a.take<double>(B * p.mean_parts);
+    p.quirk = a.take<double>(B * p.nch * 4);
+    p.fwd = a.take<double>(B * p.m_stride);
+    p.y = a.take<double>(B * p.y_stride);
+    p.events = a.take<double>(E * p.nch * 4 * p.ev_cap);
+    p.ev_count = a.take<int>(E * p.nch * 4);
+    if (direct_lists) {
+      p.seg_events = p.events; p.seg_count = p.ev_count;
+    } else {
+      p.seg_events = a.take<double>(E * p.nch * 4 * p.nseg * p.seg_cap);
+      p.seg_count = a.take<int>(E * p.nch * 4 * p.nseg);
+    }
+    p.blk_spec = a.take<double2>(B * p.nblk * kBandFftBins);
+    p.raw = a.take<double>(B * p.nch * p.fb_stride);
+    p.cand_a = a.take<double>(cand_elems); p.score_a = a.take<double>(cand_elems);
+    p.cand_b = a.take<double>(cand_elems); p.score_b = a.take<double>(cand_elems);
+    p.nc = a.take<int>(B);
+    p.c0 = a.take<double>(B * p.fb_stride);
+    p.c2 = a.take<double>(B * p.fb_stride); p.c3 = a.take<double>(B * p.fb_stride);
+    p.basic_f0 = a.take<double>(B * p.fb_stride);
+    p.sec = a.take<int>(B * 6 * p.sec_cap);
+    p.sec_n = a.take<int>(B * 2);
+    p.sec_sum = a.take<double>(B * p.sec_cap);
+    p.ext = a.take<double>(B * p.ext_cap);
+  });
+  p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, nfr.data(), f_stride);
   p.y_len = upload(c, yl);
   p.nfb = upload(c, nfb);
   p.ref_fft = upload(c, rfft);
-  p.nyq_slices = (max_y + 4095) / 4096;                                // kMeanSlice of harvest.hip
-  p.nyq = c->arena.take<double>(B * p.nyq_slices * 4);
-  // launch_harvest's grids: spans of the decimation sweeps (harvest.hip), or the 4096-sample slices at ratio 1
-  p.mean_parts = p.ratio == 1 ? p.nyq_slices : (max_x + 2 * p.lag + 2 * kDecPad + kDecSpan - 1) / kDecSpan;
-  p.mean_part = c->arena.take<double>(B * p.mean_parts);
-  p.quirk = c->arena.take<double>(B * p.nch * 4);
   p.band_f0 = hb.d_band_f0; p.band_half = hb.d_half; p.band_off = hb.d_off; p.band_taps = hb.d_taps;
   p.win_tab = hb.d_win_tab; p.win_lane = hb.d_win_tab + (size_t)hb.win_tab_len * 6;
   p.win_full = hb.win_full_entries && !getenv("WORLD_HIP_REFINE_ROTATE")
                    ? reinterpret_cast<const double2 *>(p.win_lane + (size_t)hb.win_tab_len * WAVE * 2) : nullptr;
-  p.fwd = c->arena.take<double>(B * p.m_stride);
-  p.y = c->arena.take<double>(B * p.y_stride);
-  p.events = c->arena.take<double>(E * p.nch * 4 * p.ev_cap);
-  p.ev_count = c->arena.take<int>(E * p.nch * 4);
-  if (direct_lists) {
-    p.seg_events = p.events; p.seg_count = p.ev_count;
-  } else {
-    p.seg_events = c->arena.take<double>(E * p.nch * 4 * p.nseg * p.seg_cap);
-    p.seg_count = c->arena.take<int>(E * p.nch * 4 * p.nseg);
-  }
-  p.blk_spec = c->arena.take<double2>(B * p.nblk * kBandFftBins);
-  p.raw = c->arena.take<double>(B * p.nch * p.fb_stride);
-  p.cand_a = c->arena.take<double>(cand_elems); p.score_a = c->arena.take<double>(cand_elems);
-  p.cand_b = c->arena.take<double>(cand_elems); p.score_b = c->arena.take<double>(cand_elems);
-  p.nc = c->arena.take<int>(B);
-  p.c0 = c->arena.take<double>(B * p.fb_stride);
-  p.c2 = c->arena.take<double>(B * p.fb_stride); p.c3 = c->arena.take<double>(B * p.fb_stride);
-  p.basic_f0 = c->arena.take<double>(B * p.fb_stride);
-  p.sec = c->arena.take<int>(B * 6 * p.sec_cap);
-  p.sec_n = c->arena.take<int>(B * 2);
-  p.sec_sum = c->arena.take<double>(B * p.sec_cap);
-  p.ext = c->arena.take<double>(B * p.ext_cap);
   p.tpos = d_tpos; p.f0 = d_f0;
   launch_harvest(p, max_x, max_y, max_fb, max_fr, c->stream);
 #ifdef WORLD_EMU
@@ -775,16 +796,8 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
 // ---------------------------------------------------------------------------
 // DIO / StoneMask
 // ---------------------------------------------------------------------------
-struct DioBands {                // cached per (fs, f0_floor, f0_ceil, channels, ratio)
-  int fs = 0, ratio = 0;
-  double f0_floor = 0, f0_ceil = 0, cpo = 0;
-  int nb = 0, cut = 0, max_ntap = 0;
-  double band_f0_first = 0;      // boundary_f0_list[0]
-  double *d_band_f0 = nullptr, *d_taps = nullptr, *d_lowcut = nullptr;
-  int *d_hal = nullptr, *d_off = nullptr;
-};
-
-static void prepare_dio_bands(WorldHipContext *c, DioBands &db, int fs, const DioOption *opt, int ratio) {
+static void prepare_dio_bands(WorldHipContext *c, int fs, const DioOption *opt, int ratio) {
+  DioBands &db = c->dio_bands;
   if (db.fs == fs && db.ratio == ratio && db.f0_floor == opt->f0_floor && db.f0_ceil == opt->f0_ceil &&
       db.cpo == opt->channels_in_octave && db.nb > 0)
     return;
@@ -816,21 +829,11 @@ static void prepare_dio_bands(WorldHipContext *c, DioBands &db, int fs, const Di
   for (int i = 0; i < n; ++i) lowcut[i] = -lowcut[i] / sum;
   lowcut[cut] += 1.0;
   devrt::sync(c->stream);
-  ++c->generation;
-  if (db.d_band_f0) {
-    devrt::dfree(db.d_band_f0); devrt::dfree(db.d_taps); devrt::dfree(db.d_lowcut); devrt::dfree(db.d_hal);
-    devrt::dfree(db.d_off);
-  }
-  db.d_band_f0 = static_cast<double *>(devrt::dmalloc(sizeof(double) * nb));
-  db.d_taps = static_cast<double *>(devrt::dmalloc(sizeof(double) * taps.size()));
-  db.d_lowcut = static_cast<double *>(devrt::dmalloc(sizeof(double) * n));
-  db.d_hal = static_cast<int *>(devrt::dmalloc(sizeof(int) * nb));
-  db.d_off = static_cast<int *>(devrt::dmalloc(sizeof(int) * nb));
-  devrt::h2d(db.d_band_f0, fb.data(), sizeof(double) * nb, c->stream);
-  devrt::h2d(db.d_taps, taps.data(), sizeof(double) * taps.size(), c->stream);
-  devrt::h2d(db.d_lowcut, lowcut.data(), sizeof(double) * n, c->stream);
-  devrt::h2d(db.d_hal, hal.data(), sizeof(int) * nb, c->stream);
-  devrt::h2d(db.d_off, off.data(), sizeof(int) * nb, c->stream);
+  put_table(c, db.d_band_f0, fb);
+  put_table(c, db.d_taps, taps);
+  put_table(c, db.d_lowcut, lowcut);
+  put_table(c, db.d_hal, hal);
+  put_table(c, db.d_off, off);
   devrt::sync(c->stream);
   db.fs = fs; db.ratio = ratio; db.f0_floor = opt->f0_floor; db.f0_ceil = opt->f0_ceil;
   db.cpo = opt->channels_in_octave; db.nb = nb; db.cut = cut; db.max_ntap = max_ntap;
@@ -846,8 +849,8 @@ static void run_dio(WorldHipContext *c, int n_utt, int fs, const double *d_x, in
   DioParams p;
   p.ratio = std::max(std::min(opt->speed, 12), 1);                    // dio.cpp:589
   p.afs = static_cast<double>(fs) / p.ratio;
-  DioBands &db = *reinterpret_cast<DioBands *>(c->dio_bands);
-  prepare_dio_bands(c, db, fs, opt, p.ratio);
+  prepare_dio_bands(c, fs, opt, p.ratio);
+  const DioBands &db = c->dio_bands;
   p.f0_floor = opt->f0_floor; p.f0_ceil = opt->f0_ceil; p.frame_period = opt->frame_period;
   p.allowed_range = opt->allowed_range;
   p.nb = db.nb; p.cut = db.cut; p.max_ntap = db.max_ntap;
@@ -874,36 +877,26 @@ static void run_dio(WorldHipContext *c, int n_utt, int fs, const double *d_x, in
   p.nseg = band_segments(max_y);
   p.ev_cap = max_y / 2 + 2;
   const size_t B = n_utt;
-  const size_t seg_list = (size_t)p.nseg * kSegCap;
-  size_t need = 5 * pad256(sizeof(int) * B) + pad256(sizeof(double) * B * 4) + pad256(sizeof(double) * B * p.nb * 4);
-  need += pad256(sizeof(double) * B * p.m_stride) + pad256(sizeof(double) * B * p.y_stride) +
-          pad256(sizeof(double) * B * p.z_stride);
-  need += pad256(sizeof(double) * B * p.nb * 4 * seg_list) + pad256(sizeof(int) * B * p.nb * 4 * p.nseg);
-  need += pad256(sizeof(double) * B * p.nb * 4 * p.ev_cap) + pad256(sizeof(int) * B * p.nb * 4);
-  need += 2 * pad256(sizeof(double) * B * p.nb * f_stride) + 2 * pad256(sizeof(double) * B * f_stride);
-  ensure_arena(c, need);
-  arena_reset(c);
-  CallScope scope(c, 4 * sizeof(int) * n_utt + 512);
-  p.b.n_utt = n_utt; p.b.fs = fs; p.b.x_stride = x_stride; p.b.f_stride = f_stride; p.b.x = d_x;
-  p.b.x_len = upload(c, xl);
-  p.b.n_frames = upload(c, nfr);
+  begin_stage(c, [&](Arena &a) {
+    p.nyq = a.take<double>(B * 4);
+    p.quirk = a.take<double>(B * p.nb * 4);
+    p.fwd = a.take<double>(B * p.m_stride);
+    p.y = a.take<double>(B * p.y_stride);
+    p.z = a.take<double>(B * p.z_stride);
+    p.seg_events = a.take<double>(B * p.nb * 4 * p.nseg * kSegCap);
+    p.seg_count = a.take<int>(B * p.nb * 4 * p.nseg);
+    p.events = a.take<double>(B * p.nb * 4 * p.ev_cap);
+    p.ev_count = a.take<int>(B * p.nb * 4);
+    p.cand = a.take<double>(B * p.nb * f_stride);
+    p.score = a.take<double>(B * p.nb * f_stride);
+    p.t1 = a.take<double>(B * f_stride);
+    p.t2 = a.take<double>(B * f_stride);
+  });
+  p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, nfr.data(), f_stride);
   p.y_len = upload(c, yl);
   p.ref_fft = upload(c, rfft);
-  p.nyq = c->arena.take<double>(B * 4);
-  p.quirk = c->arena.take<double>(B * p.nb * 4);
   p.band_f0 = db.d_band_f0; p.band_hal = db.d_hal; p.band_off = db.d_off; p.band_taps = db.d_taps;
   p.lowcut_taps = db.d_lowcut;
-  p.fwd = c->arena.take<double>(B * p.m_stride);
-  p.y = c->arena.take<double>(B * p.y_stride);
-  p.z = c->arena.take<double>(B * p.z_stride);
-  p.seg_events = c->arena.take<double>(B * p.nb * 4 * seg_list);
-  p.seg_count = c->arena.take<int>(B * p.nb * 4 * p.nseg);
-  p.events = c->arena.take<double>(B * p.nb * 4 * p.ev_cap);
-  p.ev_count = c->arena.take<int>(B * p.nb * 4);
-  p.cand = c->arena.take<double>(B * p.nb * f_stride);
-  p.score = c->arena.take<double>(B * p.nb * f_stride);
-  p.t1 = c->arena.take<double>(B * f_stride);
-  p.t2 = c->arena.take<double>(B * f_stride);
   p.tpos = d_tpos; p.f0 = d_f0;
   launch_dio(p, max_x, max_y, max_fr, c->stream);
 }
@@ -912,22 +905,14 @@ static void run_stonemask(WorldHipContext *c, int n_utt, int fs, const double *d
                           const int *x_length, const int *n_frames, int f_stride, const double *d_tpos,
                           const double *d_f0, double *d_refined) {
   check_batch(n_utt, fs, d_x, x_stride, x_length);
-  int max_frames = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    if (n_frames[u] < 0 || n_frames[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
-    max_frames = std::max(max_frames, n_frames[u]);
-  }
+  const int max_frames = max_frame_count(n_frames, n_utt, f_stride);
   StoneMaskParams p;
   p.win_cap = 2 * static_cast<int>(1.5 * fs / 40.0 + 1.0) + 4;       // longest window: f0 just above 40 Hz
   if (stonemask_lds_bytes(p.win_cap) > 160 * 1024)
     fail("StoneMask: fs=%d needs a %d-sample window (%zu bytes of LDS > 160 KiB); fs <= 240 kHz supported", fs, p.win_cap,
          stonemask_lds_bytes(p.win_cap));
-  ensure_arena(c, 2 * pad256(sizeof(int) * n_utt));
-  arena_reset(c);
-  CallScope scope(c, 2 * sizeof(int) * n_utt + 256);
-  p.b.n_utt = n_utt; p.b.fs = fs; p.b.x_stride = x_stride; p.b.f_stride = f_stride; p.b.x = d_x;
-  p.b.x_len = upload(c, std::vector<int>(x_length, x_length + n_utt));
-  p.b.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  begin_stage(c, [](Arena &) {});
+  p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride);
   p.tpos = d_tpos; p.f0 = d_f0; p.refined = d_refined;
   p.tab = c->tab;
   launch_stonemask(p, max_frames, c->stream);
@@ -936,14 +921,6 @@ static void run_stonemask(WorldHipContext *c, int n_utt, int fs, const double *d
 // ---------------------------------------------------------------------------
 // Codec (reference src/codec.cpp): every table depends on (fs, fft_size) only
 // ---------------------------------------------------------------------------
-struct CodecTables {
-  int fs = 0, fft_size = 0;
-  int *d_knot_code = nullptr, *d_knot_dec = nullptr, *d_knot_ap = nullptr;
-  double *d_frac_code = nullptr, *d_frac_dec = nullptr, *d_frac_ap = nullptr;
-  double *d_wc_re = nullptr, *d_wc_im = nullptr, *d_wd_re = nullptr, *d_wd_im = nullptr;
-};
-struct CodecTableSet { std::vector<CodecTables> sets; };
-
 // interp1's histc + weights (matlabfunctions.cpp:136-176) for fixed knots x and queries xi
 static void interp1_tables(const std::vector<double> &x, const std::vector<double> &xi, std::vector<int> *knot,
                            std::vector<double> *frac) {
@@ -958,15 +935,8 @@ static void interp1_tables(const std::vector<double> &x, const std::vector<doubl
   }
 }
 
-template <class T> static T *to_device(WorldHipContext *c, const std::vector<T> &v) {
-  T *d = static_cast<T *>(devrt::dmalloc(sizeof(T) * std::max<size_t>(v.size(), 1)));
-  if (!v.empty()) devrt::h2d(d, v.data(), sizeof(T) * v.size(), c->stream);
-  return d;
-}
-
 static const CodecTables &codec_tables(WorldHipContext *c, int fs, int fft_size) {
-  CodecTableSet *set = static_cast<CodecTableSet *>(c->codec_tables);
-  for (const CodecTables &t : set->sets)
+  for (const CodecTables &t : c->codec_tables)
     if (t.fs == fs && t.fft_size == fft_size) return t;
   const int md = fft_size / 2, nb = md + 1;
   const double kM0 = 1127.01048, kF0 = 700.0;                          // constantnumbers.h:45-46
@@ -987,8 +957,8 @@ static const CodecTables &codec_tables(WorldHipContext *c, int fs, int fft_size)
     wr[0] /= sqrt(2.0);
     for (int i = 0; i <= md; ++i) faxis[i] = mel_of(static_cast<double>(i) * fs / fft_size);
     interp1_tables(faxis, mel_axis, &knot, &frac);
-    t.d_knot_code = to_device(c, knot); t.d_frac_code = to_device(c, frac);
-    t.d_wc_re = to_device(c, wr); t.d_wc_im = to_device(c, wi);
+    put_table(c, t.d_knot_code, knot); put_table(c, t.d_frac_code, frac);
+    put_table(c, t.d_wc_re, wr); put_table(c, t.d_wc_im, wi);
     devrt::sync(c->stream);
   }
   {  // GetParametersForDecoding, codec.cpp:185-207
@@ -1003,8 +973,8 @@ static const CodecTables &codec_tables(WorldHipContext *c, int fs, int fft_size)
     mel_axis[md + 1] = fs / 2.0;
     for (int i = 0; i < nb; ++i) faxis[i] = static_cast<double>(i) * fs / fft_size;
     interp1_tables(mel_axis, faxis, &knot, &frac);
-    t.d_knot_dec = to_device(c, knot); t.d_frac_dec = to_device(c, frac);
-    t.d_wd_re = to_device(c, wr); t.d_wd_im = to_device(c, wi);
+    put_table(c, t.d_knot_dec, knot); put_table(c, t.d_frac_dec, frac);
+    put_table(c, t.d_wd_re, wr); put_table(c, t.d_wd_im, wi);
     devrt::sync(c->stream);
   }
   {  // DecodeAperiodicity's axes, codec.cpp:242-250
@@ -1014,23 +984,11 @@ static const CodecTables &codec_tables(WorldHipContext *c, int fs, int fft_size)
     caxis[std::max(nap, 0) + 1] = fs / 2.0;
     for (int i = 0; i < nb; ++i) faxis[i] = static_cast<double>(fs) / fft_size * i;
     interp1_tables(caxis, faxis, &knot, &frac);
-    t.d_knot_ap = to_device(c, knot); t.d_frac_ap = to_device(c, frac);
+    put_table(c, t.d_knot_ap, knot); put_table(c, t.d_frac_ap, frac);
     devrt::sync(c->stream);
   }
-  set->sets.push_back(t);
-  return set->sets.back();
-}
-
-static void free_codec_tables(WorldHipContext *c) {
-  CodecTableSet *set = static_cast<CodecTableSet *>(c->codec_tables);
-  if (!set) return;
-  for (CodecTables &t : set->sets) {
-    devrt::dfree(t.d_knot_code); devrt::dfree(t.d_knot_dec); devrt::dfree(t.d_knot_ap);
-    devrt::dfree(t.d_frac_code); devrt::dfree(t.d_frac_dec); devrt::dfree(t.d_frac_ap);
-    devrt::dfree(t.d_wc_re); devrt::dfree(t.d_wc_im); devrt::dfree(t.d_wd_re); devrt::dfree(t.d_wd_im);
-  }
-  delete set;
-  c->codec_tables = nullptr;
+  c->codec_tables.push_back(t);
+  return c->codec_tables.back();
 }
 
 static int number_of_aperiodicities(int fs) {                          // codec.cpp:212-215
@@ -1112,9 +1070,7 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
     }
     for (int i = 0; i < fft_size / 2; ++i) { rem[i] /= dc; rem[fft_size - i - 1] = rem[i]; }
     devrt::sync(c->stream);
-    if (c->d_dc_remover) { devrt::dfree(c->d_dc_remover); ++c->generation; }
-    c->d_dc_remover = static_cast<double *>(devrt::dmalloc(sizeof(double) * fft_size));
-    devrt::h2d(c->d_dc_remover, rem.data(), sizeof(double) * fft_size, c->stream);
+    put_table(c, c->d_dc_remover, rem);
     devrt::sync(c->stream);
     c->dc_remover_len = fft_size;
   }
@@ -1130,28 +1086,23 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
   // drop-in Synthesis() -- which waits for its result anyway -- repeats the call with the exact capacity.
   p.pulse_cap = c->synth_pulse_cap > 0 ? c->synth_pulse_cap : static_cast<int>(static_cast<double>(max_y) * 1200.0 / fs) + 16;
   if (!c->d_synth_need) {
-    c->d_synth_need = static_cast<int *>(devrt::dmalloc(sizeof(int)));
+    put_table(c, c->d_synth_need, 1);
     devrt::dzero(c->d_synth_need, sizeof(int), c->stream);
   }
   p.need = c->d_synth_need;
   p.resp_stride = lg > 12 ? fft_size + 2 : fft_size;                   // (sy_pulse: the 8192-point pulse keeps its spectrum in its slot)
   const size_t B = n_utt;
-  size_t need = 2 * pad256(sizeof(int) * B) + pad256(sizeof(double) * B * y_stride) + pad256(B * y_stride) +
-                pad256(sizeof(double) * B * p.nblk) + pad256(sizeof(int) * B * p.nblk) +
-                pad256(sizeof(int) * B * p.pulse_cap) + pad256(sizeof(double) * B * p.pulse_cap) + pad256(sizeof(int) * B) +
-                pad256(sizeof(double) * B * p.pulse_cap * p.resp_stride);
-  ensure_arena(c, need);
-  arena_reset(c);
-  CallScope scope(c, 2 * sizeof(int) * n_utt + 256);
+  begin_stage(c, [&](Arena &a) {
+    p.inc = a.take<double>(B * y_stride);
+    p.flags = a.take<unsigned char>(B * y_stride);
+    p.blk_cnt = a.take<int>(B * p.nblk);
+    p.pidx = a.take<int>(B * p.pulse_cap);
+    p.pshift = a.take<double>(B * p.pulse_cap);
+    p.np = a.take<int>(B);
+    p.resp = a.take<double>(B * p.pulse_cap * p.resp_stride);
+  });
   p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
   p.y_len = upload(c, std::vector<int>(y_length, y_length + n_utt));
-  p.inc = c->arena.take<double>(B * y_stride);
-  p.flags = c->arena.take<unsigned char>(B * y_stride);
-  p.blk_cnt = c->arena.take<int>(B * p.nblk);
-  p.pidx = c->arena.take<int>(B * p.pulse_cap);
-  p.pshift = c->arena.take<double>(B * p.pulse_cap);
-  p.np = c->arena.take<int>(B);
-  p.resp = c->arena.take<double>(B * p.pulse_cap * p.resp_stride);
   p.dc_remover = c->d_dc_remover;
   p.noise = ensure_noise(c, (size_t)max_y + 8);
   p.tab = c->tab;
@@ -1167,23 +1118,19 @@ static void run_pack(WorldHipContext *c, bool unpack, int n_utt, const int *n_fr
   if (n_utt <= 0) fail("n_utt must be positive");
   if (!n_frames || !d_tpos || !d_f0 || !d_sp || !d_ap || !d_block) fail("null buffer");
   if (nb < 1 || first_row < 0) fail("bad record shape");
-  std::vector<int> nf(n_frames, n_frames + n_utt), off(n_utt);
+  const int max_frames = max_frame_count(n_frames, n_utt, f_stride);
+  std::vector<int> off(n_utt);
   long long row = first_row;
-  int max_frames = 0;
   for (int u = 0; u < n_utt; ++u) {
-    if (nf[u] < 0 || nf[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
-    if (row + nf[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
+    if (row + n_frames[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
     off[u] = static_cast<int>(row);
-    row += nf[u];
-    max_frames = std::max(max_frames, nf[u]);
+    row += n_frames[u];
   }
   if (max_frames == 0) return;
-  ensure_arena(c, 2 * pad256(sizeof(int) * n_utt));
-  arena_reset(c);
-  CallScope scope(c, 2 * sizeof(int) * n_utt + 256);
+  begin_stage(c, [](Arena &) {});
   PackArgs a;
   a.n_utt = n_utt; a.f_stride = f_stride; a.nb = nb;
-  a.n_frames = upload(c, nf);
+  a.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
   a.row_offset = upload(c, off);
   a.tpos = d_tpos; a.f0 = d_f0; a.sp = d_sp; a.ap = d_ap; a.block = d_block;
   launch_pack_rows(a, max_frames, unpack, c->stream);
@@ -1198,13 +1145,13 @@ static void run_spectral_stages(WorldHipContext *c, int n_utt, int fs, const dou
                                 const int *n_frames, int f_stride, const double *d_tpos, const double *d_f0,
                                 const CheapTrickOption *copt, const D4COption *dopt, double *d_sp, double *d_ap,
                                 const RowLayout &lay_sp, const RowLayout &lay_ap) {
-  ensure_arena(c, cheaptrick_arena_bytes(n_utt, f_stride, copt->fft_size) + d4c_arena_bytes(n_utt, f_stride, fs));
-  CallScope scope(c, 6 * sizeof(int) * n_utt + 512);        // ONE upload section for both stages' small arrays
+  open_uploads(c);                                          // ONE upload section for both stages' small arrays
   int max_ct = 0, max_d4c = 0;
   CtParams cp = setup_cheaptrick(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, copt, d_sp, lay_sp,
                                  &max_ct);
   D4cParams dp = setup_d4c(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride, d_tpos, d_f0, copt->fft_size, dopt, d_ap,
                            lay_ap, &max_d4c);
+  spectral_workspace(c, &cp, &dp, x_length, n_frames);
   // both stages' first offset scans depend on F0 alone: one launch serves both (two 1-workgroup kernels per job were two
   // of the narrow launches the twelve-jobs-in-flight mode pays 10-25 us apiece for)
   if (!cp.skip_prepare && !dp.skip_prepare) {
@@ -1255,9 +1202,8 @@ static void analyze_into_records(WorldHipContext *c, int n_utt, int fs, const do
   const size_t fr = (size_t)n_utt * f_stride;
   if (c->pk_cap < 2 * fr) {
     devrt::sync(c->stream);
-    if (c->d_pk) { devrt::dfree(c->d_pk); ++c->generation; }
+    put_table(c, c->d_pk, 2 * fr + fr / 4);
     c->pk_cap = 2 * fr + fr / 4;
-    c->d_pk = static_cast<double *>(devrt::dmalloc(sizeof(double) * c->pk_cap));
   }
   double *d_tpos = c->d_pk, *d_f0 = c->d_pk + fr;
   run_harvest(c, n_utt, fs, d_x, x_stride, x_length, hopt, f_stride, d_tpos, d_f0);
@@ -1332,10 +1278,10 @@ static void run_spectral_packed_range(WorldHipContext *c, int n_utt, int fs, con
     fail("spectral_packed_range: %d columns, fft_size %d needs %d (f64 records) or %d (f32 spectra)", cols, copt->fft_size,
          record_cols(copt->fft_size, 0), record_cols(copt->fft_size, 1));
   // utterance u's frame f goes to row rows[u] + f: its range's first frame lands where the previous utterance's range ended
+  max_frame_count(n_frames, n_utt, f_stride);
   std::vector<int> rows(n_utt);
   long long row = first_row;
   for (int u = 0; u < n_utt; ++u) {
-    if (n_frames[u] < 0 || n_frames[u] > f_stride) fail("n_frames[%d] outside [0, f_stride]", u);
     const int lo = std::min(frame_lo, n_frames[u]), hi = std::min(frame_hi, n_frames[u]);
     if (row - lo < -0x7FFFFFFFll || row + (hi - lo) > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
     rows[u] = static_cast<int>(row - lo);
@@ -1439,16 +1385,13 @@ WorldHipContext *world_hip_create(int device, void *stream) {
     build_twiddles(tw.data());
     std::vector<uint4> jump((size_t)kJumpLevels * kJumpStride);
     build_jump_tables(jump.data());
-    double2 *d_tw = static_cast<double2 *>(devrt::dmalloc(sizeof(double2) * tw.size()));
-    uint4 *d_jump = static_cast<uint4 *>(devrt::dmalloc(sizeof(uint4) * jump.size()));
-    devrt::h2d(d_tw, tw.data(), sizeof(double2) * tw.size(), c->stream);
-    devrt::h2d(d_jump, jump.data(), sizeof(uint4) * jump.size(), c->stream);
+    double2 *d_tw = nullptr;
+    uint4 *d_jump = nullptr;
+    put_table(c, d_tw, tw);
+    put_table(c, d_jump, jump);
     devrt::sync(c->stream);
-    c->tab.tw = d_tw;
-    c->tab.jump = d_jump;
+    c->tab = Tables{d_tw, d_jump};
     noise_table_retain(device);
-    c->dio_bands = new DioBands;
-    c->codec_tables = new CodecTableSet;
     return c;
   } catch (const std::exception &e) {
     g_last_error = e.what();
@@ -1464,31 +1407,12 @@ void world_hip_destroy(WorldHipContext *c) {
   try {
     DeviceScope on_device(c->device);    // the context's allocations belong to ITS device, not to the caller's current one
     devrt::sync(c->stream);
-    devrt::dfree(const_cast<double2 *>(c->tab.tw));
-    devrt::dfree(const_cast<uint4 *>(c->tab.jump));
     if (c->arena.base) devrt::dfree(c->arena.base);
-    if (c->d_nuttall) devrt::dfree(c->d_nuttall);
-    if (c->d_ap_frac) { devrt::dfree(c->d_ap_frac); devrt::dfree(c->d_ap_knot); }
-    if (c->d_pk) devrt::dfree(c->d_pk);
     if (c->d_xin) devrt::dfree(c->d_xin);
     if (c->h_xin) devrt::hfree_pinned(c->h_xin);
     if (c->xstream) { devrt::sync(c->xstream); devrt::stream_destroy(c->xstream); }
-    if (c->dio_bands) {
-      DioBands *db = static_cast<DioBands *>(c->dio_bands);
-      if (db->d_band_f0) {
-        devrt::dfree(db->d_band_f0); devrt::dfree(db->d_taps); devrt::dfree(db->d_lowcut); devrt::dfree(db->d_hal);
-        devrt::dfree(db->d_off);
-      }
-      delete db;
-    }
-    free_codec_tables(c);
-    if (c->d_dc_remover) devrt::dfree(c->d_dc_remover);
-    if (c->d_synth_need) devrt::dfree(c->d_synth_need);
+    for (void *t : c->tables) devrt::dfree(t);
     drop_small_arrays(c);
-    HarvestBands &hb = c->bands;
-    if (hb.d_band_f0) { devrt::dfree(hb.d_band_f0); devrt::dfree(hb.d_taps); devrt::dfree(hb.d_half); devrt::dfree(hb.d_off); }
-    if (hb.d_win_tab) devrt::dfree(hb.d_win_tab);
-    if (hb.d_spec) devrt::dfree(hb.d_spec);
     if (c->xchg_ready) devrt::event_destroy(c->xchg_ready);
     if (c->xchg_done) devrt::event_destroy(c->xchg_done);
   } catch (...) {
