@@ -770,6 +770,8 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   p.win_tab = hb.d_win_tab; p.win_lane = hb.d_win_tab + (size_t)hb.win_tab_len * 6;
   p.win_full = hb.win_full_entries && !getenv("WORLD_HIP_REFINE_ROTATE")
                    ? reinterpret_cast<const double2 *>(p.win_lane + (size_t)hb.win_tab_len * WAVE * 2) : nullptr;
+  // the candidate-major hv_refine serves the table route; this runs the frame-major kernel there instead (same bits)
+  p.refine_frames = getenv("WORLD_HIP_REFINE_FRAMES") != nullptr;
   p.tpos = d_tpos; p.f0 = d_f0;
   launch_harvest(p, max_x, max_y, max_fb, max_fr, c->stream);
 #ifdef WORLD_EMU

@@ -45,6 +45,7 @@ struct HarvestParams {
   const double *win_lane;  // [hw][WAVE][2] = (sin, cos)(pi (lane - hw - 1) d): a lane's first window sample at a whole-sample frame centre
   const double2 *win_full; // [hw^2 + i] = (main window, its central difference)[i] of half length hw centred on a sample; nullptr:
                            // a millisecond is not a whole number of samples at the analysis rate -- the kernel rotates (win_tab / win_lane)
+  int refine_frames;       // 1: refine frame-major (hv_refine_frames) on the table route too (WORLD_HIP_REFINE_FRAMES)
   Tables tab;
   // ---- workspace (device) ----
   double *fwd;             // [n_utt][m_stride] forward-filtered padded signal

@@ -486,12 +486,14 @@ __global__ void hv_detect(HarvestParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// OverlapF0Candidates + RefineF0Candidates (harvest.cpp:417-631), one wavefront
-// per (frame, utt).  Slot s = j + nc*m takes candidate j of frame-m (m = 1..3) or
-// frame+(m-3) (m = 4..6); each non-zero slot is refined by instantaneous frequency.
+// OverlapF0Candidates + RefineF0Candidates (harvest.cpp:417-631).  Slot s = j + nc*m of frame f takes candidate j of
+// frame f-m (m = 1..3) or f+(m-3) (m = 4..6); each non-zero slot is refined by instantaneous frequency.  Two kernels:
+// hv_refine (below) is candidate-major and serves whole-sample frame centres (p.win_full); hv_refine_frames is
+// frame-major, one wavefront per (frame, utt), and serves every rate (the rotated windows) and the like-for-like
+// comparison (WORLD_HIP_REFINE_FRAMES).
 __device__ __forceinline__ int floor_log2_int(int v) { return 31 - __builtin_clz((unsigned)v); }   // v >= 1
 
-__global__ void hv_refine(HarvestParams p) {
+__global__ void hv_refine_frames(HarvestParams p) {
   DYN_LDS(lds);
   const int frame = wave_item_x(), u = blockIdx.y;
   if (frame >= p.nfb[u]) return;
@@ -796,6 +798,200 @@ __global__ void hv_refine(HarvestParams p) {
   WH_ACC_FLUSH(0, lane == 0);
 }
 
+// Candidate-major refinement where a millisecond is a whole number K = afs / 1000 of samples (p.win_full): candidate j of
+// source frame sf lands in the target frames sf-3 .. sf+3, and the seven windows it is refined with there are ONE row of
+// the host's table (its half length hw) over signal spans K samples apart, with ONE set of harmonic bins.  One wavefront
+// per (source frame, utt), its tracks in turn; lane = (target shift s, sample phase g), 56 of 64 lanes busy (the
+// frame-major kernel: 48, and the window, bins and products rebuilt by each of the seven wavefronts).  A lane runs the
+// recurrences of all six harmonics from one signal and one window read per sample, the products rounded to doubles
+// before they enter the fma as hv_refine_frames' stored ones are.  Every (slot, harmonic, phase) recurrence takes that
+// kernel's samples, operands and order, the phase sums are its DPP tree (oct_sum), and the harmonic sum -- harmonic h on
+// lane g = h, the same tree over lane bits 0..2 -- pairs h with h ^ 1, h ^ 2, h ^ 4 as its cross-row sum does: same bits.
+__device__ __forceinline__ int uniform_int(int v) {
+#ifndef WORLD_EMU
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+__global__ void hv_refine(HarvestParams p) {
+  DYN_LDS(lds);
+  const int sf = uniform_int(wave_item_x());               // (wave-uniform: the candidate loads are scalar)
+  const int u = blockIdx.y;
+  const int nfb = p.nfb[u];
+  if (sf >= nfb) return;
+  constexpr int G = WAVE >= 64 ? 8 : 1;                   // sample phases: hv_refine_frames' G
+  constexpr int SL = WAVE / G;                            // shift groups (on the GPU the eighth idles)
+  constexpr int kS = (7 + SL - 1) / SL * SL;
+  constexpr int kH = 6;                                   // harmonics (FixF0 uses at most six)
+  const int lane = lane_id(), g = lane % G;
+  const int K = static_cast<int>(p.afs / 1000.0);
+  const int cap = p.refine_cap, span = cap + 6 * K;       // the seven windows of the widest candidate
+  double *ys = reinterpret_cast<double *>(lds) + (size_t)wave_in_block() * (3 * cap + 6 * K + 2);
+  double2 *wv = reinterpret_cast<double2 *>(ys + span);   // the candidate's window row: up to 2 hw_max + 1 <= cap + 1 pairs
+  const int nc = p.nc[u];
+  const double *src = p.cand_a + (size_t)u * p.fb_stride * p.maxc;
+  double *dst_f0 = p.cand_b + (size_t)u * p.fb_stride * p.maxc;
+  double *dst_sc = p.score_b + (size_t)u * p.fb_stride * p.maxc;
+  const double *y = p.y + (size_t)u * p.y_stride;
+  const int y_len = p.y_len[u];
+  const double fs = p.afs, inv_fs = 1.0 / fs;
+  // the samples of every window centred on sf-3 .. sf+3 (clamped at the signal ends like GetBaseIndex's safe_index,
+  // harvest.cpp:434-441)
+  const int org = mround(sf * 1 / 1000.0 * fs) - 3 * K - cap / 2;
+  {
+    constexpr int kB = 6;
+    for (int k0 = lane; k0 < span; k0 += kB * WAVE) {
+      double v[kB];
+#pragma unroll
+      for (int q = 0; q < kB; ++q) v[q] = y[imax(0, imin(y_len - 1, org + k0 + q * WAVE))];
+#pragma unroll
+      for (int q = 0; q < kB; ++q) if (k0 + q * WAVE < span) ys[k0 + q * WAVE] = v[q];
+    }
+  }
+  // target frame sf + d holds this candidate in slot j + nc m
+  auto slot_m = [](int d) { return d > 0 ? d : (d == 0 ? 0 : 3 - d); };
+  auto put = [&](int tf, int slot, double f0v, double scv) {
+    const size_t at = (size_t)tf * p.maxc + slot;
+    dst_f0[at] = f0v; dst_sc[at] = scv;
+  };
+  // the slots whose source frame lies outside the utterance are empty: the first and last source frames write them
+  if (sf == 0 || sf == nfb - 1) {
+    for (int e = lane; e < 42 * nc; e += WAVE) {
+      const int j = e / 42, r = e % 42, v = r % 3 + 1, d = (r / 3) % 7 - 3;
+      const int sv = r < 21 ? (sf == 0 ? -v : -1) : (sf == nfb - 1 ? nfb - 1 + v : -1), tf = sv + d;
+      if ((sv < 0 || sv >= nfb) && tf >= 0 && tf < nfb) put(tf, j + nc * slot_m(d), 0.0, 0.0);
+    }
+  }
+  for (int j = 0; j < nc; ++j) {
+    const double f0c = src[(size_t)sf * p.maxc + j];
+    if (!(f0c > 0.0)) {
+      for (int sh = lane / G; sh < kS; sh += SL)
+        if (g == 0 && sh < 7 && sf + sh - 3 >= 0 && sf + sh - 3 < nfb) put(sf + sh - 3, j + nc * slot_m(sh - 3), 0.0, 0.0);
+      continue;
+    }
+    // GetRefinedF0 (harvest.cpp:589-617): what the candidate fixes before any sample is touched
+    const int hw = static_cast<int>(1.5 * fs / f0c + 1.0);
+    const int blen = 2 * hw + 1;
+    const int lgN = 2 + floor_log2_int(blen);                   // fft_size = 2^(2+floor(log2(2hw+1)))
+    const int N = 1 << lgN;
+    const double base0 = static_cast<double>(-hw) * inv_fs;
+    const int nh = imin(static_cast<int>(fs / 2.0 / f0c), 6);
+    const double bins = f0c * (1 << lgN) / fs;                  // bin of harmonic h: round(bins * (h + 1)), FixF0 :515
+    // per harmonic: the bin (wave-uniform) and 2 cos(2 pi idx G / N)
+    int idx[kH];
+    double c2[kH];
+#pragma unroll
+    for (int h = 0; h < kH; ++h) {                              // (harmonics >= nh are formed and never read)
+      idx[h] = uniform_int(mround(bins * (h + 1)));
+      c2[h] = 2.0 * p.tab.tw[(size_t)((idx[h] * G) & (N - 1)) << (kTwLog2 - lgN)].x;
+    }
+    {
+      const double2 *wf = p.win_full + (size_t)hw * hw;
+      wave_sync();                                              // the previous candidate's reads are done
+      for (int i0 = lane; i0 < blen; i0 += 2 * WAVE) {          // (two loads in flight per lane)
+        const double2 a = wf[i0], b = wf[imin(blen - 1, i0 + WAVE)];
+        wv[i0] = a;
+        if (i0 + WAVE < blen) wv[i0 + WAVE] = b;
+      }
+      wave_sync();
+    }
+    auto refine_shift = [&](int sh) __attribute__((always_inline)) {
+      const int d = sh - 3, tf = sf + d;
+      const double pos = tf * 1 / 1000.0;
+      const int first = mround((pos + base0) * fs + 0.001);     // GetBaseIndex, harvest.cpp:434-441
+      // window sample i is signal sample first + i - 1 = ys[kb + i]; for the seven shifts the span holds it by
+      // construction, the clamp keeps the idle eighth inside LDS
+      const int kb = imax(0, imin(span - blen, first - 1 - org));
+      double s1[kH], s2[kH], t1[kH], t2[kH];
+#pragma unroll
+      for (int h = 0; h < kH; ++h) s1[h] = s2[h] = t1[h] = t2[h] = 0.0;
+      // sum_n v[g+nG] e^{-i theta n}, theta = 2 pi idx G / N:  s[n] = v[n] + 2cos(theta) s[n-1] - s[n-2]
+      auto step = [&](double xv, double2 w) __attribute__((always_inline)) {
+        const double pa = xv * w.x, pd = xv * w.y;
+#pragma unroll
+        for (int h = 0; h < kH; ++h) {
+          const double sa = fma(c2[h], s1[h], pa) - s2[h], ta = fma(c2[h], t1[h], pd) - t2[h];
+          s2[h] = s1[h]; s1[h] = sa; t2[h] = t1[h]; t1[h] = ta;
+        }
+      };
+      const double *xp = ys + kb + g;
+      const double2 *wp = wv + g;
+      const int n_uni = blen / G;                               // the steps every phase takes (wave-uniform counter)
+#pragma unroll 2
+      for (int t = 0; t < n_uni; ++t) step(xp[t * G], wp[t * G]);
+      // the phases that take one more sample: a step for every lane, kept by those (under a branch the join holds both
+      // generations of the 24 sums: 128 registers instead of 118)
+      const bool more = g < blen - n_uni * G;
+      {
+        const int tr = more ? n_uni * G : 0;
+        const double xv = xp[tr];
+        const double2 w = wp[tr];
+        const double pa = xv * w.x, pd = xv * w.y;
+#pragma unroll
+        for (int h = 0; h < kH; ++h) {
+          const double sa = fma(c2[h], s1[h], pa) - s2[h], ta = fma(c2[h], t1[h], pd) - t2[h];
+          s2[h] = more ? s1[h] : s2[h]; s1[h] = more ? sa : s1[h];
+          t2[h] = more ? t1[h] : t2[h]; t1[h] = more ? ta : t1[h];
+        }
+      }
+      const int cnt = n_uni + (more ? 1 : 0);
+      // the last sample taken, g + G (cnt - 1): its phase e^{-2 pi i idx last / N} closes the sum; then the sum over
+      // phases, and lane g keeps harmonic g's (the emulation's one lane keeps all of them)
+      const int last = g + G * (cnt - 1);
+      double keep[8 / G][4];
+      for (int hi = 0; hi < 8 / G; ++hi) keep[hi][0] = keep[hi][1] = keep[hi][2] = keep[hi][3] = 0.0;
+#pragma unroll
+      for (int h = 0; h < kH; ++h) {
+        double are = 0.0, aim = 0.0, dre = 0.0, dim = 0.0;
+        if (cnt > 0) {
+          const double2 st = p.tab.tw[(size_t)((idx[h] * G) & (N - 1)) << (kTwLog2 - lgN)];
+          const double2 wl = p.tab.tw[(size_t)((idx[h] * last) & (N - 1)) << (kTwLog2 - lgN)];
+          const double A = s1[h] - st.x * s2[h], B = st.y * s2[h], C = t1[h] - st.x * t2[h], D = st.y * t2[h];
+          are = A * wl.x + B * wl.y; aim = B * wl.x - A * wl.y;
+          dre = C * wl.x + D * wl.y; dim = D * wl.x - C * wl.y;
+        }
+#ifndef WORLD_EMU
+        static_assert(G == 8, "oct_sum reduces over eight sample phases");
+        are = oct_sum(are); aim = oct_sum(aim); dre = oct_sum(dre); dim = oct_sum(dim);
+#endif
+        for (int hi = 0; hi < 8 / G; ++hi) {
+          if (h == g + G * hi) { keep[hi][0] = are; keep[hi][1] = aim; keep[hi][2] = dre; keep[hi][3] = dim; }
+#ifndef WORLD_EMU
+          // (the pick is made here: left to the compiler it kept all 24 sums to the end and the kernel spilled)
+          asm volatile("" : "+v"(keep[hi][0]), "+v"(keep[hi][1]), "+v"(keep[hi][2]), "+v"(keep[hi][3]));
+#endif
+        }
+      }
+      // FixF0 (harvest.cpp:507-536): lane g takes harmonic h = g (+ G hi)
+      double num = 0.0, den = 0.0, sc = 0.0;
+      for (int hi = 0; hi < 8 / G; ++hi) {
+        const int h = g + G * hi;
+        if (h >= nh) continue;
+        const double a_re = keep[hi][0], a_im = keep[hi][1], d_re = keep[hi][2], d_im = keep[hi][3];
+        const double pwv = a_re * a_re + a_im * a_im;           // harvest.cpp:564-569
+        const double niv = a_re * d_im - a_im * d_re;
+        const double inst = pwv == 0.0 ? 0.0 : static_cast<double>(mround(bins * (h + 1))) * fs / N + niv / pwv * fs / 2.0 / kPi;
+        const double amp = sqrt(pwv);
+        num += amp * inst;
+        den += amp * (h + 1.0);
+        sc += fabs((inst / (h + 1.0) - f0c) / f0c);
+      }
+#ifndef WORLD_EMU
+      num = oct_sum(num); den = oct_sum(den); sc = oct_sum(sc);
+#endif
+      if (g == 0 && sh < 7 && tf >= 0 && tf < nfb) {
+        double rf0 = num / (den + kTiny);
+        double rsc = 1.0 / (sc / nh + kTiny);
+        if (rf0 < p.f0_floor || rf0 > p.f0_ceil || rsc < 2.5) { rf0 = 0.0; rsc = 0.0; }
+        put(tf, j + nc * slot_m(d), rf0, rsc);
+      }
+    };
+    if constexpr (SL == 8) refine_shift(lane / G);              // (the GPU: every lane has one shift)
+    else for (int sh = lane / G; sh < kS; sh += SL) refine_shift(sh);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // RemoveUnreliableCandidates (harvest.cpp:636-688): keep a candidate only if a
 // neighbouring frame holds one within 5 %.  Reads the refined set (b), writes (a).
@@ -954,7 +1150,10 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
               8 * kIntervalCap * sizeof(double) + 4 * sizeof(IntervalRange), stream, g);
   }
   WH_THREADS(hv_detect, max_fb, B, 1, stream, p);
-  WH_WAVES(hv_refine, max_fb, B, 1, 3 * sizeof(double) * p.refine_cap, stream, p);
+  if (p.win_full && !p.refine_frames)
+    WH_WAVES(hv_refine, max_fb, B, 1, sizeof(double) * (3 * p.refine_cap + 6 * static_cast<int>(p.afs / 1000.0) + 2), stream, p);
+  else
+    WH_WAVES(hv_refine_frames, max_fb, B, 1, 3 * sizeof(double) * p.refine_cap, stream, p);
   WH_BLOCKS(hv_prune, dim3((max_fb + kPruneFrames - 1) / kPruneFrames, B), 256,
             sizeof(double) * (size_t)(2 * kPruneFrames + 2) * p.maxc, stream, p);          // + the base pick (c0)
   launch_harvest_contour(p, max_fb, max_frames, stream);
