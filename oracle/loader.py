@@ -3,6 +3,9 @@
 Two interchangeable back ends with one Python surface:
 
 * ``PortOracle``  -- oracle/libworld_oracle.so, this repo's plain-C restatement.
+* ``WideOracle``  -- oracle/libworld_oracle_wide.so, the same source with its value
+  arithmetic in long double (-DWO_WIDE): the more precise answer the accuracy
+  tests measure both the GPU and the reference against.
 * ``RefOracle``   -- oracle/_ref/libworld_ref*.so, the UNMODIFIED reference
   compiled in place from /root/reference by oracle/Makefile (present whenever
   it was built in the container; the .so travels to the GPU box).
@@ -179,6 +182,21 @@ class PortOracle(_Base):
         coded = _f64(coded); out = np.zeros((coded.shape[0], fft_size // 2 + 1))
         self.lib.wo_decode_spectral_envelope(_p(coded), coded.shape[0], fs, fft_size, coded.shape[1], _p(out))
         return out
+
+
+def wide_is_wider():
+    """long double is wider than double on this host (x86-64: 64-bit mantissa); else WideOracle is just PortOracle"""
+    return float(np.finfo(np.longdouble).eps) < float(np.finfo(np.float64).eps)
+
+
+class WideOracle(PortOracle):
+    kind = "wide"
+
+    def __init__(self, path=None):
+        path = path or os.path.join(HERE, "libworld_oracle_wide.so")
+        if not os.path.exists(path):
+            build()
+        super().__init__(path)
 
 
 # The generic binding of the reference's 13-symbol C ABI lives in the product's

@@ -16,13 +16,30 @@
 #define _DEFAULT_SOURCE
 #include "world_oracle.h"
 
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+/* Value arithmetic goes through wo_real: double by default, long double with -DWO_WIDE
+ * (libworld_oracle_wide.so, the accuracy yardstick of tests/test_gpu_accuracy.py).  <tgmath.h>
+ * then makes cos / exp / log / sqrt their long double forms.  Whatever decides discrete
+ * structure -- window half-lengths, wo_round arguments, origins, bin indices, band edges,
+ * pulse positions -- stays double and is computed exactly as the reference computes it, so
+ * both builds take the same path and only the values differ.  Harvest and DIO are discrete
+ * selection and stay double in both builds (they call the double entry points below).  The
+ * ABI is double throughout: inputs are exact, outputs are rounded to double once. */
+#ifdef WO_WIDE
+#include <tgmath.h>
+typedef long double wo_real;
+#define WO_PI 3.14159265358979323846264338327950288L
+#else
+#include <math.h>
+typedef double wo_real;
+#define WO_PI 3.14159265358979323846
+#endif
+
 /* constantnumbers.h:8-37 */
-static const double K_PI = 3.1415926535897932384;
+static const wo_real K_PI = WO_PI;
 static const double K_TINY = 0.000000000001;
 static const double K_EPS = 0.00000000000000022204460492503131;
 static const double K_LOG2 = 0.69314718055994529;
@@ -32,7 +49,11 @@ static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
 static double dmin(double a, double b) { return a < b ? a : b; }
 static double dmax(double a, double b) { return a > b ? a : b; }
+static wo_real rmin(wo_real a, wo_real b) { return a < b ? a : b; }
 static double *dalloc(size_t n) { return (double *)calloc(n ? n : 1, sizeof(double)); }
+static wo_real *ralloc(size_t n) { return (wo_real *)calloc(n ? n : 1, sizeof(wo_real)); }
+static void to_real(const double *a, int n, wo_real *r) { for (int i = 0; i < n; ++i) r[i] = a[i]; }
+static void to_double(const wo_real *r, int n, double *a) { for (int i = 0; i < n; ++i) a[i] = (double)r[i]; }
 static int *ialloc(size_t n) { return (int *)calloc(n ? n : 1, sizeof(int)); }
 
 /* ------------------------------------------------------------------ */
@@ -66,14 +87,14 @@ double wo_randn(uint32_t s[4]) {
 /* forward = rfft, backward = N * irfft, Im of DC/Nyquist ignored)      */
 /* ------------------------------------------------------------------ */
 #define WO_MAX_LOG2 22
-static double *g_tw[WO_MAX_LOG2 + 1]; /* g_tw[L]: cos/sin(2*pi*k/2^L), k < 2^L/2 */
+static wo_real *g_tw[WO_MAX_LOG2 + 1]; /* g_tw[L]: cos/sin(2*pi*k/2^L), k < 2^L/2 */
 
-static const double *twiddles(int log2n) {
+static const wo_real *twiddles(int log2n) {
   if (!g_tw[log2n]) {
     int n = 1 << log2n, h = n / 2 > 0 ? n / 2 : 1;
-    double *t = (double *)malloc(sizeof(double) * 2 * h);
+    wo_real *t = (wo_real *)malloc(sizeof(wo_real) * 2 * h);
     for (int k = 0; k < h; ++k) {
-      double a = 2.0 * 3.14159265358979323846 * k / n;
+      wo_real a = 2.0 * K_PI * k / n;
       t[2 * k] = cos(a);
       t[2 * k + 1] = sin(a);
     }
@@ -85,53 +106,53 @@ static const double *twiddles(int log2n) {
 static int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
 /* in-place complex FFT, sign = -1 forward / +1 backward, unscaled */
-static void cfft(int n, double *re, double *im, int sign) {
+static void cfft(int n, wo_real *re, wo_real *im, int sign) {
   int lg = ilog2(n);
   for (int i = 1, j = 0; i < n; ++i) {
     int bit = n >> 1;
     for (; j & bit; bit >>= 1) j ^= bit;
     j ^= bit;
     if (i < j) {
-      double t = re[i]; re[i] = re[j]; re[j] = t;
+      wo_real t = re[i]; re[i] = re[j]; re[j] = t;
       t = im[i]; im[i] = im[j]; im[j] = t;
     }
   }
-  const double *tw = twiddles(lg);
+  const wo_real *tw = twiddles(lg);
   for (int len = 2; len <= n; len <<= 1) {
     int half = len >> 1, step = n / len;
     for (int base = 0; base < n; base += len)
       for (int k = 0; k < half; ++k) {
-        double wr = tw[2 * k * step], wi = sign * tw[2 * k * step + 1];
+        wo_real wr = tw[2 * k * step], wi = sign * tw[2 * k * step + 1];
         int a = base + k, b = a + half;
-        double xr = re[b] * wr - im[b] * wi, xi = re[b] * wi + im[b] * wr;
+        wo_real xr = re[b] * wr - im[b] * wi, xi = re[b] * wi + im[b] * wr;
         re[b] = re[a] - xr; im[b] = im[a] - xi;
         re[a] += xr; im[a] += xi;
       }
   }
 }
 
-void wo_rfft(int n, const double *in, double *re, double *im) {
+static void rfft(int n, const wo_real *in, wo_real *re, wo_real *im) {
   if (n < 4) { /* tiny sizes never occur on the path; direct DFT */
     for (int k = 0; k <= n / 2; ++k) {
-      double sr = 0, si = 0;
+      wo_real sr = 0, si = 0;
       for (int t = 0; t < n; ++t) {
-        sr += in[t] * cos(2 * 3.14159265358979323846 * k * t / n);
-        si -= in[t] * sin(2 * 3.14159265358979323846 * k * t / n);
+        sr += in[t] * cos(2 * K_PI * k * t / n);
+        si -= in[t] * sin(2 * K_PI * k * t / n);
       }
       re[k] = sr; im[k] = si;
     }
     return;
   }
   int h = n / 2;
-  double *zr = (double *)malloc(sizeof(double) * 2 * h), *zi = zr + h;
+  wo_real *zr = (wo_real *)malloc(sizeof(wo_real) * 2 * h), *zi = zr + h;
   for (int k = 0; k < h; ++k) { zr[k] = in[2 * k]; zi[k] = in[2 * k + 1]; }
   cfft(h, zr, zi, -1);
-  const double *tw = twiddles(ilog2(n));
+  const wo_real *tw = twiddles(ilog2(n));
   for (int k = 0; k <= h; ++k) {
     int a = k % h, b = (h - k) % h;
-    double er = 0.5 * (zr[a] + zr[b]), ei = 0.5 * (zi[a] - zi[b]);
-    double orr = 0.5 * (zi[a] + zi[b]), oi = -0.5 * (zr[a] - zr[b]);
-    double wr, wi;
+    wo_real er = 0.5 * (zr[a] + zr[b]), ei = 0.5 * (zi[a] - zi[b]);
+    wo_real orr = 0.5 * (zi[a] + zi[b]), oi = -0.5 * (zr[a] - zr[b]);
+    wo_real wr, wi;
     if (k < h) { wr = tw[2 * k]; wi = -tw[2 * k + 1]; } else { wr = -1.0; wi = 0.0; }
     re[k] = er + (orr * wr - oi * wi);
     im[k] = ei + (orr * wi + oi * wr);
@@ -140,19 +161,19 @@ void wo_rfft(int n, const double *in, double *re, double *im) {
   free(zr);
 }
 
-void wo_irfft_unscaled(int n, const double *re, const double *im, double *out) {
+static void irfft_unscaled(int n, const wo_real *re, const wo_real *im, wo_real *out) {
   int h = n / 2;
-  double *zr = (double *)malloc(sizeof(double) * 2 * h), *zi = zr + h;
-  const double *tw = twiddles(ilog2(n));
+  wo_real *zr = (wo_real *)malloc(sizeof(wo_real) * 2 * h), *zi = zr + h;
+  const wo_real *tw = twiddles(ilog2(n));
   for (int k = 0; k < h; ++k) {
     int b = h - k;
-    double xr = re[k], xi = (k == 0) ? 0.0 : im[k];
-    double yr = re[b], yi = (b == h) ? 0.0 : -im[b];   /* conj(X[h-k]) */
-    double sr = xr + yr, si = xi + yi;
-    double dr = xr - yr, di = xi - yi;
-    double wr = tw[2 * k], wi = tw[2 * k + 1];          /* e^{+2 pi i k/n} */
+    wo_real xr = re[k], xi = (k == 0) ? 0.0 : im[k];
+    wo_real yr = re[b], yi = (b == h) ? 0.0 : -im[b];   /* conj(X[h-k]) */
+    wo_real sr = xr + yr, si = xi + yi;
+    wo_real dr = xr - yr, di = xi - yi;
+    wo_real wr = tw[2 * k], wi = tw[2 * k + 1];          /* e^{+2 pi i k/n} */
     /* i * w * d */
-    double tr = -(dr * wi + di * wr), ti = dr * wr - di * wi;
+    wo_real tr = -(dr * wi + di * wr), ti = dr * wr - di * wi;
     zr[k] = sr + tr; zi[k] = si + ti;
   }
   cfft(h, zr, zi, +1);
@@ -160,39 +181,95 @@ void wo_irfft_unscaled(int n, const double *re, const double *im, double *out) {
   free(zr);
 }
 
+/* the codec stays double: its transforms go through these copies */
+static void cfft_double(int n, double *re, double *im, int sign) {
+  wo_real *t = ralloc(2 * n);
+  to_real(re, n, t);
+  to_real(im, n, t + n);
+  cfft(n, t, t + n, sign);
+  to_double(t, n, re);
+  to_double(t + n, n, im);
+  free(t);
+}
+
+void wo_rfft(int n, const double *in, double *re, double *im) {
+  wo_real *t = ralloc(n + 2 * (n / 2 + 1));
+  to_real(in, n, t);
+  rfft(n, t, t + n, t + n + n / 2 + 1);
+  to_double(t + n, n / 2 + 1, re);
+  to_double(t + n + n / 2 + 1, n / 2 + 1, im);
+  free(t);
+}
+
+void wo_irfft_unscaled(int n, const double *re, const double *im, double *out) {
+  wo_real *t = ralloc(n + 2 * (n / 2 + 1));
+  to_real(re, n / 2 + 1, t + n);
+  to_real(im, n / 2 + 1, t + n + n / 2 + 1);
+  irfft_unscaled(n, t + n, t + n + n / 2 + 1, t);
+  to_double(t, n, out);
+  free(t);
+}
+
 /* ------------------------------------------------------------------ */
 /* shared DSP helpers                                                  */
 /* ------------------------------------------------------------------ */
-void wo_nuttall(int len, double *w) {
+static void nuttall(int len, wo_real *w) {
   for (int i = 0; i < len; ++i) {
-    double t = i / (len - 1.0);
+    wo_real t = i / (len - (wo_real)1.0);
     w[i] = 0.355768 - 0.487396 * cos(2.0 * K_PI * t) +
            0.144232 * cos(4.0 * K_PI * t) - 0.012604 * cos(6.0 * K_PI * t);
   }
 }
 
 /* interp1 + histc (matlabfunctions.cpp:136-176): the bin of a query is
- * clamp(#{knots <= query}, 1, n-1), so both ends extrapolate linearly. */
-void wo_interp1(const double *x, const double *y, int n, const double *xi,
-                int ni, double *yi) {
+ * clamp(#{knots <= query}, 1, n-1), so both ends extrapolate linearly.
+ * Knots and queries are double (they pick the bin); values are wo_real. */
+static void interp1(const double *x, const wo_real *y, int n, const double *xi,
+                    int ni, wo_real *yi) {
   int c = 0; /* knots are ascending and so are the queries on every call site */
   for (int i = 0; i < ni; ++i) {
     while (c < n && x[c] <= xi[i]) ++c;
     int k = c < 1 ? 1 : (c > n - 1 ? n - 1 : c);
-    double h = x[k] - x[k - 1];
-    double s = (xi[i] - x[k - 1]) / h;
+    wo_real h = (wo_real)x[k] - x[k - 1];
+    wo_real s = ((wo_real)xi[i] - x[k - 1]) / h;
     yi[i] = y[k - 1] + s * (y[k] - y[k - 1]);
   }
 }
 
-void wo_interp1q(double x0, double dx, const double *y, int n,
-                 const double *xi, int ni, double *yi) {
+/* the bin b is the reference's double expression; only the fraction is wo_real */
+static void interp1q(double x0, double dx, const wo_real *y, int n,
+                     const double *xi, int ni, wo_real *yi) {
   for (int i = 0; i < ni; ++i) {
     int b = (int)((xi[i] - x0) / dx);
-    double frac = (xi[i] - x0) / dx - b;
-    double dy = (b < n - 1) ? y[b + 1] - y[b] : 0.0;
+    wo_real frac = ((wo_real)xi[i] - x0) / dx - b;
+    wo_real dy = (b < n - 1) ? y[b + 1] - y[b] : 0.0;
     yi[i] = y[b] + dy * frac;
   }
+}
+
+void wo_nuttall(int len, double *w) {
+  wo_real *t = ralloc(len);
+  nuttall(len, t);
+  to_double(t, len, w);
+  free(t);
+}
+
+void wo_interp1(const double *x, const double *y, int n, const double *xi,
+                int ni, double *yi) {
+  wo_real *t = ralloc(n + ni);
+  to_real(y, n, t);
+  interp1(x, t, n, xi, ni, t + n);
+  to_double(t + n, ni, yi);
+  free(t);
+}
+
+void wo_interp1q(double x0, double dx, const double *y, int n,
+                 const double *xi, int ni, double *yi) {
+  wo_real *t = ralloc(n + ni);
+  to_real(y, n, t);
+  interp1q(x0, dx, t, n, xi, ni, t + n);
+  to_double(t + n, ni, yi);
+  free(t);
 }
 
 /* decimation IIR coefficients, matlabfunctions.cpp:27-113 */
@@ -245,12 +322,13 @@ void wo_decimate(const double *x, int n, int r, double *y) {
 }
 
 /* common.cpp:56-75 (in == out allowed) */
-void wo_dc_correction(const double *in, double f0, int fs, int fft_size, double *out) {
+static void dc_correction(const wo_real *in, double f0, int fs, int fft_size, wo_real *out) {
   int upper = 2 + (int)(f0 * fft_size / fs);
   int nrep = upper - 1;
-  double *axis = dalloc(upper), *rep = dalloc(upper);
+  double *axis = dalloc(upper);
+  wo_real *rep = ralloc(upper);
   for (int i = 0; i < upper; ++i) axis[i] = (double)i * fs / fft_size;
-  wo_interp1q(f0 - axis[0], -(double)fs / fft_size, in, upper + 1, axis, nrep, rep);
+  interp1q(f0 - axis[0], -(double)fs / fft_size, in, upper + 1, axis, nrep, rep);
   for (int i = 0; i < nrep; ++i) out[i] = in[i] + rep[i];
   if (out != in) for (int i = nrep; i <= fft_size / 2; ++i) out[i] = in[i];
   free(axis); free(rep);
@@ -258,14 +336,14 @@ void wo_dc_correction(const double *in, double f0, int fs, int fft_size, double 
 
 /* common.cpp:27-46,77-111: rectangular smoothing through a SERIAL prefix sum
  * of the mirrored spectrum (the summation order is part of the result). */
-void wo_linear_smoothing(const double *in, double width, int fs, int fft_size, double *out) {
+static void linear_smoothing(const wo_real *in, double width, int fs, int fft_size, wo_real *out) {
   int half = fft_size / 2;
   int bnd = (int)(width * fft_size / fs) + 1;
   int len = half + 2 * bnd + 1;
-  double *seg = dalloc(len), *axis = dalloc(half + 1);
-  double *lo = dalloc(half + 1), *hi = dalloc(half + 1);
+  wo_real *seg = ralloc(len), *lo = ralloc(half + 1), *hi = ralloc(half + 1);
+  double *axis = dalloc(half + 1);
   for (int i = 0; i < len; ++i) {
-    double m;
+    wo_real m;
     if (i < bnd) m = in[bnd - i];
     else if (i < half + bnd) m = in[i - bnd];
     else m = in[half - (i - (half + bnd))];
@@ -275,11 +353,29 @@ void wo_linear_smoothing(const double *in, double width, int fs, int fft_size, d
   for (int i = 0; i <= half; ++i) axis[i] = (double)i / fft_size * fs - width / 2.0;
   double origin = -(bnd - 0.5) * fs / fft_size;
   double step = (double)fs / fft_size;
-  wo_interp1q(origin, step, seg, len, axis, half + 1, lo);
+  interp1q(origin, step, seg, len, axis, half + 1, lo);
   for (int i = 0; i <= half; ++i) axis[i] += width;
-  wo_interp1q(origin, step, seg, len, axis, half + 1, hi);
+  interp1q(origin, step, seg, len, axis, half + 1, hi);
   for (int i = 0; i <= half; ++i) out[i] = (hi[i] - lo[i]) / width;
   free(seg); free(axis); free(lo); free(hi);
+}
+
+void wo_dc_correction(const double *in, double f0, int fs, int fft_size, double *out) {
+  int nb = fft_size / 2 + 1;
+  wo_real *t = ralloc(nb);
+  to_real(in, nb, t);
+  dc_correction(t, f0, fs, fft_size, t);
+  to_double(t, nb, out);
+  free(t);
+}
+
+void wo_linear_smoothing(const double *in, double width, int fs, int fft_size, double *out) {
+  int nb = fft_size / 2 + 1;
+  wo_real *t = ralloc(nb);
+  to_real(in, nb, t);
+  linear_smoothing(t, width, fs, fft_size, t);
+  to_double(t, nb, out);
+  free(t);
 }
 
 int wo_frame_count(int fs, int x_length, double frame_period) {
@@ -953,47 +1049,48 @@ void wo_dio(const double *x, int x_length, int fs, double f0_floor, double f0_ce
 /* ------------------------------------------------------------------ */
 /* StoneMask (stonemask.cpp:24-218)                                     */
 /* ------------------------------------------------------------------ */
-static double stonemask_if(const double *pw, const double *ni, int N, int fs, double f0, int nh) {
-  double num = 0.0, den = 0.0;
+static wo_real stonemask_if(const wo_real *pw, const wo_real *ni, int N, int fs, double f0, int nh) {
+  wo_real num = 0.0, den = 0.0;
   for (int k = 0; k < nh; ++k) {
     int idx = imin(wo_round(f0 * N / fs * (k + 1)), N / 2);
-    double inst = pw[idx] == 0.0 ? 0.0 : (double)idx * fs / N + ni[idx] / pw[idx] * fs / 2.0 / K_PI;
-    double amp = sqrt(pw[idx]);
+    wo_real inst = pw[idx] == 0.0 ? 0.0 : (wo_real)idx * fs / N + ni[idx] / pw[idx] * fs / 2.0 / K_PI;
+    wo_real amp = sqrt(pw[idx]);
     num += amp * inst;
     den += amp * (k + 1);
   }
   return num / (den + K_TINY);
 }
 
-static double stonemask_one(const double *x, int n, int fs, double pos, double f0) {
+static wo_real stonemask_one(const double *x, int n, int fs, double pos, double f0) {
   if (f0 <= 40.0 || f0 > fs / 12.0) return 0.0;
   int hw = (int)(1.5 * fs / f0 + 1.0);
   double wlen = (2.0 * hw + 1.0) / fs;
   int blen = 2 * hw + 1;
   int N = (int)pow(2.0, 2.0 + (int)(log(hw * 2.0 + 1.0) / K_LOG2));
   int *raw = ialloc(blen);
-  double *mw = dalloc(blen), *dw = dalloc(blen), *buf = dalloc(N);
-  double *ar = dalloc(N / 2 + 1), *ai = dalloc(N / 2 + 1), *br = dalloc(N / 2 + 1), *bi = dalloc(N / 2 + 1);
+  wo_real *mw = ralloc(blen), *dw = ralloc(blen), *buf = ralloc(N);
+  wo_real *ar = ralloc(N / 2 + 1), *ai = ralloc(N / 2 + 1), *br = ralloc(N / 2 + 1), *bi = ralloc(N / 2 + 1);
   for (int i = 0; i < blen; ++i) {
     double bt = (double)(-hw + i) / fs;
     raw[i] = wo_round((pos + bt) * fs);
-    double t = (raw[i] - 1.0) / fs - pos;
+    wo_real t = (raw[i] - (wo_real)1.0) / fs - pos;
     mw[i] = 0.42 + 0.5 * cos(2.0 * K_PI * t / wlen) + 0.08 * cos(4.0 * K_PI * t / wlen);
   }
   dw[0] = -mw[1] / 2.0;
   for (int i = 1; i < blen - 1; ++i) dw[i] = -(mw[i + 1] - mw[i - 1]) / 2.0;
   dw[blen - 1] = mw[blen - 2] / 2.0;
   for (int i = 0; i < blen; ++i) buf[i] = x[imax(0, imin(n - 1, raw[i] - 1))] * mw[i];
-  wo_rfft(N, buf, ar, ai);
+  rfft(N, buf, ar, ai);
   for (int i = 0; i < blen; ++i) buf[i] = x[imax(0, imin(n - 1, raw[i] - 1))] * dw[i];
-  wo_rfft(N, buf, br, bi);
-  double *pw = dalloc(N / 2 + 1), *ni = dalloc(N / 2 + 1);
+  rfft(N, buf, br, bi);
+  wo_real *pw = ralloc(N / 2 + 1), *ni = ralloc(N / 2 + 1);
   for (int j = 0; j <= N / 2; ++j) {
     ni[j] = ar[j] * bi[j] - ai[j] * br[j];
     pw[j] = ar[j] * ar[j] + ai[j] * ai[j];
   }
-  double tent = stonemask_if(pw, ni, N, fs, f0, 2);
-  double mean;
+  /* the tentative F0 picks the harmonic bins of the second pass: rounded as the reference holds it */
+  double tent = (double)stonemask_if(pw, ni, N, fs, f0, 2);
+  wo_real mean;
   if (tent <= 0.0 || tent > f0 * 2) mean = 0.0;
   else mean = stonemask_if(pw, ni, N, fs, tent, 6);
   if (fabs(mean - f0) > f0 * 0.2) mean = f0;
@@ -1003,7 +1100,7 @@ static double stonemask_one(const double *x, int n, int fs, double pos, double f
 
 void wo_stonemask(const double *x, int x_length, int fs, const double *tpos, const double *f0,
                   int nf, double *refined) {
-  for (int i = 0; i < nf; ++i) refined[i] = stonemask_one(x, x_length, fs, tpos[i], f0[i]);
+  for (int i = 0; i < nf; ++i) refined[i] = (double)stonemask_one(x, x_length, fs, tpos[i], f0[i]);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1019,50 +1116,50 @@ void wo_cheaptrick(const double *x, int x_length, int fs, const double *tpos, co
   wo_randn_seed(rng);
   int half = fft_size / 2, nb = half + 1;
   double floor_f0 = 3.0 * fs / (fft_size - 3.0);
-  double *wave = dalloc(fft_size), *win = dalloc(fft_size);
-  double *re = dalloc(nb), *im = dalloc(nb), *zero = dalloc(nb);
+  wo_real *wave = ralloc(fft_size), *win = ralloc(fft_size);
+  wo_real *re = ralloc(nb), *im = ralloc(nb), *zero = ralloc(nb);
   for (int f = 0; f < nf; ++f) {
     double cf0 = f0[f] <= floor_f0 ? 500.0 : f0[f];
     /* windowed waveform (87-142) */
     int hw = wo_round(1.5 * fs / cf0);
     int origin = wo_round(tpos[f] * fs + 0.001);
-    double e = 0.0;
+    wo_real e = 0.0;
     for (int i = 0; i <= 2 * hw; ++i) {
-      double p = (i - hw) / 1.5 / fs;
+      wo_real p = (i - hw) / (wo_real)1.5 / fs;
       win[i] = 0.5 * cos(K_PI * p * cf0) + 0.5;
       e += win[i] * win[i];
     }
     e = sqrt(e);
     for (int i = 0; i <= 2 * hw; ++i) win[i] /= e;
     for (int i = 0; i <= 2 * hw; ++i)
-      wave[i] = x[imin(x_length - 1, imax(0, origin + i - hw))] * win[i] + wo_randn(rng) * K_TINY;
-    double s1 = 0, s2 = 0;
+      wave[i] = x[imin(x_length - 1, imax(0, origin + i - hw))] * win[i] + (wo_real)wo_randn(rng) * K_TINY;
+    wo_real s1 = 0, s2 = 0;
     for (int i = 0; i <= 2 * hw; ++i) { s1 += wave[i]; s2 += win[i]; }
-    double coef = s1 / s2;
+    wo_real coef = s1 / s2;
     for (int i = 0; i <= 2 * hw; ++i) wave[i] -= win[i] * coef;
     for (int i = 2 * hw + 1; i < fft_size; ++i) wave[i] = 0.0;
     /* power spectrum + DC correction (64-82) */
-    wo_rfft(fft_size, wave, re, im);
+    rfft(fft_size, wave, re, im);
     for (int i = 0; i <= half; ++i) wave[i] = re[i] * re[i] + im[i] * im[i];
-    wo_dc_correction(wave, cf0, fs, fft_size, wave);
-    wo_linear_smoothing(wave, cf0 * 2.0 / 3.0, fs, fft_size, wave);
-    for (int i = 0; i <= half; ++i) wave[i] = wave[i] + fabs(wo_randn(rng)) * K_EPS;
+    dc_correction(wave, cf0, fs, fft_size, wave);
+    linear_smoothing(wave, cf0 * 2.0 / 3.0, fs, fft_size, wave);
+    for (int i = 0; i <= half; ++i) wave[i] = wave[i] + fabs((wo_real)wo_randn(rng)) * K_EPS;
     /* cepstral smoothing + recovery (22-57) */
     for (int i = 0; i <= half; ++i) wave[i] = log(wave[i]);
     for (int i = 1; i < half; ++i) wave[fft_size - i] = wave[i];
-    wo_rfft(fft_size, wave, re, im);
+    rfft(fft_size, wave, re, im);
     for (int i = 0; i <= half; ++i) {
-      double sl, cl;
-      if (i == 0) { sl = 1.0; cl = (1.0 - 2.0 * q1) + 2.0 * q1; }
+      wo_real sl, cl;
+      if (i == 0) { sl = 1.0; cl = (1.0 - (wo_real)2.0 * q1) + 2.0 * q1; }
       else {
-        double q = (double)i / fs;
+        wo_real q = (wo_real)i / fs;
         sl = sin(K_PI * cf0 * q) / (K_PI * cf0 * q);
-        cl = (1.0 - 2.0 * q1) + 2.0 * q1 * cos(2.0 * K_PI * q * cf0);
+        cl = (1.0 - (wo_real)2.0 * q1) + 2.0 * q1 * cos(2.0 * K_PI * q * cf0);
       }
       re[i] = re[i] * sl * cl / fft_size;
     }
-    wo_irfft_unscaled(fft_size, re, zero, wave);
-    for (int i = 0; i <= half; ++i) spectrogram[(size_t)f * nb + i] = exp(wave[i]);
+    irfft_unscaled(fft_size, re, zero, wave);
+    for (int i = 0; i <= half; ++i) spectrogram[(size_t)f * nb + i] = (double)exp(wave[i]);
   }
   free(wave); free(win); free(re); free(im); free(zero);
 }
@@ -1072,20 +1169,20 @@ void wo_cheaptrick(const double *x, int x_length, int fs, const double *tpos, co
 /* ------------------------------------------------------------------ */
 /* d4c.cpp:21-84 ; kind 1 = Hanning, 2 = Blackman */
 static int d4c_window(const double *x, int n, int fs, double f0, double pos, int kind,
-                      double ratio, double *wave, uint32_t rng[4]) {
+                      double ratio, wo_real *wave, uint32_t rng[4]) {
   int hw = wo_round(ratio * fs / f0 / 2.0);
   int origin = wo_round(pos * fs + 0.001);
-  double *win = dalloc(2 * hw + 1);
+  wo_real *win = ralloc(2 * hw + 1);
   for (int i = 0; i <= 2 * hw; ++i) {
-    double p = (2.0 * (i - hw) / ratio) / fs;
+    wo_real p = ((wo_real)2.0 * (i - hw) / ratio) / fs;
     if (kind == 1) win[i] = 0.5 * cos(K_PI * p * f0) + 0.5;
     else win[i] = 0.42 + 0.5 * cos(K_PI * p * f0) + 0.08 * cos(K_PI * p * f0 * 2);
   }
   for (int i = 0; i <= 2 * hw; ++i)
-    wave[i] = x[imin(n - 1, imax(0, origin + i - hw))] * win[i] + wo_randn(rng) * 0.000001;
-  double s1 = 0, s2 = 0;
+    wave[i] = x[imin(n - 1, imax(0, origin + i - hw))] * win[i] + (wo_real)wo_randn(rng) * 0.000001;
+  wo_real s1 = 0, s2 = 0;
   for (int i = 0; i <= 2 * hw; ++i) { s1 += wave[i]; s2 += win[i]; }
-  double coef = s1 / s2;
+  wo_real coef = s1 / s2;
   for (int i = 0; i <= 2 * hw; ++i) wave[i] -= win[i] * coef;
   free(win);
   return hw;
@@ -1093,17 +1190,17 @@ static int d4c_window(const double *x, int n, int fs, double f0, double pos, int
 
 /* d4c.cpp:90-120 */
 static void d4c_centroid(const double *x, int n, int fs, double f0, int N, double pos,
-                         double *wave, double *cen, uint32_t rng[4]) {
-  memset(wave, 0, sizeof(double) * N);
+                         wo_real *wave, wo_real *cen, uint32_t rng[4]) {
+  memset(wave, 0, sizeof(wo_real) * N);
   d4c_window(x, n, fs, f0, pos, 2, 4.0, wave, rng);
   int last = wo_round(2.0 * fs / f0) * 2;
-  double pw = 0.0;
+  wo_real pw = 0.0;
   for (int i = 0; i <= last; ++i) pw += wave[i] * wave[i];
   for (int i = 0; i <= last; ++i) wave[i] /= sqrt(pw);
-  double *ar = dalloc(N / 2 + 1), *ai = dalloc(N / 2 + 1), *br = dalloc(N / 2 + 1), *bi = dalloc(N / 2 + 1);
-  wo_rfft(N, wave, ar, ai);
-  for (int i = 0; i < N; ++i) wave[i] *= i + 1.0;
-  wo_rfft(N, wave, br, bi);
+  wo_real *ar = ralloc(N / 2 + 1), *ai = ralloc(N / 2 + 1), *br = ralloc(N / 2 + 1), *bi = ralloc(N / 2 + 1);
+  rfft(N, wave, ar, ai);
+  for (int i = 0; i < N; ++i) wave[i] *= i + (wo_real)1.0;
+  rfft(N, wave, br, bi);
   for (int i = 0; i <= N / 2; ++i) cen[i] = br[i] * ar[i] + ai[i] * bi[i];
   free(ar); free(ai); free(br); free(bi);
 }
@@ -1118,21 +1215,21 @@ void wo_d4c(const double *x, int x_length, int fs, const double *tpos, const dou
   int N = (int)pow(2.0, 1.0 + (int)(log(4.0 * fs / 47.0 + 1) / K_LOG2));
   int nap = (int)(dmin(15000.0, fs / 2.0 - 3000.0) / 3000.0);
   int wl = (int)(3000.0 * N / fs) * 2 + 1;
-  double *nut = dalloc(wl);
-  wo_nuttall(wl, nut);
+  wo_real *nut = ralloc(wl);
+  nuttall(wl, nut);
 
   /* pass 1: D4CLoveTrain (227-285) */
-  double *ap0 = dalloc(nf);
+  wo_real *ap0 = ralloc(nf);
   {
     int M = (int)pow(2.0, 1.0 + (int)(log(3.0 * fs / 40.0 + 1) / K_LOG2));
     int b0 = (int)ceil(100.0 * M / fs), b1 = (int)ceil(4000.0 * M / fs), b2 = (int)ceil(7900.0 * M / fs);
-    double *wave = dalloc(M), *re = dalloc(M / 2 + 1), *im = dalloc(M / 2 + 1), *ps = dalloc(M);
+    wo_real *wave = ralloc(M), *re = ralloc(M / 2 + 1), *im = ralloc(M / 2 + 1), *ps = ralloc(M);
     for (int f = 0; f < nf; ++f) {
       if (f0[f] == 0.0) { ap0[f] = 0.0; continue; }
       double cf0 = dmax(f0[f], 40.0);
       int hw = d4c_window(x, x_length, fs, cf0, tpos[f], 2, 3.0, wave, rng);
       for (int i = 2 * hw + 1; i < M; ++i) wave[i] = 0.0;
-      wo_rfft(M, wave, re, im);
+      rfft(M, wave, re, im);
       for (int i = 0; i <= b0; ++i) ps[i] = 0.0;
       for (int i = b0 + 1; i < M / 2 + 1; ++i) ps[i] = re[i] * re[i] + im[i] * im[i];
       for (int i = b0; i <= b2; ++i) ps[i] += +ps[i - 1];
@@ -1142,15 +1239,16 @@ void wo_d4c(const double *x, int x_length, int fs, const double *tpos, const dou
   }
 
   /* pass 2: D4CGeneralBody on frames that pass the threshold (293-395) */
-  double *coarse = dalloc(nap + 2), *caxis = dalloc(nap + 2), *faxis = dalloc(nb);
+  wo_real *coarse = ralloc(nap + 2);
+  double *caxis = dalloc(nap + 2), *faxis = dalloc(nb);
   coarse[0] = -60.0; coarse[nap + 1] = -K_TINY;
   for (int i = 0; i <= nap; ++i) caxis[i] = i * 3000.0;
   caxis[nap + 1] = fs / 2.0;
   for (int i = 0; i < nb; ++i) faxis[i] = (double)i * fs / fft_size;
   int H = N / 2;
-  double *wave = dalloc(N), *c1 = dalloc(H + 1), *c2 = dalloc(H + 1), *sc = dalloc(H + 1);
-  double *sp = dalloc(H + 1), *gd = dalloc(H + 1), *sg = dalloc(H + 1);
-  double *re = dalloc(H + 1), *im = dalloc(H + 1), *ps = dalloc(H + 1);
+  wo_real *wave = ralloc(N), *c1 = ralloc(H + 1), *c2 = ralloc(H + 1), *sc = ralloc(H + 1);
+  wo_real *sp = ralloc(H + 1), *gd = ralloc(H + 1), *sg = ralloc(H + 1);
+  wo_real *re = ralloc(H + 1), *im = ralloc(H + 1), *ps = ralloc(H + 1), *row = ralloc(nb);
   for (int f = 0; f < nf; ++f) {
     if (f0[f] == 0 || ap0[f] <= threshold) continue;
     double cf0 = dmax(47.0, f0[f]);
@@ -1158,44 +1256,43 @@ void wo_d4c(const double *x, int x_length, int fs, const double *tpos, const dou
     d4c_centroid(x, x_length, fs, cf0, N, tpos[f] - 0.25 / cf0, wave, c1, rng);
     d4c_centroid(x, x_length, fs, cf0, N, tpos[f] + 0.25 / cf0, wave, c2, rng);
     for (int i = 0; i <= H; ++i) sc[i] = c1[i] + c2[i];
-    wo_dc_correction(sc, cf0, fs, N, sc);
+    dc_correction(sc, cf0, fs, N, sc);
     /* smoothed power spectrum (149-166) */
-    memset(wave, 0, sizeof(double) * N);
+    memset(wave, 0, sizeof(wo_real) * N);
     d4c_window(x, x_length, fs, cf0, tpos[f], 1, 4.0, wave, rng);
-    wo_rfft(N, wave, re, im);
+    rfft(N, wave, re, im);
     for (int i = 0; i <= H; ++i) sp[i] = re[i] * re[i] + im[i] * im[i];
-    wo_dc_correction(sp, cf0, fs, N, sp);
-    wo_linear_smoothing(sp, cf0, fs, N, sp);
+    dc_correction(sp, cf0, fs, N, sp);
+    linear_smoothing(sp, cf0, fs, N, sp);
     /* static group delay (172-188) */
     for (int i = 0; i <= H; ++i) gd[i] = sc[i] / sp[i];
-    wo_linear_smoothing(gd, cf0 / 2.0, fs, N, gd);
-    wo_linear_smoothing(gd, cf0, fs, N, sg);
+    linear_smoothing(gd, cf0 / 2.0, fs, N, gd);
+    linear_smoothing(gd, cf0, fs, N, sg);
     for (int i = 0; i <= H; ++i) gd[i] -= sg[i];
     /* coarse aperiodicity (194-225) */
     int bnd = wo_round(N * 8.0 / wl), hwl = wl / 2;
-    memset(wave, 0, sizeof(double) * N);
+    memset(wave, 0, sizeof(wo_real) * N);
     for (int b = 0; b < nap; ++b) {
       int center = (int)(3000.0 * (b + 1) * N / fs);
       for (int j = 0; j <= hwl * 2; ++j) wave[j] = gd[center - hwl + j] * nut[j];
-      wo_rfft(N, wave, re, im);
+      rfft(N, wave, re, im);
       for (int j = 0; j <= H; ++j) ps[j] = re[j] * re[j] + im[j] * im[j];
       /* ascending sort; any correct sort gives the same array */
       for (int gap = (H + 1) / 2; gap > 0; gap /= 2)
         for (int i = gap; i <= H; ++i) {
-          double t = ps[i]; int j = i;
+          wo_real t = ps[i]; int j = i;
           for (; j >= gap && ps[j - gap] > t; j -= gap) ps[j] = ps[j - gap];
           ps[j] = t;
         }
       for (int j = 1; j <= H; ++j) ps[j] += ps[j - 1];
       coarse[1 + b] = 10 * log10(ps[H - bnd - 1] / ps[H]);
     }
-    for (int b = 0; b < nap; ++b) coarse[1 + b] = dmin(0.0, coarse[1 + b] + (cf0 - 100) / 50.0);
+    for (int b = 0; b < nap; ++b) coarse[1 + b] = rmin(0.0, coarse[1 + b] + (cf0 - (wo_real)100) / 50.0);
     /* spectral representation (330-338) */
-    double *row = aperiodicity + (size_t)f * nb;
-    wo_interp1(caxis, coarse, nap + 2, faxis, nb, row);
-    for (int i = 0; i < nb; ++i) row[i] = pow(10.0, row[i] / 20.0);
+    interp1(caxis, coarse, nap + 2, faxis, nb, row);
+    for (int i = 0; i < nb; ++i) aperiodicity[(size_t)f * nb + i] = (double)pow((wo_real)10.0, row[i] / 20.0);
   }
-  free(nut); free(ap0); free(coarse); free(caxis); free(faxis);
+  free(nut); free(ap0); free(coarse); free(caxis); free(faxis); free(row);
   free(wave); free(c1); free(c2); free(sc); free(sp); free(gd); free(sg); free(re); free(im); free(ps);
 }
 
@@ -1295,7 +1392,7 @@ void wo_decode_spectral_envelope(const double *coded, int nf, int fs, int fft_si
     }
     /* the reference's backward c2c (fft.cpp:36-45) returns conj(sum in[j] e^{-2 pi i jk/n});
      * only its real part is read here */
-    cfft(md, zr, zi, -1);
+    cfft_double(md, zr, zi, -1);
     for (int i = 0; i < md / 2; ++i) {
       mel[1 + i * 2] = zr[i];
       mel[1 + i * 2 + 1] = zr[md - i - 1];
@@ -1314,12 +1411,12 @@ void wo_decode_spectral_envelope(const double *coded, int nf, int fs, int fft_si
 /* ------------------------------------------------------------------ */
 /* GetMinimumPhaseSpectrum (common.cpp:182-220).  lg[0..N/2] in; (mr, mi)[0..N/2] out.
  * The reference's forward c2c plan computes FFT(conj(x)) (fft.cpp:62-71). */
-static void minimum_phase(const double *lg, int N, double *mr, double *mi) {
+static void minimum_phase(const wo_real *lg, int N, wo_real *mr, wo_real *mi) {
   int H = N / 2;
-  double *full = dalloc(N), *cr = dalloc(H + 1), *ci = dalloc(H + 1), *zr = dalloc(N), *zi = dalloc(N);
+  wo_real *full = ralloc(N), *cr = ralloc(H + 1), *ci = ralloc(H + 1), *zr = ralloc(N), *zi = ralloc(N);
   for (int i = 0; i <= H; ++i) full[i] = lg[i];
   for (int i = H + 1; i < N; ++i) full[i] = lg[N - i];
-  wo_rfft(N, full, cr, ci);
+  rfft(N, full, cr, ci);
   zr[0] = cr[0]; zi[0] = -ci[0];
   for (int i = 1; i < H; ++i) { zr[i] = cr[i] * 2.0; zi[i] = ci[i] * -2.0; }
   zr[H] = cr[H]; zi[H] = -ci[H];
@@ -1327,26 +1424,29 @@ static void minimum_phase(const double *lg, int N, double *mr, double *mi) {
   for (int i = 0; i < N; ++i) zi[i] = -zi[i];            /* conj of the input ... */
   cfft(N, zr, zi, -1);                                   /* ... forward transform */
   for (int i = 0; i <= H; ++i) {
-    double t = exp(zr[i] / N);
+    wo_real t = exp(zr[i] / N);
     mr[i] = t * cos(zi[i] / N);
     mi[i] = t * sin(zi[i] / N);
   }
   free(full); free(cr); free(ci); free(zr); free(zi);
 }
 
-static void fft_shift(const double *x, int n, double *y) {          /* matlabfunctions.cpp:129-134 */
+static void fft_shift(const wo_real *x, int n, wo_real *y) {        /* matlabfunctions.cpp:129-134 */
   for (int i = 0; i < n / 2; ++i) { y[i] = x[i + n / 2]; y[i + n / 2] = x[i]; }
 }
 
 static double safe_ap(double x) { return dmax(0.001, dmin(0.999999999999, x)); }   /* common.h:111-113 */
 
+/* The time base -- instantaneous F0, phase, pulse positions and fractional shifts -- decides where
+ * the pulses fall, so it stays double in both builds; the per-pulse responses and the overlap-add are wo_real. */
 void wo_synthesis(const double *f0, int nf, const double *sp, const double *ap, int fft_size,
                   double frame_period, int fs, int y_length, double *y) {
   const int N = fft_size, H = N / 2, nb = H + 1;
-  const double two_pi = 2.0 * K_PI;
+  const double two_pi_d = 2.0 * K_PI;
+  const wo_real two_pi = 2.0 * K_PI;
   uint32_t rng[4];
   wo_randn_seed(rng);
-  for (int i = 0; i < y_length; ++i) y[i] = 0.0;
+  wo_real *acc = ralloc(y_length);
   double fp = frame_period / 1000.0;
   /* ---- GetTimeBase (synthesis.cpp:225-318) ---- */
   double lowest_f0 = fs / fft_size + 1.0;                /* integer division, as in the reference's call (:361) */
@@ -1370,24 +1470,24 @@ void wo_synthesis(const double *f0, int nf, const double *sp, const double *ap, 
   double *total = dalloc(y_length), *wrap = dalloc(y_length);
   double *ploc = dalloc(y_length), *pshift = dalloc(y_length);
   int *pidx = ialloc(y_length);
-  total[0] = two_pi * if0[0] / fs;
-  wrap[0] = fmod(total[0], two_pi);
+  total[0] = two_pi_d * if0[0] / fs;
+  wrap[0] = fmod(total[0], two_pi_d);
   for (int i = 1; i < y_length; ++i) {
-    total[i] = total[i - 1] + two_pi * if0[i] / fs;
-    wrap[i] = fmod(total[i], two_pi);
+    total[i] = total[i - 1] + two_pi_d * if0[i] / fs;
+    wrap[i] = fmod(total[i], two_pi_d);
   }
   int np = 0;
   for (int i = 0; i < y_length - 1; ++i) {
-    if (fabs(wrap[i + 1] - wrap[i]) > K_PI) {
+    if (fabs(wrap[i + 1] - wrap[i]) > (double)K_PI) {
       ploc[np] = time_axis[i];
       pidx[np] = i;
-      double y1 = wrap[i] - two_pi, y2 = wrap[i + 1];
+      double y1 = wrap[i] - two_pi_d, y2 = wrap[i + 1];
       pshift[np] = (-y1 / (y2 - y1)) / fs;
       ++np;
     }
   }
   /* ---- GetDCRemover (:320-335) ---- */
-  double *rem = dalloc(N), dcsum = 0.0;
+  wo_real *rem = ralloc(N), dcsum = 0.0;
   for (int i = 0; i < H; ++i) {
     rem[i] = 0.5 - 0.5 * cos(two_pi * (i + 1.0) / (1.0 + N));
     rem[N - i - 1] = rem[i];
@@ -1395,19 +1495,19 @@ void wo_synthesis(const double *f0, int nf, const double *sp, const double *ap, 
   }
   for (int i = 0; i < H; ++i) { rem[i] /= dcsum; rem[N - i - 1] = rem[i]; }
 
-  double *env = dalloc(nb), *ratio = dalloc(nb), *lg = dalloc(nb), *mr = dalloc(nb), *mi = dalloc(nb);
-  double *sr = dalloc(nb), *si = dalloc(nb), *wave = dalloc(N), *per = dalloc(N), *aper = dalloc(N), *tmp = dalloc(N);
-  double *nr = dalloc(nb), *ni = dalloc(nb);
+  wo_real *env = ralloc(nb), *ratio = ralloc(nb), *lg = ralloc(nb), *mr = ralloc(nb), *mi = ralloc(nb);
+  wo_real *sr = ralloc(nb), *si = ralloc(nb), *wave = ralloc(N), *per = ralloc(N), *aper = ralloc(N), *tmp = ralloc(N);
+  wo_real *nr = ralloc(nb), *ni = ralloc(nb);
   for (int p = 0; p < np; ++p) {
     int nxt = p + 1 < np - 1 ? p + 1 : np - 1;
     int noise_size = pidx[nxt] - pidx[p];
     double vuv = ivuv[pidx[p]], t = ploc[p];
     /* GetSpectralEnvelope / GetAperiodicRatio (:140-180) */
     int ff = imin(nf - 1, (int)floor(t / fp)), fc = imin(nf - 1, (int)ceil(t / fp));
-    double w = t / fp - ff;
+    wo_real w = (wo_real)t / fp - ff;
     for (int i = 0; i < nb; ++i) {
-      double a0 = fabs(sp[(size_t)ff * nb + i]), a1 = fabs(sp[(size_t)fc * nb + i]);
-      double b0 = safe_ap(ap[(size_t)ff * nb + i]), b1 = safe_ap(ap[(size_t)fc * nb + i]);
+      wo_real a0 = fabs(sp[(size_t)ff * nb + i]), a1 = fabs(sp[(size_t)fc * nb + i]);
+      wo_real b0 = safe_ap(ap[(size_t)ff * nb + i]), b1 = safe_ap(ap[(size_t)fc * nb + i]);
       if (ff == fc) { env[i] = a0; ratio[i] = pow(b0, 2.0); }
       else { env[i] = (1.0 - w) * a0 + w * a1; ratio[i] = pow((1.0 - w) * b0 + w * b1, 2.0); }
     }
@@ -1417,26 +1517,26 @@ void wo_synthesis(const double *f0, int nf, const double *sp, const double *ap, 
     } else {
       for (int i = 0; i < nb; ++i) lg[i] = log(env[i] * (1.0 - ratio[i]) + K_TINY) / 2.0;
       minimum_phase(lg, N, mr, mi);
-      double coef = two_pi * pshift[p] * fs / N;
+      wo_real coef = two_pi * pshift[p] * fs / N;
       for (int i = 0; i < nb; ++i) {                     /* GetSpectrumWithFractionalTimeShift (:86-98) */
-        double re2 = cos(coef * i), im2 = sqrt(1.0 - re2 * re2);
+        wo_real re2 = cos(coef * i), im2 = sqrt(1.0 - re2 * re2);
         sr[i] = mr[i] * re2 + mi[i] * im2;
         si[i] = mi[i] * re2 - mr[i] * im2;
       }
-      wo_irfft_unscaled(N, sr, si, tmp);
+      irfft_unscaled(N, sr, si, tmp);
       fft_shift(tmp, N, per);
-      double dc = 0.0;                                   /* RemoveDCComponent in place (:72-80) */
+      wo_real dc = 0.0;                                  /* RemoveDCComponent in place (:72-80) */
       for (int i = H; i < N; ++i) dc += per[i];
       for (int i = 0; i < H; ++i) per[i] = -dc * rem[i];
       for (int i = H; i < N; ++i) per[i] -= dc * rem[i];
     }
     /* GetAperiodicResponse (:38-66) with GetNoiseSpectrum (:19-33) */
-    double avg = 0.0;
+    wo_real avg = 0.0;
     for (int i = 0; i < noise_size; ++i) { wave[i] = wo_randn(rng); avg += wave[i]; }
     avg /= noise_size;
     for (int i = 0; i < noise_size; ++i) wave[i] -= avg;
     for (int i = noise_size > 0 ? noise_size : 0; i < N; ++i) wave[i] = 0.0;
-    wo_rfft(N, wave, nr, ni);
+    rfft(N, wave, nr, ni);
     if (vuv != 0.0) for (int i = 0; i < nb; ++i) lg[i] = log(env[i] * ratio[i]) / 2.0;
     else for (int i = 0; i < nb; ++i) lg[i] = log(env[i]) / 2.0;
     minimum_phase(lg, N, mr, mi);
@@ -1444,14 +1544,16 @@ void wo_synthesis(const double *f0, int nf, const double *sp, const double *ap, 
       sr[i] = mr[i] * nr[i] - mi[i] * ni[i];
       si[i] = mr[i] * ni[i] + mi[i] * nr[i];
     }
-    wo_irfft_unscaled(N, sr, si, tmp);
+    irfft_unscaled(N, sr, si, tmp);
     fft_shift(tmp, N, aper);
     /* GetOneFrameSegment (:213-218) and the overlap-add (:376-385) */
-    double sq = sqrt((double)noise_size);
+    wo_real sq = sqrt((wo_real)noise_size);
     int offset = pidx[p] - H + 1;
     int lo = imax(0, -offset), hi = imin(N, y_length - offset);
-    for (int j = lo; j < hi; ++j) y[j + offset] += (per[j] * sq + aper[j]) / N;
+    for (int j = lo; j < hi; ++j) acc[j + offset] += (per[j] * sq + aper[j]) / N;
   }
+  to_double(acc, y_length, y);
+  free(acc);
   free(time_axis); free(ctime); free(cf0); free(cvuv); free(if0); free(ivuv); free(total); free(wrap);
   free(ploc); free(pshift); free(pidx); free(rem); free(env); free(ratio); free(lg); free(mr); free(mi);
   free(sr); free(si); free(wave); free(per); free(aper); free(tmp); free(nr); free(ni);

@@ -134,3 +134,90 @@ def option_defaults(L):
         getattr(L, init)(ctypes.byref(a))
         out[init] = np.frombuffer(bytes(a), dtype=np.uint8)
     return out
+
+
+# ---- accuracy against a more precise answer (tests/test_gpu_accuracy.py, tests/test_accuracy_cpu.py) ----------------------
+# W = oracle/libworld_oracle_wide.so (long double value arithmetic, same discrete path), R = the unmodified reference,
+# H = the code under test.  Per array, with e_X = |X - W| / |W| element-wise (Synthesis: / max|W|), for each quantile q:
+#     quantile_q(e_H) <= ACC_A * quantile_q(e_R) + ACC_C * 2^-52
+# The median catches a uniform loss of digits, the maximum a single bad bin or row.  A and c: DESIGN.md section 6.
+ACC_A = 4.0
+ACC_C = 64.0
+ACC_QUANTILES = (0.5, 0.99, 1.0)
+ULP = 2.0 ** -52
+
+
+def rel_errors(a, w, peak=False):
+    a = np.asarray(a, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    scale = np.max(np.abs(w)) if peak else np.abs(w)
+    return np.abs(a - w) / np.maximum(scale, 1e-300)
+
+
+def discrete_agreement(what, h, r, w, max_w_only=None):
+    """Per-row discrete outcomes (V/UV, LoveTrain exit, StoneMask fallback ...): H and R must agree on every row; rows where
+    W alone decides differently are returned (to be excluded from the value comparison), and there may be only a few."""
+    h, r, w = (np.asarray(v) for v in (h, r, w))
+    assert h.shape == r.shape == w.shape, what
+    bad = np.flatnonzero(h != r)
+    assert bad.size == 0, f"{what}: H and R decide differently on rows {bad[:10].tolist()} (of {bad.size})"
+    w_only = np.flatnonzero(w != r)
+    limit = max(2, len(r) // 50) if max_w_only is None else max_w_only
+    assert w_only.size <= limit, f"{what}: the wide oracle alone decides differently on {w_only.size} rows (limit {limit})"
+    return w_only
+
+
+def accuracy_stats(h, r, w, peak=False, rows=None):
+    """(e_H quantiles, e_R quantiles, worst index of e_H) over the selected rows (all rows when None)"""
+    h, r, w = (np.asarray(v, dtype=np.float64) for v in (h, r, w))
+    if rows is not None:
+        h, r, w = h[rows], r[rows], w[rows]
+    eh, er = rel_errors(h, w, peak), rel_errors(r, w, peak)
+    worst = np.unravel_index(int(np.argmax(eh)), eh.shape) if eh.size else ()
+    return np.quantile(eh, ACC_QUANTILES), np.quantile(er, ACC_QUANTILES), worst, eh, er
+
+
+def assert_accurate(what, h, r, w, peak=False, exclude_rows=(), A=ACC_A, c=ACC_C, log=True):
+    """The accuracy criterion above, on every row (but `exclude_rows`) and every bin.  Prints the worst element on failure."""
+    h, r, w = (np.asarray(v, dtype=np.float64) for v in (h, r, w))
+    assert h.shape == r.shape == w.shape, f"{what}: shapes {h.shape} {r.shape} {w.shape}"
+    keep = np.ones(h.shape[0], dtype=bool)
+    keep[list(exclude_rows)] = False
+    index = np.flatnonzero(keep)
+    assert index.size, f"{what}: nothing left to compare"
+    qh, qr, worst, eh, er = accuracy_stats(h, r, w, peak, index)
+    if log:
+        _log_accuracy(what, qh, qr, len(exclude_rows), h.size)
+    bound = A * qr + c * ULP
+    failed = [q for q, a, b in zip(ACC_QUANTILES, qh, bound) if not a <= b]
+    if failed:
+        row = (int(index[worst[0]]),) + tuple(int(i) for i in worst[1:])
+        msg = (f"{what}: e_H quantiles {qh.tolist()} exceed {A} * e_R {qr.tolist()} + {c} ulp at q = {failed}; "
+               f"worst element {row}: e_H {eh[worst]:.3e}, e_R {er[worst]:.3e} (H {h[row]!r}, R {r[row]!r}, W {w[row]!r})")
+        print(msg)
+        raise AssertionError(msg)
+    return qh, qr
+
+
+def _log_accuracy(what, qh, qr, excluded, n):
+    """WORLD_ACCURACY_LOG=<file>: one JSON line per checked array (the source of DESIGN.md section 6's table)"""
+    path = os.environ.get("WORLD_ACCURACY_LOG")
+    if path:
+        import json
+        with open(path, "a") as f:
+            f.write(json.dumps({"what": what, "e_H": [float(v) for v in qh], "e_R": [float(v) for v in qr],
+                                "excluded_rows": int(excluded), "elements": int(n)}) + "\n")
+
+
+def assert_f0_tight(what, h, r, rtol=1e-10):
+    """Harvest / DIO against the reference: identical V/UV, F0 within rtol relative on voiced frames."""
+    h, r = np.asarray(h, dtype=np.float64), np.asarray(r, dtype=np.float64)
+    assert h.shape == r.shape, what
+    flips = np.flatnonzero((h > 0) != (r > 0))
+    assert flips.size == 0, f"{what}: voiced/unvoiced differ at frames {flips[:10].tolist()}"
+    v = r > 0
+    assert v.any(), f"{what}: no voiced frame to compare"
+    e = np.abs(h[v] - r[v]) / r[v]
+    _log_accuracy(what, np.quantile(e, ACC_QUANTILES), np.zeros(3), 0, int(v.sum()))
+    i = int(np.argmax(e))
+    assert e[i] <= rtol, f"{what}: F0 rel err {e[i]:.3e} at frame {int(np.flatnonzero(v)[i])} (H {h[v][i]!r}, R {r[v][i]!r})"
