@@ -103,10 +103,108 @@ WORLD_HIP_API void DecodeSpectralEnvelope(const double *const *coded_spectral_en
                                           int fft_size, int number_of_dimensions, double **spectrogram);
 
 /* reference src/world/synthesis.h:30 (src/synthesis.cpp:339-399) -- SURVEY.md 8f.3.  The only public
- * symbol of synthesis.o; SynthesisRealtime (synthesisrealtime.o) is not provided. */
+ * symbol of synthesis.o; the real-time synthesiser of synthesisrealtime.o follows below. */
 WORLD_HIP_API void Synthesis(const double *f0, int f0_length, const double *const *spectrogram,
                              const double *const *aperiodicity, int fft_size, double frame_period, int fs,
                              int y_length, double *y);
+
+/* ---- real-time synthesis: reference src/world/synthesisrealtime.h (src/synthesisrealtime.cpp) -----------------------
+ * The synthesiser struct and the types it embeds, with the reference's sizes, field offsets and public field names, so
+ * that a caller's `WorldSynthesizer s = {0};` and its reads of s.buffer, s.head_pointer, ... work unchanged.  The types
+ * below are those of the reference's world/fft.h, world/common.h and world/matlabfunctions.h; this library fills none of
+ * the FFT members (the transforms run on the GPU), and they are declared only so that the struct has its size. */
+typedef double fft_complex[2];
+typedef struct {                 /* world/fft.h: a plan of the reference's FFT (unused here) */
+  int n;
+  int sign;
+  unsigned int flags;
+  fft_complex *c_in;
+  double *in;
+  fft_complex *c_out;
+  double *out;
+  double *input;
+  int *ip;
+  double *w;
+} fft_plan;
+typedef struct {                 /* world/common.h */
+  int fft_size;
+  double *waveform;
+  fft_complex *spectrum;
+  fft_plan forward_fft;
+} ForwardRealFFT;
+typedef struct {                 /* world/common.h */
+  int fft_size;
+  double *waveform;
+  fft_complex *spectrum;
+  fft_plan inverse_fft;
+} InverseRealFFT;
+typedef struct {                 /* world/common.h */
+  int fft_size;
+  double *log_spectrum;
+  fft_complex *minimum_phase_spectrum;
+  fft_complex *cepstrum;
+  fft_plan inverse_fft;
+  fft_plan forward_fft;
+} MinimumPhaseAnalysis;
+typedef struct {                 /* world/matlabfunctions.h: xorshift128 state of randn() */
+  unsigned int g_randn_x;
+  unsigned int g_randn_y;
+  unsigned int g_randn_z;
+  unsigned int g_randn_w;
+} RandnState;
+/* What this library keeps in each field.  The contract covers every scalar field, f0_length[], f0_origin[],
+ * number_of_pulses[] and pulse_locations_index[] (host arrays mirrored after every call), randn_state (the generator
+ * after the pulses Synthesis2 has gone past), dc_remover[0, fft_size / 2) and buffer[0, buffer_size): the output of the
+ * last successful Synthesis2.  Deviations from the reference:
+ *   - the spectrogram / aperiodicity rows are read when AddParameters is called (copied to the GPU), not when they are
+ *     synthesised: a caller that rewrites rows after adding them gets the values they had when added;
+ *   - buffer[buffer_size, 2 buffer_size + fft_size) is the library's own (the reference keeps its partial sums there);
+ *   - `spectrogram` holds the library's state (an opaque handle; do not touch), `aperiodicity`, interpolated_vuv,
+ *     pulse_locations, impulse_response and the three FFT members are NULL / zero.
+ * fft_size must be a power of two from 128 to 8192 (checked before any GPU work).  Failures report through
+ * world_hip_set_error_handler (below); AddParameters, Synthesis2 and IsLocked then return 0. */
+typedef struct {
+  int fs;
+  double frame_period;           /* seconds */
+  int buffer_size;
+  int number_of_pointers;
+  int fft_size;
+  double *buffer;                /* [2 buffer_size + fft_size]; [0, buffer_size) = the last Synthesis2 output */
+  int current_pointer;
+  int i;
+  double *dc_remover;            /* [fft_size / 2] */
+  int *f0_length;                /* [number_of_pointers] */
+  int *f0_origin;                /* [number_of_pointers] */
+  double ***spectrogram;         /* this library: its state */
+  double ***aperiodicity;
+  int current_pointer2;
+  int head_pointer;
+  int synthesized_sample;
+  int handoff;
+  double handoff_phase;
+  double handoff_f0;
+  int last_location;
+  int cumulative_frame;
+  int current_frame;
+  double **interpolated_vuv;
+  double **pulse_locations;
+  int **pulse_locations_index;   /* [number_of_pointers] -> number_of_pulses[k] sample indices */
+  int *number_of_pulses;         /* [number_of_pointers] */
+  double *impulse_response;
+  RandnState randn_state;
+  MinimumPhaseAnalysis minimum_phase;
+  InverseRealFFT inverse_real_fft;
+  ForwardRealFFT forward_real_fft;
+} WorldSynthesizer;
+/* reference src/world/synthesisrealtime.h:93,112,118,123,139,151 (src/synthesisrealtime.cpp:444-603) */
+WORLD_HIP_API void InitializeSynthesizer(int fs, double frame_period, int fft_size, int buffer_size,
+                                         int number_of_pointers, WorldSynthesizer *synth);
+WORLD_HIP_API int AddParameters(double *f0, int f0_length, double **spectrogram, double **aperiodicity,
+                                WorldSynthesizer *synth);
+WORLD_HIP_API void RefreshSynthesizer(WorldSynthesizer *synth);
+WORLD_HIP_API void DestroySynthesizer(WorldSynthesizer *synth);
+WORLD_HIP_API int IsLocked(WorldSynthesizer *synth);
+WORLD_HIP_API int Synthesis2(WorldSynthesizer *synth);
 
 /* ---- audio and parameter files: the reference's tools/ library ------------
  * Same names, arguments and on-disk bytes as tools/audioio.h:25-47 and tools/parameterio.h:24-114,
@@ -204,7 +302,8 @@ WORLD_HIP_API const char *world_hip_last_error(void);
 /* Version of the batched C ABI below (the reference's own 13 symbols never change).  Bumped whenever a prototype in this
  * header changes incompatibly; a binding built against another major value must refuse to bind (world_amd/api.py does).
  *   5  round 5: world_hip_spectral_packed_range / _cheaptrick_batch_range / _d4c_batch_range take `reuse_offsets`
- *   6  round 6: + world_hip_abi_version itself; no prototype changed
+ *   6  round 6: + world_hip_abi_version itself; no prototype changed.  Later additions keep 6: they add entry points and
+ *      change no prototype (the world_hip_realtime_* calls); bindings look for them by name.
  * Libraries older than 6 lack the symbol. */
 #define WORLD_HIP_ABI_VERSION 6
 /* Launch-geometry hints of a context (bits; default 0).  Results never depend on them.
@@ -446,6 +545,37 @@ WORLD_HIP_API int world_hip_code_aperiodicity(WorldHipContext *ctx, int rows, in
                                               const double *d_aperiodicity, double *d_coded);
 WORLD_HIP_API int world_hip_decode_aperiodicity(WorldHipContext *ctx, int rows, int fs, int fft_size,
                                                 const double *d_coded, double *d_aperiodicity);
+
+/* Real-time synthesis, batched (reference src/synthesisrealtime.cpp; the drop-in WorldSynthesizer above is built on it).
+ * One object serves n_streams independent streams with one fs, frame_period (ms), fft_size, buffer_size and ring size
+ * number_of_pointers; every stream behaves exactly as one reference synthesiser: same pulses, same return values, its own
+ * randn() sequence from the seed.  Pulse schedules and ring bookkeeping run on the host; pulse responses and the
+ * overlap-add on the GPU, on the context's stream (the object uses the context; destroy the object first).
+ *   _add: AddParameters of one chunk of n_frames frames: f0 is HOST memory, the spectrogram / aperiodicity rows are DEVICE
+ *       rows row_stride doubles apart (fft_size / 2 + 1 used), e.g. records of world_hip_analyze_packed.  They are copied
+ *       into the stream's frame store on the stream before the call returns, so the caller may reuse its buffers for
+ *       later work on the same stream.  Returns 1 (added), 0 (the stream's ring is full), -1 (error: world_hip_last_error).
+ *   _synthesize: Synthesis2 for every stream at once: produced[s] (host) = its return value; d_out [n_streams][buffer_size]
+ *       (device) gets each producing stream's buffer, zeros for the others.  When some streams need samples not yet
+ *       rendered, their pulses that have a successor are rendered in batches of two kernels and one wait for the download:
+ *       first what each stream's next buffer needs, then ahead, up to 256 MB of responses per batch.  One batch whatever
+ *       n_streams while that holds (about 10 900 pulses at fft 2048, 2 700 at fft 8192); more batches only when it
+ *       does not.  Calls that find their samples rendered only copy.  0 / -1; after -1 no stream
+ *       has advanced (produced and d_out untouched).
+ *   _is_locked: IsLocked (1 / 0; -1 = error).  _refresh: RefreshSynthesizer of one stream (0 / -1).
+ *   _create: 0 = success, non-zero = failure (world_hip_last_error), as the calls above; *out = NULL then. */
+typedef struct WorldHipRealtime WorldHipRealtime;
+WORLD_HIP_API int world_hip_realtime_create(WorldHipContext *ctx, int n_streams, int fs, double frame_period_ms,
+                                            int fft_size, int buffer_size, int number_of_pointers,
+                                            WorldHipRealtime **out);
+WORLD_HIP_API void world_hip_realtime_destroy(WorldHipRealtime *rt);
+WORLD_HIP_API int world_hip_realtime_add(WorldHipRealtime *rt, int stream, const double *f0, int n_frames,
+                                         const double *d_sp, const double *d_ap, int row_stride);
+WORLD_HIP_API int world_hip_realtime_synthesize(WorldHipRealtime *rt, double *d_out, int *produced);
+WORLD_HIP_API int world_hip_realtime_is_locked(WorldHipRealtime *rt, int stream);
+WORLD_HIP_API int world_hip_realtime_refresh(WorldHipRealtime *rt, int stream);
+/* test hook: the randn() generator state `draws` calls after `state` ({x, y, z, w}), as the scheduler computes it */
+WORLD_HIP_API void world_hip_realtime_rng_jump(const unsigned int *state, unsigned long long draws, unsigned int *out);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ The extension must exist: importing this module on a machine where
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -41,6 +42,145 @@ class CheapTrickOption(C.Structure):  # reference cheaptrick.h:16-20
 
 class D4COption(C.Structure):        # reference d4c.h:16-18
     _fields_ = [("threshold", C.c_double)]
+
+
+# -- the real-time synthesiser (reference synthesisrealtime.h; include/world_hip.h declares the same layout) --
+class RandnState(C.Structure):       # reference matlabfunctions.h
+    _fields_ = [("g_randn_x", C.c_uint32), ("g_randn_y", C.c_uint32), ("g_randn_z", C.c_uint32), ("g_randn_w", C.c_uint32)]
+
+
+class FftPlan(C.Structure):          # reference fft.h
+    _fields_ = [("n", C.c_int), ("sign", C.c_int), ("flags", C.c_uint), ("c_in", C.c_void_p), ("in_", C.c_void_p),
+                ("c_out", C.c_void_p), ("out", C.c_void_p), ("input", C.c_void_p), ("ip", C.c_void_p), ("w", C.c_void_p)]
+
+
+class ForwardRealFFT(C.Structure):   # reference common.h
+    _fields_ = [("fft_size", C.c_int), ("waveform", C.c_void_p), ("spectrum", C.c_void_p), ("forward_fft", FftPlan)]
+
+
+class InverseRealFFT(C.Structure):   # reference common.h
+    _fields_ = [("fft_size", C.c_int), ("waveform", C.c_void_p), ("spectrum", C.c_void_p), ("inverse_fft", FftPlan)]
+
+
+class MinimumPhaseAnalysis(C.Structure):   # reference common.h
+    _fields_ = [("fft_size", C.c_int), ("log_spectrum", C.c_void_p), ("minimum_phase_spectrum", C.c_void_p),
+                ("cepstrum", C.c_void_p), ("inverse_fft", FftPlan), ("forward_fft", FftPlan)]
+
+
+class WorldSynthesizer(C.Structure):  # reference synthesisrealtime.h
+    _fields_ = [("fs", C.c_int), ("frame_period", C.c_double), ("buffer_size", C.c_int), ("number_of_pointers", C.c_int),
+                ("fft_size", C.c_int), ("buffer", _dp), ("current_pointer", C.c_int), ("i", C.c_int),
+                ("dc_remover", _dp), ("f0_length", _ip), ("f0_origin", _ip), ("spectrogram", C.c_void_p),
+                ("aperiodicity", C.c_void_p), ("current_pointer2", C.c_int), ("head_pointer", C.c_int),
+                ("synthesized_sample", C.c_int), ("handoff", C.c_int), ("handoff_phase", C.c_double),
+                ("handoff_f0", C.c_double), ("last_location", C.c_int), ("cumulative_frame", C.c_int),
+                ("current_frame", C.c_int), ("interpolated_vuv", C.c_void_p), ("pulse_locations", C.c_void_p),
+                ("pulse_locations_index", C.POINTER(_ip)), ("number_of_pulses", _ip), ("impulse_response", _dp),
+                ("randn_state", RandnState), ("minimum_phase", MinimumPhaseAnalysis),
+                ("inverse_real_fft", InverseRealFFT), ("forward_real_fft", ForwardRealFFT)]
+
+
+# the synthesiser's scalar control fields, in the order run_realtime_plan records them (after op, return value)
+REALTIME_SCALARS = ("current_pointer", "i", "current_pointer2", "head_pointer", "synthesized_sample", "handoff",
+                    "handoff_phase", "handoff_f0", "last_location", "cumulative_frame", "current_frame")
+RT_ADD, RT_SYNTH, RT_LOCKED, RT_REFRESH = 0, 1, 2, 3
+
+
+def bind_realtime(L):
+    """argument types of the six real-time symbols on any library that has them (this one, or a reference build)"""
+    sp = C.POINTER(WorldSynthesizer)
+    L.InitializeSynthesizer.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, sp]
+    L.InitializeSynthesizer.restype = None
+    L.AddParameters.argtypes = [_dp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), sp]
+    L.RefreshSynthesizer.argtypes = [sp]
+    L.RefreshSynthesizer.restype = None
+    L.DestroySynthesizer.argtypes = [sp]
+    L.DestroySynthesizer.restype = None
+    L.IsLocked.argtypes = [sp]
+    L.Synthesis2.argtypes = [sp]
+    return L
+
+
+def run_realtime_plan(L, plan):
+    """Drive one reference-style synthesiser through a chunk plan and record everything its contract covers.
+
+    plan: fs, frame_period (ms), fft_size, buffer_size, number_of_pointers, f0 [F], sp / ap [F][fft/2+1], chunks (frame
+    counts that add up to at most F) and optionally drain_every (Synthesis2 until 0, then IsLocked, after every k-th
+    successful AddParameters and after every refused one; default 1), refresh_before (RefreshSynthesizer before adding
+    that chunk; default -1), stop_on_lock (stop at the first IsLocked() == 1, as test.cpp's "Synthesis 3" does).
+
+    Returns a dict: calls [n, 2 + len(REALTIME_SCALARS) + 4] (op, return value, the scalar fields, randn_state after the
+    call), out (every successful Synthesis2's buffer[0, buffer_size), concatenated), pulses (the pulse indices of every
+    added chunk, concatenated), pulse_counts, rings [adds][3][number_of_pointers] (f0_length, f0_origin,
+    number_of_pulses after each successful add; slots not written yet read 0)."""
+    fs, fp, fft, bs, P = (int(plan["fs"]), float(plan["frame_period"]), int(plan["fft_size"]), int(plan["buffer_size"]),
+                          int(plan["number_of_pointers"]))
+    f0, sp, ap = _f64(plan["f0"]), _f64(plan["sp"]), _f64(plan["ap"])
+    chunks = [int(c) for c in plan["chunks"]]
+    drain_every = int(plan.get("drain_every", 1))
+    refresh_before = int(plan.get("refresh_before", -1))
+    stop_on_lock = bool(plan.get("stop_on_lock", False))
+    # the reference keeps the caller's row-pointer arrays (not the rows) until it synthesises: they live as long as the plan
+    rows_sp, rows_ap = _rows(sp), _rows(ap)
+
+    def at(rows, i):
+        return C.cast(C.c_void_p(C.cast(rows, C.c_void_p).value + i * C.sizeof(_dp)), C.POINTER(_dp))
+
+    s = WorldSynthesizer()
+    L.InitializeSynthesizer(fs, fp, fft, bs, P, C.byref(s))
+    calls, out, pulses, counts, rings = [], [], [], [], []
+
+    def record(op, ret):
+        r = s.randn_state
+        calls.append([op, ret] + [getattr(s, k) for k in REALTIME_SCALARS] +
+                     [r.g_randn_x, r.g_randn_y, r.g_randn_z, r.g_randn_w])
+
+    def drain():
+        while True:
+            r = L.Synthesis2(C.byref(s))
+            record(RT_SYNTH, r)
+            if r == 0:
+                break
+            out.append(np.ctypeslib.as_array(s.buffer, shape=(bs,)).copy())
+        locked = L.IsLocked(C.byref(s))
+        record(RT_LOCKED, locked)
+        return locked
+
+    i = k = adds = 0
+    refused = 0
+    try:
+        while k < len(chunks):
+            if k == refresh_before and refused == 0:
+                L.RefreshSynthesizer(C.byref(s))
+                record(RT_REFRESH, 0)
+                refresh_before = -1
+            n = chunks[k]
+            r = L.AddParameters(f0[i:].ctypes.data_as(_dp), n, at(rows_sp, i), at(rows_ap, i), C.byref(s))
+            record(RT_ADD, r)
+            if r == 1:
+                slot = (s.head_pointer - 1) % P
+                npu = s.number_of_pulses[slot]
+                counts.append(npu)
+                if npu:
+                    pulses.extend(s.pulse_locations_index[slot][:npu])
+                i += n; k += 1; adds += 1; refused = 0
+                w = min(adds, P)             # (slots never written hold whatever the reference's new[] left there)
+                rings.append([[s.f0_length[j] if j < w else 0 for j in range(P)],
+                              [s.f0_origin[j] if j < w else 0 for j in range(P)],
+                              [s.number_of_pulses[j] for j in range(P)]])
+                if adds % drain_every != 0 and k < len(chunks):
+                    continue
+            else:
+                refused += 1
+                if refused > 1:
+                    break                    # refused again after draining: the ring cannot move
+            if drain() and stop_on_lock:
+                break
+    finally:
+        L.DestroySynthesizer(C.byref(s))
+    return {"calls": np.array(calls, dtype=np.float64).reshape(-1, 2 + len(REALTIME_SCALARS) + 4),
+            "out": np.concatenate(out) if out else np.zeros(0), "pulses": np.array(pulses, dtype=np.int64),
+            "pulse_counts": np.array(counts, dtype=np.int64), "rings": np.array(rings, dtype=np.int64).reshape(-1, 3, P)}
 
 
 def _hip_runtime_first():
@@ -134,6 +274,17 @@ def load_library(path=LIB_PATH):
     lib.world_hip_decode_aperiodicity.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.GetNumberOfAperiodicities.argtypes = [C.c_int]
     lib.GetFFTSizeForCheapTrick.argtypes = [C.c_int, C.POINTER(CheapTrickOption)]
+    if hasattr(lib, "world_hip_realtime_create"):                    # (added under ABI 6: looked up by name)
+        lib.world_hip_realtime_create.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(vp)]
+        lib.world_hip_realtime_destroy.argtypes = [vp]
+        lib.world_hip_realtime_destroy.restype = None
+        lib.world_hip_realtime_add.argtypes = [vp, C.c_int, _dp, C.c_int, vp, vp, C.c_int]
+        lib.world_hip_realtime_synthesize.argtypes = [vp, vp, _ip]
+        lib.world_hip_realtime_is_locked.argtypes = [vp, C.c_int]
+        lib.world_hip_realtime_refresh.argtypes = [vp, C.c_int]
+        lib.world_hip_realtime_rng_jump.argtypes = [C.POINTER(C.c_uint32), C.c_ulonglong, C.POINTER(C.c_uint32)]
+        lib.world_hip_realtime_rng_jump.restype = None
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -261,6 +412,41 @@ class HostAPI:
         y = np.zeros(y_length)
         self.lib.Synthesis(_p(f0), len(f0), _rows(sp), _rows(ap), fft_size, frame_period, fs, y_length, _p(y))
         return y
+
+    # -- real-time synthesis (reference synthesisrealtime.h) --
+    def _rt(self):
+        if not getattr(self, "_rt_bound", False):
+            bind_realtime(self.lib)
+            self._rt_bound = True
+        return self.lib
+
+    def initialize_synthesizer(self, fs, frame_period, fft_size, buffer_size, number_of_pointers):
+        s = WorldSynthesizer()
+        self._rt().InitializeSynthesizer(fs, frame_period, fft_size, buffer_size, number_of_pointers, C.byref(s))
+        return s
+
+    def add_parameters(self, synth, f0, sp, ap):
+        """AddParameters of one chunk; the row pointers only live for the call (this library copies the rows then)"""
+        f0, sp, ap = _f64(f0), _f64(sp), _f64(ap)
+        return self._rt().AddParameters(_p(f0), len(f0), _rows(sp), _rows(ap), C.byref(synth))
+
+    def synthesis2(self, synth):
+        """(return value, copy of buffer[0, buffer_size))"""
+        r = self._rt().Synthesis2(C.byref(synth))
+        return r, np.ctypeslib.as_array(synth.buffer, shape=(synth.buffer_size,)).copy()
+
+    def is_locked(self, synth):
+        return self._rt().IsLocked(C.byref(synth))
+
+    def refresh_synthesizer(self, synth):
+        self._rt().RefreshSynthesizer(C.byref(synth))
+
+    def destroy_synthesizer(self, synth):
+        self._rt().DestroySynthesizer(C.byref(synth))
+
+    def realtime_plan(self, plan):
+        """run_realtime_plan() on this library"""
+        return run_realtime_plan(self._rt(), plan)
 
     # -- codec (reference codec.h) --
     def number_of_aperiodicities(self, fs):
@@ -405,6 +591,7 @@ class WorldHip:
         self.lib = load_library(lib_path)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self._ctxs = {}                  # stream handle -> library context
+        self._realtime = weakref.WeakSet()   # open RealtimeStreams: they use a context, so close() closes them first
 
     def _context(self):
         """One library context (workspace + stream binding) per torch stream in use, created lazily and kept:
@@ -426,6 +613,8 @@ class WorldHip:
         return self._ctxs.get(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def close(self):
+        for rt in list(getattr(self, "_realtime", ())):
+            rt.close()
         for ctx in self._ctxs.values():
             self.lib.world_hip_destroy(ctx)
         self._ctxs = {}
@@ -709,6 +898,14 @@ class WorldHip:
                                                       ap.data_ptr()), "unpack_results")
         return tpos, f0, sp, ap
 
+    def realtime(self, n_streams, fs, frame_period, fft_size, buffer_size, number_of_pointers):
+        """n_streams real-time synthesisers (reference synthesisrealtime.cpp) on this GPU: see RealtimeStreams"""
+        if not hasattr(self.lib, "world_hip_realtime_create"):
+            raise RuntimeError("this libworld_hip.so has no real-time synthesis (world_hip_realtime_create)")
+        rt = RealtimeStreams(self, n_streams, fs, frame_period, fft_size, buffer_size, number_of_pointers)
+        self._realtime.add(rt)
+        return rt
+
     def synthesis_pulses_dropped(self):
         """pulses per utterance the last synthesis calls had no room for (0 = all rendered); synchronises"""
         need = C.c_int(0)
@@ -873,3 +1070,63 @@ def analyze_sharded_c(lib, ctxs, xs, fs, block_ptrs, rows_capacity, sub_batch=32
     if rc != 0:
         raise RuntimeError("analyze_sharded: " + lib.world_hip_last_error().decode())
     return where[:n]
+
+
+class RealtimeStreams:
+    """world_hip_realtime_*: n_streams independent streams, each behaving as one reference WorldSynthesizer.
+
+    add(stream, f0, sp, ap): one chunk; f0 host (numpy / list), sp / ap [frames, fft/2+1] float64 CUDA tensors (copied into
+    the stream's frame store on the current stream); returns 1, or 0 when the stream's ring is full.
+    synthesize(): (out [n_streams, buffer_size] CUDA tensor, produced [n_streams] numpy bool) -- Synthesis2 of every stream.
+    is_locked(stream), refresh(stream), close()."""
+
+    def __init__(self, wh, n_streams, fs, frame_period, fft_size, buffer_size, number_of_pointers):
+        self.wh, self.lib, self.torch = wh, wh.lib, wh.torch
+        self.n_streams, self.buffer_size, self.bins = int(n_streams), int(buffer_size), int(fft_size) // 2 + 1
+        self.ctx = wh._context()
+        h = C.c_void_p()
+        wh._check(self.lib.world_hip_realtime_create(self.ctx, self.n_streams, int(fs), float(frame_period), int(fft_size),
+                                                     self.buffer_size, int(number_of_pointers), C.byref(h)),
+                  "world_hip_realtime_create")
+        self.h = h
+
+    def _ok(self, r, what):
+        if r < 0:
+            raise RuntimeError(f"{what}: {self.lib.world_hip_last_error().decode()}")
+        return r
+
+    def add(self, stream, f0, sp, ap):
+        t = self.torch
+        f0 = _f64(f0)
+        for a in (sp, ap):
+            assert a.dtype == t.float64 and a.is_cuda and a.dim() == 2 and a.shape[1] >= self.bins and a.stride(1) == 1
+        assert sp.shape[0] >= len(f0) and ap.shape[0] >= len(f0) and sp.stride(0) == ap.stride(0)
+        return self._ok(self.lib.world_hip_realtime_add(self.h, int(stream), _p(f0), len(f0), C.c_void_p(sp.data_ptr()),
+                                                        C.c_void_p(ap.data_ptr()), sp.stride(0)), "world_hip_realtime_add")
+
+    def synthesize(self):
+        t = self.torch
+        out = t.empty((self.n_streams, self.buffer_size), dtype=t.float64, device=self.wh.device)
+        produced = np.zeros(self.n_streams, dtype=np.int32)
+        self._ok(self.lib.world_hip_realtime_synthesize(self.h, C.c_void_p(out.data_ptr()), produced.ctypes.data_as(_ip)),
+                 "world_hip_realtime_synthesize")
+        return out, produced.astype(bool)
+
+    def is_locked(self, stream):
+        return bool(self._ok(self.lib.world_hip_realtime_is_locked(self.h, int(stream)), "world_hip_realtime_is_locked"))
+
+    def refresh(self, stream):
+        self._ok(self.lib.world_hip_realtime_refresh(self.h, int(stream)), "world_hip_realtime_refresh")
+
+    def close(self):
+        """(WorldHip.close() calls this first: the object uses one of its contexts)"""
+        if self.h:
+            self.lib.world_hip_realtime_destroy(self.h)
+            self.h = None
+            self.wh._realtime.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

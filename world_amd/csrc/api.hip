@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstring>
 #include <cstdarg>
+#include <deque>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -1974,5 +1975,6 @@ int world_hip_decode_aperiodicity(WorldHipContext *c, int rows, int fs, int fft_
 
 }  // extern "C"
 
+#include "realtime.inc"
 #include "dropin.inc"
 #include "fileio.inc"

@@ -908,3 +908,5 @@ void Synthesis(const double *f0, int f0_length, const double *const *spectrogram
 }
 
 }  // extern "C"
+
+#include "realtime_dropin.inc"

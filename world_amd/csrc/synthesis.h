@@ -42,4 +42,45 @@ size_t synth_pulse_lds_bytes(int lg_fft);
 int synth_tile_samples();                        // samples one workgroup of the time-base kernels covers (the unit's own constant:
                                                  // callers size their per-tile arrays by asking, not by including it)
 
+// ---- Real-time synthesis (reference src/synthesisrealtime.cpp; the host scheduler is realtime.inc) ----
+// One entry per pulse, written by the host when it schedules the pulse: where its two frame rows lie in the stream's frame
+// store, how it interpolates between them, and its place in the stream's randn() sequence.
+struct RtPulseJob {
+  const double *sp0, *sp1, *ap0, *ap1;  // rows of frames floor(t / fp) and floor(t / fp) + 1 (sp1 / ap1 unread when same)
+  double wgt;                           // t / fp - floor(t / fp)
+  double vuv;                           // the chunk's interpolated V/UV at the pulse (GetCurrentVUV, :230-241)
+  uint32_t rng[4];                      // xorshift state at the pulse's first draw (x, y, z, w)
+  int noise_size;                       // draws of the pulse, 1 .. fft_size
+  int same;                             // floor == ceil: the envelope is the front row alone
+  int loc;                              // pulse_locations_index
+  int first;                            // first output sample it may touch: the start of the buffer it is rendered into
+};
+// One stream's part of an overlap-add launch.  Samples [lo, hi): those below final_end are finished and go to out[n - lo],
+// the rest stay partial sums in tail_out[n - final_end]; tail_in[n - lo] holds the partial sums of [lo, tail_end).
+struct RtOlaStream {
+  int p0, np;                           // this stream's pulses in the launch's job list, in pulse order
+  int lo, hi, tail_end, final_end;
+  const double *tail_in;
+  double *tail_out, *out;
+};
+struct RtParams {
+  int fft_size, lg_fft;
+  int n_pulses;
+  const RtPulseJob *jobs;
+  double *resp;                         // [n_pulses][resp_stride]: response, spectrum scratch, noise words
+  int resp_stride;                      // rt_resp_stride(fft_size)
+  const double *dc_remover;             // [fft_size / 2] GetDCRemover(fft_size / 2) (synthesisrealtime.cpp:428-440)
+  const RtOlaStream *ola;
+  int n_streams;
+  Tables tab;
+};
+// doubles per pulse: fft_size response values (the 8192-point pulse keeps its spectrum there first: fft_size + 2), then
+// fft_size 32-bit noise words
+inline int rt_resp_stride(int fft_size) { return fft_size + 2 + fft_size / 2; }
+void launch_rt_pulse(const RtParams &p, hipStream_t stream);
+void launch_rt_overlap_add(const RtParams &p, int max_span, hipStream_t stream);
+// rows [0, n) of src (row_stride doubles apart, nb used) -> frame store rows (first + r) % cap of dst ([cap][nb])
+void launch_rt_store_rows(double *dst, int cap, int nb, long long first, const double *src, int row_stride, int n,
+                          hipStream_t stream);
+
 }  // namespace world_hip

@@ -228,50 +228,51 @@ __device__ __forceinline__ void minimum_phase(cplx *Z, cplx *C, const double *LG
   __syncthreads();
 }
 
-// NMAX: the largest fft_size of the instantiation (a thread's samples of the periodic response wait in registers).
+// One pulse's response, the body both pulse kernels share.  NMAX: the largest fft_size of the instantiation (a thread's
+// samples of the periodic response wait in registers).
 // 8192 points: the N-point complex transform of the minimum-phase step is 128 KB of LDS by itself, so the pulse's spectrum C
-// (N/2 + 1 complex) lives in global memory -- in the pulse's own slot of the response buffer, two doubles longer for it
-// (p.resp_stride); the response is written there last, when nobody reads C any more.
-template <int NMAX>
-__global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
-  DYN_LDS(lds);
-  const int u = blockIdx.y, pi = blockIdx.x;
-  const int np = p.np[u];
-  if (pi >= np) return;
+// (N/2 + 1 complex) lives in global memory -- in the pulse's own slot of the response buffer, two doubles longer for it;
+// the response is written there last, when nobody reads C any more.
+// RT = false, Synthesis() (synthesis.cpp:38-218): fractional delay by `delay_coef`, RemoveDCComponent that REPLACES the
+//   first half by -dc * dc_remover[i] (a table of fft_size), no safeguard in the aperiodic logarithm.
+// RT = true, Synthesis2 (synthesisrealtime.cpp:47-79,141-182,271-275): no delay, the in-place RemoveDCComponent (first
+//   half zero, the second minus dc * dc_remover[i - N/2], a table of fft_size / 2), the safeguard in both logarithms.
+struct PulseIn {
+  const double *sp0, *sp1, *ap0, *ap1;   // envelope rows of the frames floor / ceil of the pulse time
+  double wgt;                            // interpolation weight between them
+  bool same;                             // floor == ceil: the first rows alone
+  double vuv;
+  int noise_size;
+  const uint32_t *noise;                 // the pulse's randn() words: randn_value(noise[k]) is its k-th draw
+  double delay_coef;                     // RT = false: 2 pi (fractional shift) fs / N
+};
+template <int NMAX, bool RT>
+__device__ __forceinline__ void pulse_response(char *lds, double *slot, int lgn, const double2 *tw_table,
+                                               const double *dc_remover, const PulseIn &in) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int lgn = p.lg_fft, N = 1 << lgn, H = N / 2, nb = H + 1;
+  const int N = 1 << lgn, H = N / 2, nb = H + 1;
   constexpr bool c_global = NMAX > 4096;
   cplx *Z = reinterpret_cast<cplx *>(lds);
-  double *const slot = p.resp + ((size_t)u * p.pulse_cap + pi) * p.resp_stride;
   cplx *C = c_global ? reinterpret_cast<cplx *>(slot) : Z + N + 8;
   double *LG = reinterpret_cast<double *>(C);
   double *scratch = c_global ? reinterpret_cast<double *>(Z + N + 8) : reinterpret_cast<double *>(C + nb + 1);
   // table of the half-size transforms; the N-point complex transform derives its odd twiddles
-  const TwLds tw = stage_twiddles(scratch + 64, lgn - 1, p.tab.tw);
-
-  const int *pidx = p.pidx + (size_t)u * p.pulse_cap;
-  const int idx = pidx[pi];
-  const int nxt = pi + 1 < np - 1 ? pi + 1 : np - 1;
-  const int noise_size = pidx[nxt] - idx;                              // synthesis.cpp:369-370
-  const double vuv = (p.flags[(size_t)u * p.y_stride + idx] & 1) ? 1.0 : 0.0;
-  const double t = idx / static_cast<double>(p.fs);                    // pulse_locations = time_axis[i]
-  const int nf = p.n_frames[u];
-  // GetSpectralEnvelope / GetAperiodicRatio (:140-180)
-  const double fp = p.frame_period;
-  const int ff = imin(nf - 1, static_cast<int>(floor(t / fp))), fc = imin(nf - 1, static_cast<int>(ceil(t / fp)));
-  const double wgt = t / fp - ff;
-  const double *sp0 = p.sp + ((size_t)u * p.f_stride + ff) * nb, *sp1 = p.sp + ((size_t)u * p.f_stride + fc) * nb;
-  const double *ap0 = p.ap + ((size_t)u * p.f_stride + ff) * nb, *ap1 = p.ap + ((size_t)u * p.f_stride + fc) * nb;
+  const TwLds tw = stage_twiddles(scratch + 64, lgn - 1, tw_table);
+  const int noise_size = in.noise_size;
+  const double vuv = in.vuv, wgt = in.wgt;
+  const bool same = in.same;
+  const double *sp0 = in.sp0, *sp1 = in.sp1, *ap0 = in.ap0, *ap1 = in.ap1;
+  // GetSpectralEnvelope / GetAperiodicRatio (synthesis.cpp:140-180, synthesisrealtime.cpp:184-228)
   auto envelope = [&](int i) {
-    return ff == fc ? fabs(sp0[i]) : (1.0 - wgt) * fabs(sp0[i]) + wgt * fabs(sp1[i]);
+    return same ? fabs(sp0[i]) : (1.0 - wgt) * fabs(sp0[i]) + wgt * fabs(sp1[i]);
   };
   auto safe = [](double x) { return fmax(0.001, fmin(0.999999999999, x)); };   // common.h:111-113
   auto ratio = [&](int i) {
-    const double a = ff == fc ? safe(ap0[i]) : (1.0 - wgt) * safe(ap0[i]) + wgt * safe(ap1[i]);
+    const double a = same ? safe(ap0[i]) : (1.0 - wgt) * safe(ap0[i]) + wgt * safe(ap1[i]);
     return a * a;                                                          // pow(.., 2.0)
   };
 
-  // ---- periodic response (GetPeriodicResponse, :103-135); this thread's samples stay in registers
+  // ---- periodic response (GetPeriodicResponse); this thread's samples stay in registers
   constexpr int kPer = NMAX / kSyThreads;            // fft_size <= NMAX
   double per[kPer];
 #pragma unroll
@@ -281,35 +282,44 @@ __global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
     __syncthreads();
     for (int i = tid; i < nb; i += nt) LG[i] = log(envelope(i) * (1.0 - ratio(i)) + kTiny) / 2.0;
     minimum_phase(Z, C, LG, lgn, tw);
-    // fractional delay by a linear phase (GetSpectrumWithFractionalTimeShift, :86-98; the
-    // reference takes sin = sqrt(1 - cos^2), i.e. |sin|)
-    const double coef = 2.0 * kPi * p.pshift[(size_t)u * p.pulse_cap + pi] * p.fs / N;
-    for (int i = tid; i < nb; i += nt) {
-      const cplx m = C[i];
-      const double re2 = cos(coef * i), im2 = sqrt(1.0 - re2 * re2);
-      cplx s; s.re = m.re * re2 + m.im * im2; s.im = m.im * re2 - m.re * im2;
-      C[i] = s;
+    if (!RT) {
+      // fractional delay by a linear phase (GetSpectrumWithFractionalTimeShift, synthesis.cpp:86-98; the
+      // reference takes sin = sqrt(1 - cos^2), i.e. |sin|)
+      const double coef = in.delay_coef;
+      for (int i = tid; i < nb; i += nt) {
+        const cplx m = C[i];
+        const double re2 = cos(coef * i), im2 = sqrt(1.0 - re2 * re2);
+        cplx s; s.re = m.re * re2 + m.im * im2; s.im = m.im * re2 - m.re * im2;
+        C[i] = s;
+      }
     }
     block_irfft<3>(Z, lgn, tw, [&](int k) { return C[k]; });
     __syncthreads();
-    // fftshift + RemoveDCComponent in place (:72-80): the first half is REPLACED by -dc * remover
+    // fftshift + RemoveDCComponent; dc = the sum of the shifted second half
     double dc = 0.0;
     for (int n = tid; n < H; n += nt) dc += rfft_in(Z, n);               // shifted index n + H
     dc = block_sum(dc, scratch);
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
       const int i = tid + q * nt;
-      if (i < N) per[q] = i < H ? -dc * p.dc_remover[i] : rfft_in(Z, i - H) - dc * p.dc_remover[i];
+      if (RT) {
+        if (i >= H && i < N) per[q] = rfft_in(Z, i - H) - dc * dc_remover[i - H];
+      } else {
+        if (i < N) per[q] = i < H ? -dc * dc_remover[i] : rfft_in(Z, i - H) - dc * dc_remover[i];
+      }
     }
   }
 
-  // ---- aperiodic response (GetAperiodicResponse, :38-66)
+  // ---- aperiodic response (GetAperiodicResponse)
   __syncthreads();
-  for (int i = tid; i < nb; i += nt) LG[i] = vuv != 0.0 ? log(envelope(i) * ratio(i)) / 2.0 : log(envelope(i)) / 2.0;
-  minimum_phase(Z, C, LG, lgn, tw);
-  // GetNoiseSpectrum (:19-33): this pulse's draws, mean removed, zero padded; its spectrum is
-  // multiplied into the minimum-phase spectrum as the merge step emits it
-  const uint32_t *noise = p.noise + (idx - pidx[0]);
+  for (int i = tid; i < nb; i += nt) {
+    if (RT) LG[i] = vuv != 0.0 ? log(envelope(i) * ratio(i) + kTiny) / 2.0 : log(envelope(i)) / 2.0;
+    else LG[i] = vuv != 0.0 ? log(envelope(i) * ratio(i)) / 2.0 : log(envelope(i)) / 2.0;
+  }
+  minimum_phase(Z, C, LG, lgn, tw);                 // (ends with a barrier)
+  // GetNoiseSpectrum: the pulse's draws, mean removed, zero padded; its spectrum is multiplied into the minimum-phase
+  // spectrum as the merge step emits it
+  const uint32_t *noise = in.noise;
   double avg = 0.0;
   for (int i = tid; i < noise_size; i += nt) avg += randn_value(noise[i]);
   avg = block_sum(avg, scratch) / noise_size;
@@ -328,7 +338,7 @@ __global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
     });
   block_irfft<3>(Z, lgn, tw, [&](int k) { return C[k]; });
   __syncthreads();
-  // GetOneFrameSegment (:213-218): (periodic sqrt(noise_size) + fftshift(aperiodic)) / fft_size
+  // GetOneFrameSegment: (periodic sqrt(noise_size) + fftshift(aperiodic)) / fft_size
   const double sq = sqrt(static_cast<double>(noise_size));
   double *out = slot;                                 // (8192 points: over C, which the transform above has consumed)
 #pragma unroll
@@ -336,6 +346,34 @@ __global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
     const int i = tid + q * nt;
     if (i < N) out[i] = (per[q] * sq + rfft_in(Z, (i + H) & (N - 1))) / N;
   }
+}
+
+// One pulse of Synthesis() per workgroup.
+template <int NMAX>
+__global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
+  DYN_LDS(lds);
+  const int u = blockIdx.y, pi = blockIdx.x;
+  const int np = p.np[u];
+  if (pi >= np) return;
+  const int lgn = p.lg_fft, N = 1 << lgn, nb = N / 2 + 1;
+  double *const slot = p.resp + ((size_t)u * p.pulse_cap + pi) * p.resp_stride;
+  const int *pidx = p.pidx + (size_t)u * p.pulse_cap;
+  const int idx = pidx[pi];
+  const int nxt = pi + 1 < np - 1 ? pi + 1 : np - 1;
+  PulseIn in;
+  in.noise_size = pidx[nxt] - idx;                                     // synthesis.cpp:369-370
+  in.vuv = (p.flags[(size_t)u * p.y_stride + idx] & 1) ? 1.0 : 0.0;
+  const double t = idx / static_cast<double>(p.fs);                    // pulse_locations = time_axis[i]
+  const int nf = p.n_frames[u];
+  const double fp = p.frame_period;
+  const int ff = imin(nf - 1, static_cast<int>(floor(t / fp))), fc = imin(nf - 1, static_cast<int>(ceil(t / fp)));
+  in.wgt = t / fp - ff;
+  in.same = ff == fc;
+  in.sp0 = p.sp + ((size_t)u * p.f_stride + ff) * nb; in.sp1 = p.sp + ((size_t)u * p.f_stride + fc) * nb;
+  in.ap0 = p.ap + ((size_t)u * p.f_stride + ff) * nb; in.ap1 = p.ap + ((size_t)u * p.f_stride + fc) * nb;
+  in.noise = p.noise + (idx - pidx[0]);
+  in.delay_coef = 2.0 * kPi * p.pshift[(size_t)u * p.pulse_cap + pi] * p.fs / N;
+  pulse_response<NMAX, false>(lds, slot, lgn, p.tab.tw, p.dc_remover, in);
 }
 
 // ---------------------------------------------------------------------------
@@ -366,6 +404,88 @@ void launch_synthesis(const SynthParams &p, int max_y, hipStream_t stream) {
   if (p.lg_fft <= 12) devrt::launch_blocks("sy_pulse", sy_pulse<4096>, dim3(p.pulse_cap, p.n_utt), kSyThreads, synth_pulse_lds_bytes(p.lg_fft), stream, p);
   else devrt::launch_blocks("sy_pulse", sy_pulse<8192>, dim3(p.pulse_cap, p.n_utt), kSyThreads, synth_pulse_lds_bytes(p.lg_fft), stream, p);
   WH_THREADS(sy_overlap_add, max_y, p.n_utt, 1, stream, p);
+}
+
+// ---------------------------------------------------------------------------
+// Real-time synthesis (reference src/synthesisrealtime.cpp).  The host (realtime.inc) schedules the pulses and hands
+// each one over as an RtPulseJob; rt_pulse renders one pulse per workgroup, rt_overlap_add sums the responses of a
+// stream's pulses into its output in pulse order.  The pulse is sy_pulse's body with the real-time arithmetic
+// (pulse_response<.., true>); its noise words come from the stream's own generator state and wait behind the response
+// in the pulse's slot.
+template <int NMAX>
+__global__ void __launch_bounds__(kSyThreads) rt_pulse(RtParams p) {
+  DYN_LDS(lds);
+  const int pi = blockIdx.x;
+  if (pi >= p.n_pulses) return;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int lgn = p.lg_fft, N = 1 << lgn;
+  double *const slot = p.resp + (size_t)pi * p.resp_stride;
+  uint32_t *const words = reinterpret_cast<uint32_t *>(slot + N + 2);
+  const RtPulseJob &job = p.jobs[pi];
+  // GetNoiseSpectrum's draws (:30-34): lane t produces draws [t run, (t + 1) run) after one jump-ahead from the pulse's
+  // state (visible to the whole workgroup after the body's first minimum-phase step, which ends with a barrier)
+  {
+    const int run = (job.noise_size + nt - 1) / nt, a = tid * run;
+    if (a < job.noise_size) {
+      Xs128 st;
+      st.x = job.rng[0]; st.y = job.rng[1]; st.z = job.rng[2]; st.w = job.rng[3];
+      st = xs_jump(p.tab.jump, st, (uint32_t)a);
+      const int e = imin(job.noise_size, a + run);
+      for (int k = a; k < e; ++k) words[k] = xs_randn_word(st);
+    }
+  }
+  PulseIn in;
+  in.sp0 = job.sp0; in.sp1 = job.sp1; in.ap0 = job.ap0; in.ap1 = job.ap1;
+  in.wgt = job.wgt;
+  in.same = job.same != 0;
+  in.vuv = job.vuv;
+  in.noise_size = job.noise_size;
+  in.noise = words;
+  in.delay_coef = 0.0;
+  pulse_response<NMAX, true>(lds, slot, lgn, p.tab.tw, p.dc_remover, in);
+}
+
+// Synthesis2's overlap-add (:586-599), for all of a launch's pulses at once: every sample starts from the partial sum the
+// stream's earlier launches left and adds this launch's responses that cover it in pulse order -- the reference's
+// rounding.  A response never reaches before the start of the buffer it was rendered into (`first`).
+__global__ void rt_overlap_add(RtParams p) {
+  const RtOlaStream o = p.ola[blockIdx.y];
+  const int n = o.lo + flat_thread_x();
+  if (n >= o.hi) return;
+  const int N = p.fft_size, H = N / 2;
+  const RtPulseJob *jobs = p.jobs + o.p0;
+  double acc = n < o.tail_end ? o.tail_in[n - o.lo] : 0.0;
+  int lo = 0, hi = o.np;                           // first pulse whose response reaches n: loc + H >= n
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (jobs[mid].loc < n - H) lo = mid + 1; else hi = mid; }
+  for (int q = lo; q < o.np; ++q) {
+    const int offset = jobs[q].loc - H + 1;
+    if (offset > n) break;
+    if (n >= jobs[q].first) acc += p.resp[(size_t)(o.p0 + q) * p.resp_stride + (n - offset)];
+  }
+  if (n < o.final_end) o.out[n - o.lo] = acc;
+  else o.tail_out[n - o.final_end] = acc;
+}
+
+__global__ void rt_store_rows(double *dst, int cap, int nb, long long first, const double *src, int row_stride, int n) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (long long)n * nb) return;
+  const int r = (int)(k / nb), i = (int)(k % nb);
+  dst[(size_t)((first + r) % cap) * nb + i] = src[(size_t)r * row_stride + i];
+}
+
+void launch_rt_pulse(const RtParams &p, hipStream_t stream) {
+  if (p.n_pulses <= 0) return;
+  if (p.lg_fft <= 12) devrt::launch_blocks("rt_pulse", rt_pulse<4096>, dim3(p.n_pulses), kSyThreads, synth_pulse_lds_bytes(p.lg_fft), stream, p);
+  else devrt::launch_blocks("rt_pulse", rt_pulse<8192>, dim3(p.n_pulses), kSyThreads, synth_pulse_lds_bytes(p.lg_fft), stream, p);
+}
+void launch_rt_overlap_add(const RtParams &p, int max_span, hipStream_t stream) {
+  if (p.n_streams <= 0 || max_span <= 0) return;
+  WH_THREADS(rt_overlap_add, max_span, p.n_streams, 1, stream, p);
+}
+void launch_rt_store_rows(double *dst, int cap, int nb, long long first, const double *src, int row_stride, int n,
+                          hipStream_t stream) {
+  if (n <= 0) return;
+  WH_THREADS(rt_store_rows, (long)n * nb, 1, 1, stream, dst, cap, nb, first, src, row_stride, n);
 }
 
 }  // namespace world_hip
