@@ -303,7 +303,8 @@ WORLD_HIP_API const char *world_hip_last_error(void);
  * header changes incompatibly; a binding built against another major value must refuse to bind (world_amd/api.py does).
  *   5  round 5: world_hip_spectral_packed_range / _cheaptrick_batch_range / _d4c_batch_range take `reuse_offsets`
  *   6  round 6: + world_hip_abi_version itself; no prototype changed.  Later additions keep 6: they add entry points and
- *      change no prototype (the world_hip_realtime_* calls); bindings look for them by name.
+ *      change no prototype (the world_hip_realtime_* calls, world_hip_modify_batch and its kin); bindings look for them
+ *      by name.
  * Libraries older than 6 lack the symbol. */
 #define WORLD_HIP_ABI_VERSION 6
 /* Launch-geometry hints of a context (bits; default 0).  Results never depend on them.
@@ -545,6 +546,58 @@ WORLD_HIP_API int world_hip_code_aperiodicity(WorldHipContext *ctx, int rows, in
                                               const double *d_aperiodicity, double *d_coded);
 WORLD_HIP_API int world_hip_decode_aperiodicity(WorldHipContext *ctx, int rows, int fs, int fft_size,
                                                 const double *d_coded, double *d_aperiodicity);
+
+/* Parameter modification between analysis and synthesis (reference test/test.cpp:221-258, ParameterModification), per
+ * utterance, on the dense arrays of the *_batch calls (f0 [n_utt][f_stride], spectrogram [n_utt][f_stride][fft_size/2+1]):
+ *   f0_scale        test.cpp's argv[3]: f0 *= f0_scale (the same multiply, bit for bit); 1 = unchanged; finite, >= 0
+ *   formant_shift   test.cpp's argv[4]: every spectrogram row is stretched along frequency -- log, interp1 from the axis
+ *                   ratio * i / fft_size * fs onto i / fft_size * fs, exp -- and, for ratio < 1, bins from
+ *                   int(fft_size / 2.0 * ratio) up take the value of the bin below; 1 = the row untouched, bit for bit;
+ *                   finite, > 0, fft_size / 2 * ratio >= 1
+ *   convert_log_f0  1: before the scaling, voiced frames (finite and > 0) become
+ *                   exp(log_f0_mean + (ln f0 - mu_s) * (sigma_s > 0 ? log_f0_std / sigma_s : 0)), where mu_s / sigma_s are the
+ *                   mean and population standard deviation of ln f0 over the utterance's voiced frames (natural log);
+ *                   log_f0_mean finite, log_f0_std finite and >= 0.  0 (off) ignores both.
+ * Unvoiced frames (0) stay 0; NaN / Inf frames pass through the conversion unchanged.  Only the spectral envelope is warped:
+ * the aperiodicity is left as it is. */
+typedef struct {
+  double f0_scale;
+  double formant_shift;
+  int convert_log_f0;
+  double log_f0_mean, log_f0_std;
+} WorldHipModification;
+/* Per-utterance log-F0 statistics: d_stats [n_utt][3] (device) = {voiced frames, mu_s, sigma_s} as defined above; an
+ * utterance without a voiced frame gets {0, 0, 0}.  The summation order is fixed per utterance: values never depend on the
+ * rest of the batch. */
+WORLD_HIP_API int world_hip_f0_statistics(WorldHipContext *ctx, int n_utt, const int *n_frames, int f_stride,
+                                          const double *d_f0, double *d_stats);
+/* The modification of each utterance u by mods[u] (HOST array of n_utt; NULL = identity for all), for the frames below
+ * n_frames[u] (HOST); frames and rows beyond are neither read nor written.  Works after either F0 route (Harvest, or DIO +
+ * StoneMask).  f0 (d_f0_in, d_f0_out) and the spectrogram (d_sp_in, d_sp_out) are independent: pass both pointers of a
+ * pair or neither (NULL: that part is not touched).  In place (in == out) and out of place give the same bits.  fs and
+ * fft_size describe the rows (fft_size a power of two, 128..8192; ignored without a spectrogram).  Every parameter is
+ * checked before any GPU work: a refused call (non-zero, world_hip_last_error) has touched no output.  The rows returned
+ * feed world_hip_synthesis_batch and world_hip_realtime_add as they are. */
+WORLD_HIP_API int world_hip_modify_batch(WorldHipContext *ctx, int n_utt, int fs, int fft_size, const int *n_frames,
+                                         int f_stride, const WorldHipModification *mods, const double *d_f0_in,
+                                         double *d_f0_out, const double *d_sp_in, double *d_sp_out);
+/* Output samples of a resynthesis (test.cpp: int((n_frames - 1) * frame_period / 1000 * fs) + 1, the frame period scaled
+ * by time_scale).  Pure host arithmetic; 0 for invalid arguments. */
+WORLD_HIP_API int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale);
+/* Harvest -> CheapTrick + D4C -> world_hip_modify_batch(mods) -> Synthesis of one batch in ONE call: the reference's
+ * test.cpp chain (analysis, ParameterModification, Synthesis) without the parameters ever leaving the device.  Synthesis
+ * runs at frame_period * time_scale (harvest_option->frame_period; time_scale finite, > 0: 2 = twice as long, the standard
+ * WORLD speed change).  x, x_length as world_hip_analyze_batch; y [n_utt][y_stride] (device), y_length [n_utt] (HOST; see
+ * world_hip_resynthesis_length).  Every utterance needs at least 2 frames.  Bit for bit what analyze_batch, modify_batch and
+ * synthesis_batch produce in sequence on the same context.  The analysis lives in the context's workspace
+ * (world_hip_workspace_bytes counts it; a capture of the call goes stale like any other when the workspace grows).  The
+ * pulse capacity is that of world_hip_synthesis_batch: a raised F0 raises the pulse count, world_hip_sync /
+ * world_hip_synthesis_pulses_dropped report a shortfall.  Invalid parameters are refused before any GPU work. */
+WORLD_HIP_API int world_hip_resynthesize_batch(WorldHipContext *ctx, int n_utt, int fs, const double *d_x, int x_stride,
+                                               const int *x_length, const HarvestOption *harvest_option,
+                                               const CheapTrickOption *cheaptrick_option, const D4COption *d4c_option,
+                                               const WorldHipModification *mods, double time_scale, const int *y_length,
+                                               int y_stride, double *d_y);
 
 /* Real-time synthesis, batched (reference src/synthesisrealtime.cpp; the drop-in WorldSynthesizer above is built on it).
  * One object serves n_streams independent streams with one fs, frame_period (ms), fft_size, buffer_size and ring size

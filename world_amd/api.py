@@ -44,6 +44,27 @@ class D4COption(C.Structure):        # reference d4c.h:16-18
     _fields_ = [("threshold", C.c_double)]
 
 
+class WorldHipModification(C.Structure):   # include/world_hip.h (test.cpp's ParameterModification, per utterance)
+    _fields_ = [("f0_scale", C.c_double), ("formant_shift", C.c_double), ("convert_log_f0", C.c_int),
+                ("log_f0_mean", C.c_double), ("log_f0_std", C.c_double)]
+
+
+def modifications(n_utt, f0_scale=1.0, formant_shift=1.0, log_f0_target=None):
+    """WorldHipModification[n_utt] from scalars or per-utterance sequences; log_f0_target = (means, stds) or None"""
+    scale = np.broadcast_to(np.asarray(f0_scale, dtype=np.float64), (n_utt,))
+    ratio = np.broadcast_to(np.asarray(formant_shift, dtype=np.float64), (n_utt,))
+    mods = (WorldHipModification * n_utt)()
+    if log_f0_target is not None:
+        mean = np.broadcast_to(np.asarray(log_f0_target[0], dtype=np.float64), (n_utt,))
+        std = np.broadcast_to(np.asarray(log_f0_target[1], dtype=np.float64), (n_utt,))
+    for u in range(n_utt):
+        m = mods[u]
+        m.f0_scale, m.formant_shift = float(scale[u]), float(ratio[u])
+        if log_f0_target is not None:
+            m.convert_log_f0, m.log_f0_mean, m.log_f0_std = 1, float(mean[u]), float(std[u])
+    return mods
+
+
 # -- the real-time synthesiser (reference synthesisrealtime.h; include/world_hip.h declares the same layout) --
 class RandnState(C.Structure):       # reference matlabfunctions.h
     _fields_ = [("g_randn_x", C.c_uint32), ("g_randn_y", C.c_uint32), ("g_randn_z", C.c_uint32), ("g_randn_w", C.c_uint32)]
@@ -285,6 +306,14 @@ def load_library(path=LIB_PATH):
         lib.world_hip_realtime_refresh.argtypes = [vp, C.c_int]
         lib.world_hip_realtime_rng_jump.argtypes = [C.POINTER(C.c_uint32), C.c_ulonglong, C.POINTER(C.c_uint32)]
         lib.world_hip_realtime_rng_jump.restype = None
+    if hasattr(lib, "world_hip_modify_batch"):                       # (added under ABI 6: looked up by name)
+        mp = C.POINTER(WorldHipModification)
+        lib.world_hip_f0_statistics.argtypes = [vp, C.c_int, _ip, C.c_int, vp, vp]
+        lib.world_hip_modify_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, mp, vp, vp, vp, vp]
+        lib.world_hip_resynthesis_length.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
+        lib.world_hip_resynthesize_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
+                                                     C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, C.c_double,
+                                                     _ip, C.c_int, vp]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -762,6 +791,103 @@ class WorldHip:
                 finally:
                     self.set_synthesis_pulse_capacity(0)
         return y
+
+    # ---- parameter modification (include/world_hip.h: world_hip_modify_batch; reference test.cpp ParameterModification) ----
+    def _modify_lib(self):
+        if not hasattr(self.lib, "world_hip_modify_batch"):
+            raise RuntimeError("this libworld_hip.so has no parameter modification (world_hip_modify_batch)")
+        return self.lib
+
+    def f0_statistics(self, f0, n_frames):
+        """f0 [B, F] float64 (device) -> [B, 3] {voiced frames, mean ln f0, std ln f0} over each utterance's voiced frames"""
+        t = self.torch
+        L = self._modify_lib()
+        assert f0.dtype == t.float64 and f0.dim() == 2 and f0.is_contiguous() and f0.device == self.device
+        B, F = f0.shape
+        nf = np.ascontiguousarray(np.broadcast_to(n_frames, (B,)), dtype=np.int32)
+        stats = t.empty((B, 3), dtype=t.float64, device=f0.device)
+        self._check(L.world_hip_f0_statistics(self._context(), B, nf.ctypes.data_as(_ip), F, f0.data_ptr(), stats.data_ptr()),
+                    "f0_statistics")
+        return stats
+
+    def modify(self, f0, sp, n_frames, fs, fft_size, f0_scale=1.0, formant_shift=1.0, log_f0_target=None, out=None):
+        """test.cpp's ParameterModification on a batch: f0 [B, F] and / or sp [B, F, fft/2+1] (float64, device; either may
+        be None).  f0_scale, formant_shift: scalars or per-utterance sequences; log_f0_target: (means, stds) of the voiced
+        log F0 to map each utterance onto, or None.  out: None = new tensors, "inplace" = the inputs are overwritten, or a
+        (f0_out, sp_out) pair.  Returns (f0', sp')."""
+        t = self.torch
+        L = self._modify_lib()
+        ref = f0 if f0 is not None else sp
+        assert ref is not None, "modify: nothing to modify"
+        B, F = ref.shape[0], ref.shape[1]
+        for a, dims in ((f0, 2), (sp, 3)):
+            if a is not None:
+                assert a.dtype == t.float64 and a.dim() == dims and a.is_contiguous() and a.device == self.device
+                assert a.shape[:2] == (B, F)
+        if sp is not None:
+            assert sp.shape[2] == fft_size // 2 + 1
+        if out == "inplace":
+            f0_out, sp_out = f0, sp
+        elif out is not None:
+            f0_out, sp_out = out
+        else:
+            f0_out = t.empty_like(f0) if f0 is not None else None
+            sp_out = t.empty_like(sp) if sp is not None else None
+            # (rows beyond an utterance's frames are not written: carry the padding over)
+            nf_min = int(np.min(n_frames))
+            if nf_min < F:
+                if f0_out is not None:
+                    f0_out.copy_(f0)
+                if sp_out is not None:
+                    sp_out.copy_(sp)
+        nf = np.ascontiguousarray(np.broadcast_to(n_frames, (B,)), dtype=np.int32)
+        mods = modifications(B, f0_scale, formant_shift, log_f0_target)
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        self._check(L.world_hip_modify_batch(self._context(), B, int(fs), int(fft_size), nf.ctypes.data_as(_ip), F, mods,
+                                             ptr(f0), ptr(f0_out), ptr(sp), ptr(sp_out)), "modify")
+        return f0_out, sp_out
+
+    def resynthesis_length(self, fs, n_frames, frame_period=5.0, time_scale=1.0):
+        return int(self._modify_lib().world_hip_resynthesis_length(int(fs), int(n_frames), float(frame_period),
+                                                                    float(time_scale)))
+
+    def resynthesize(self, x, fs, x_len=None, f0_scale=1.0, formant_shift=1.0, time_scale=1.0, log_f0_target=None,
+                     frame_period=5.0, f0_floor=71.0, f0_ceil=800.0, q1=-0.15, threshold=0.85, out=None):
+        """analyze -> modify -> synthesis in one library call (world_hip_resynthesize_batch): x [B, L] float64 (device) ->
+        (y [B, max(y_length)], y_length).  f0_floor / f0_ceil are Harvest's (CheapTrick keeps 71 Hz, as analyze());
+        synthesis runs at frame_period * time_scale.  Like synthesis(), a call whose pulses did not all fit is repeated
+        once at the capacity the device asked for -- never a truncated waveform.  out: a preallocated y of that shape."""
+        t = self.torch
+        L = self._modify_lib()
+        B, Lx, xl = self._prep(x, x_len)
+        fft_size = cheaptrick_fft_size(fs, 71.0)
+        yl = np.array([L.world_hip_resynthesis_length(int(fs), frame_count(fs, int(n), frame_period), float(frame_period),
+                                                      float(time_scale)) for n in xl], dtype=np.int32)
+        if int(yl.min()) < 1:
+            raise ValueError(f"resynthesize: invalid frame_period {frame_period} / time_scale {time_scale}")
+        Y = int(yl.max())
+        y = out if out is not None else t.zeros((B, Y), dtype=t.float64, device=x.device)
+        assert y.dtype == t.float64 and y.is_contiguous() and y.shape == (B, Y) and y.device == x.device
+        mods = modifications(B, f0_scale, formant_shift, log_f0_target)
+        hopt, copt, dopt = HarvestOption(f0_floor, f0_ceil, frame_period), CheapTrickOption(q1, 71.0, fft_size), D4COption(threshold)
+
+        def run():
+            self._check(L.world_hip_resynthesize_batch(self._context(), B, int(fs), x.data_ptr(), Lx, xl.ctypes.data_as(_ip),
+                                                       C.byref(hopt), C.byref(copt), C.byref(dopt), mods, float(time_scale),
+                                                       yl.ctypes.data_as(_ip), Y, y.data_ptr()), "resynthesize")
+        run()
+        need = self.synthesis_pulses_dropped()          # (synchronises) -- as synthesis(): one repeat at the asked capacity
+        if need:
+            if need > Y:
+                raise RuntimeError(f"resynthesize: {need} pitch pulses for {Y} output samples")
+            self.set_synthesis_pulse_capacity(need + 16)
+            try:
+                run()
+                if self.synthesis_pulses_dropped():
+                    raise RuntimeError("resynthesize: pulses dropped even at the requested capacity")
+            finally:
+                self.set_synthesis_pulse_capacity(0)
+        return y, yl
 
     # ---- the per-frame FFT in isolation (include/world_hip.h: world_hip_probe_rfft) ----
     def probe_rfft(self, x, max_lr=3, threads=0, out=None, static_plan=False):

@@ -53,7 +53,10 @@ static thread_local std::string g_last_error;
 struct Arena {
   char *base = nullptr;
   size_t cap = 0, used = 0;
-  void reset() { used = 0; }
+  // bytes at the bottom that outlive the stages of one call (world_hip_resynthesize_batch keeps its analysis there): the
+  // stages carve above them.  0 outside such a call.
+  size_t floor = 0;
+  void reset() { used = floor; }
   template <class T> T *take(size_t count) {
     size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
     if (used + bytes > cap) fail("workspace arena overflow (%zu + %zu > %zu)", used, bytes, cap);
@@ -188,8 +191,16 @@ struct WorldHipContext {
 
 namespace world_hip {
 
+// Thrown by ensure_arena while a floor is held: the arena cannot move under the arrays kept there, so the call that holds
+// the floor grows it to `bytes` (floor included) with the floor released and starts over.  Invariant: a floor is set only
+// inside run_resynthesis's attempt loop, which catches this.  It is not a std::exception, so that no stage's own error
+// handling can swallow it; should it ever escape a call, guarded() turns it into an internal error instead of letting it
+// cross the C boundary.
+struct ArenaRegrow { size_t bytes; };
+
 static void ensure_arena(WorldHipContext *c, size_t bytes) {
-  if (bytes <= c->arena.cap) return;
+  if (c->arena.floor + bytes <= c->arena.cap) return;
+  if (c->arena.floor) throw ArenaRegrow{c->arena.floor + bytes};
   devrt::sync(c->stream);
   if (c->arena.base) { devrt::dfree(c->arena.base); ++c->generation; }
   size_t cap = bytes + bytes / 8 + (1u << 20);
@@ -1340,6 +1351,145 @@ static std::string shape_limit(int what, int fs, int fft_size) {
 }
 
 // ---------------------------------------------------------------------------
+// Parameter modification between analysis and synthesis (reference test/test.cpp:221-258, ParameterModification) and the
+// whole analyse -> modify -> synthesise chain in one call (include/world_hip.h: world_hip_modify_batch,
+// world_hip_resynthesize_batch).  The kernels are codec.hip's modify_warp_sp and modify_f0.
+// ---------------------------------------------------------------------------
+// every value of every utterance's modification checked before any GPU work; fft_size = 0: the rows are not modified (the
+// fill bound does not apply)
+static void check_modifications(const WorldHipModification *mods, int n_utt, int fft_size) {
+  if (!mods) return;
+  for (int u = 0; u < n_utt; ++u) {
+    const WorldHipModification &m = mods[u];
+    if (!std::isfinite(m.f0_scale) || m.f0_scale < 0.0) fail("modification %d: f0_scale %g must be finite and >= 0", u, m.f0_scale);
+    if (!std::isfinite(m.formant_shift) || !(m.formant_shift > 0.0))
+      fail("modification %d: formant_shift %g must be finite and > 0", u, m.formant_shift);
+    if (fft_size > 0 && !(fft_size / 2.0 * m.formant_shift >= 1.0))
+      fail("modification %d: formant_shift %g leaves no bin below fft_size/2 * ratio to fill from (fft_size %d)", u,
+           m.formant_shift, fft_size);
+    if (m.convert_log_f0 != 0 && m.convert_log_f0 != 1) fail("modification %d: convert_log_f0 must be 0 or 1", u);
+    if (m.convert_log_f0 && !std::isfinite(m.log_f0_mean)) fail("modification %d: log_f0_mean %g is not finite", u, m.log_f0_mean);
+    if (m.convert_log_f0 && (!std::isfinite(m.log_f0_std) || m.log_f0_std < 0.0))
+      fail("modification %d: log_f0_std %g must be finite and >= 0", u, m.log_f0_std);
+  }
+}
+
+// f0 and sp independently optional (both pointers of a pair, or neither); in == out allowed for each
+static void run_modify(WorldHipContext *c, int n_utt, int fs, int fft_size, const int *n_frames, int f_stride,
+                       const WorldHipModification *mods, const double *d_f0_in, double *d_f0_out, const double *d_sp_in,
+                       double *d_sp_out) {
+  if (n_utt <= 0) fail("n_utt must be positive");
+  if (!n_frames) fail("null n_frames");
+  if (!d_f0_in != !d_f0_out) fail("modify: give both d_f0_in and d_f0_out, or neither");
+  if (!d_sp_in != !d_sp_out) fail("modify: give both d_sp_in and d_sp_out, or neither");
+  const bool with_sp = d_sp_in != nullptr;
+  if (with_sp) {
+    if (fs <= 0) fail("fs must be positive");
+    const int lg = ilog2_exact(fft_size);
+    if (lg < 7 || lg > 13) fail("modify: fft_size %d unsupported (128..8192)", fft_size);
+  }
+  check_modifications(mods, n_utt, with_sp ? fft_size : 0);
+  const int max_frames = max_frame_count(n_frames, n_utt, f_stride);
+  std::vector<double> ratio(n_utt, 1.0), scale(n_utt, 1.0), target(2 * (size_t)n_utt, 0.0);
+  std::vector<int> convert(n_utt, 0);
+  bool warp = with_sp && d_sp_in != d_sp_out, map = d_f0_in && d_f0_in != d_f0_out;   // out-of-place always writes
+  for (int u = 0; mods && u < n_utt; ++u) {
+    ratio[u] = mods[u].formant_shift; scale[u] = mods[u].f0_scale; convert[u] = mods[u].convert_log_f0;
+    target[2 * u] = mods[u].log_f0_mean; target[2 * u + 1] = mods[u].log_f0_std;
+    warp |= with_sp && ratio[u] != 1.0;
+    map |= d_f0_in && (scale[u] != 1.0 || convert[u] != 0);
+  }
+  if (max_frames == 0 || (!warp && !map)) return;
+  open_uploads(c);                                          // (the stage uses no workspace: prepared offsets stay valid)
+  ModifyParams p;
+  p.n_utt = n_utt; p.f_stride = f_stride; p.fs = fs; p.fft_size = fft_size;
+  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.ratio = upload(c, ratio); p.sp_in = d_sp_in; p.sp_out = d_sp_out;
+  p.f0_scale = upload(c, scale); p.convert = upload(c, convert); p.target = upload(c, target);
+  p.f0_in = d_f0_in; p.f0_out = d_f0_out; p.stats = nullptr;
+  if (warp) launch_modify_warp_sp(p, max_frames, c->stream);
+  if (map) launch_modify_f0(p, c->stream);
+}
+
+static void run_f0_statistics(WorldHipContext *c, int n_utt, const int *n_frames, int f_stride, const double *d_f0,
+                              double *d_stats) {
+  if (n_utt <= 0) fail("n_utt must be positive");
+  if (!n_frames || !d_f0 || !d_stats) fail("null buffer");
+  max_frame_count(n_frames, n_utt, f_stride);
+  open_uploads(c);
+  ModifyParams p;
+  p.n_utt = n_utt; p.f_stride = f_stride; p.fs = 0; p.fft_size = 0;
+  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.ratio = nullptr; p.sp_in = nullptr; p.sp_out = nullptr;
+  p.convert = upload(c, std::vector<int>(n_utt, 0));
+  p.f0_scale = nullptr; p.target = nullptr;
+  p.f0_in = d_f0; p.f0_out = nullptr; p.stats = d_stats;
+  launch_modify_f0(p, c->stream);
+}
+
+static int resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {   // test.cpp:302-303
+  return static_cast<int>((n_frames - 1) * frame_period * time_scale / 1000.0 * fs) + 1;
+}
+
+// Harvest -> CheapTrick + D4C -> modification -> Synthesis at frame_period * time_scale.  tpos, f0, sp and ap are carved at
+// the bottom of the arena and held there (Arena::floor) while the stages carve above them.  A stage that needs a larger
+// arena than the one held cannot grow it under those arrays: the call grows it with the floor released and starts over
+// (the first call of a shape only; the stages then fit).
+static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
+                            const HarvestOption *hopt, const CheapTrickOption *copt, const D4COption *dopt,
+                            const WorldHipModification *mods, double time_scale, const int *y_length, int y_stride,
+                            double *d_y) {
+  check_batch(n_utt, fs, d_x, x_stride, x_length);
+  if (!hopt || !copt || !dopt) fail("null option");
+  if (!(hopt->f0_floor > 0) || !(hopt->f0_ceil > hopt->f0_floor) || !(hopt->frame_period > 0) ||
+      !std::isfinite(hopt->frame_period) || !std::isfinite(hopt->f0_ceil))
+    fail("bad HarvestOption");
+  if (!std::isfinite(time_scale) || !(time_scale > 0.0)) fail("resynthesize: time_scale %g must be finite and > 0", time_scale);
+  if (!y_length || !d_y) fail("null buffer");
+  const int fft_size = copt->fft_size;
+  const std::string lim = shape_limit(6, fs, fft_size);
+  if (!lim.empty()) fail("%s", lim.c_str());
+  check_modifications(mods, n_utt, fft_size);
+  std::vector<int> nf(n_utt);
+  int f_stride = 1;
+  for (int u = 0; u < n_utt; ++u) {
+    nf[u] = frame_count(fs, x_length[u], hopt->frame_period);
+    if (nf[u] < 2) fail("resynthesize: utterance %d has %d frame(s); synthesis needs 2", u, nf[u]);
+    if (y_length[u] < 1 || y_length[u] > y_stride) fail("y_length[%d]=%d outside [1, y_stride]", u, y_length[u]);
+    f_stride = std::max(f_stride, nf[u]);
+  }
+  const size_t fr = (size_t)n_utt * f_stride, nb = fft_size / 2 + 1;
+  double *tpos = nullptr, *f0 = nullptr, *sp = nullptr, *ap = nullptr;
+  auto carve = [&](Arena &a) {
+    tpos = a.take<double>(fr); f0 = a.take<double>(fr);
+    sp = a.take<double>(fr * nb); ap = a.take<double>(fr * nb);
+  };
+  struct Release {                                          // the floor never outlives the call, whatever happens in it
+    WorldHipContext *c;
+    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
+  } release{c};
+  size_t want = 0;
+  for (int attempt = 0;; ++attempt) {
+    c->arena.floor = 0;
+    ensure_arena(c, std::max(measure(carve), want));
+    arena_reset(c);
+    carve(c->arena);
+    c->arena.floor = c->arena.used;
+    try {
+      run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
+      run_modify(c, n_utt, fs, fft_size, nf.data(), f_stride, mods, f0, f0, sp, sp);
+      run_synthesis(c, n_utt, fs, hopt->frame_period * time_scale, fft_size, nf.data(), f_stride, f0, sp, ap, y_length,
+                    y_stride, d_y);
+      return;
+    } catch (const ArenaRegrow &r) {
+      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
+      if (attempt >= 4) fail("resynthesize: the workspace did not settle");
+      want = std::max(want, r.bytes);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
 // A context's allocations and launches belong to ITS device: a thread that drives several GPUs calls in
@@ -1365,6 +1515,10 @@ template <class F> static int guarded(WorldHipContext *c, F f) {
     return 0;
   } catch (const std::exception &e) {
     g_last_error = e.what();
+    return 1;
+  } catch (const ArenaRegrow &) {
+    c->arena.floor = 0;
+    g_last_error = "internal error: the workspace had to grow under arrays held by the call";
     return 1;
   }
 }
@@ -1953,6 +2107,35 @@ int world_hip_pcm16_to_double(WorldHipContext *c, long long n, const short *d_pc
     if (n < 0) fail("negative sample count");
     if (n > 0 && (!d_pcm || !d_x)) fail("null buffer");
     if (n > 0) launch_pcm16_to_double(d_pcm, d_x, (long)n, c->stream);
+  });
+}
+
+int world_hip_f0_statistics(WorldHipContext *c, int n_utt, const int *n_frames, int f_stride, const double *d_f0,
+                            double *d_stats) {
+  return guarded(c, [&] { run_f0_statistics(c, n_utt, n_frames, f_stride, d_f0, d_stats); });
+}
+int world_hip_modify_batch(WorldHipContext *c, int n_utt, int fs, int fft_size, const int *n_frames, int f_stride,
+                           const WorldHipModification *mods, const double *d_f0_in, double *d_f0_out, const double *d_sp_in,
+                           double *d_sp_out) {
+  return guarded(c, [&] {
+    run_modify(c, n_utt, fs, fft_size, n_frames, f_stride, mods, d_f0_in, d_f0_out, d_sp_in, d_sp_out);
+  });
+}
+int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
+  if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||
+      !(time_scale > 0))
+    return 0;
+  const double y = (n_frames - 1) * frame_period * time_scale / 1000.0 * fs;
+  if (!(y < 2147483646.0)) return 0;
+  return resynthesis_length(fs, n_frames, frame_period, time_scale);
+}
+int world_hip_resynthesize_batch(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
+                                 const HarvestOption *harvest_option, const CheapTrickOption *cheaptrick_option,
+                                 const D4COption *d4c_option, const WorldHipModification *mods, double time_scale,
+                                 const int *y_length, int y_stride, double *d_y) {
+  return guarded(c, [&] {
+    run_resynthesis(c, n_utt, fs, d_x, x_stride, x_length, harvest_option, cheaptrick_option, d4c_option, mods, time_scale,
+                    y_length, y_stride, d_y);
   });
 }
 

@@ -28,4 +28,29 @@ void launch_decode_spectral_envelope(const CodecParams &p, hipStream_t stream);
 void launch_code_aperiodicity(const CodecParams &p, hipStream_t stream);
 void launch_decode_aperiodicity(const CodecParams &p, hipStream_t stream);
 
+// Parameter modification between analysis and synthesis (the reference's test/test.cpp: ParameterModification): F0
+// scaling with an optional log-F0 statistics conversion, and the spectral envelope stretched along frequency.  Every
+// per-utterance value is a device array of the context's small-array slabs ([n_utt] unless noted).
+struct ModifyParams {
+  int n_utt, f_stride;
+  int fs, fft_size;              // warp: the rows have fft_size/2+1 bins
+  const int *n_frames;           // frames of each utterance; rows / frames beyond are never read or written
+  // spectral warp (modify_warp_sp): sp_in may equal sp_out
+  const double *ratio;           // formant shift; 1 = the row is left as it is (copied when out-of-place)
+  const double *sp_in;
+  double *sp_out;
+  // F0 map (modify_f0): f0_in may equal f0_out; f0_out == nullptr = statistics only
+  const double *f0_scale;
+  const int *convert;            // 1 = voiced log-F0 mapped onto target[2u] (mean), target[2u + 1] (std)
+  const double *target;          // [n_utt][2]
+  const double *f0_in;
+  double *f0_out;
+  double *stats;                 // [n_utt][3] {voiced frames, mean log F0, std log F0}, or nullptr
+};
+
+// LDS of one warp workgroup: the row's log and the knots, 2 (fft_size/2+1) doubles (65.6 KB at fft_size 8192)
+size_t modify_warp_lds_bytes(int fft_size);
+void launch_modify_warp_sp(const ModifyParams &p, int max_frames, hipStream_t stream);
+void launch_modify_f0(const ModifyParams &p, hipStream_t stream);
+
 }  // namespace world_hip

@@ -11,6 +11,12 @@
 // Both interp1 calls have fixed knots and fixed queries, so their bin search and weights
 // are tables built once on the host (api.hip: codec_tables).  One 256-thread workgroup
 // per frame for the envelope kernels, one thread per output value for the band kernels.
+//
+// Beside them, the parameter modification of the reference's test/test.cpp (ParameterModification, :221-258):
+//   modify_warp_sp : log row -> interp1 from the axis ratio*i/fft*fs onto i/fft*fs -> exp, bins from
+//                    int(fft/2*ratio) up filled with the bin below when ratio < 1   (one workgroup per row)
+//   modify_f0      : optional log-F0 statistics conversion, then f0 *= scale     (one workgroup per utterance)
+// The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
 #include "codec.h"
 #include "fft.h"
 
@@ -115,6 +121,117 @@ __global__ void codec_decode_ap(CodecParams p) {
     v = pow(10.0, (lo + p.frac[j] * (hi - lo)) / 20.0);
   }
   p.out[(size_t)row * (p.out_stride ? p.out_stride : (size_t)nb) + j] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Spectral warp.  interp1(x, log row, nb, xi, nb) with x[i] = ratio*i/fft*fs and xi[j] = j/fft*fs (matlabfunctions.cpp:
+// 157-176): histc gives the query j the largest k in [1, nb-1] with x[k-1] <= xi[j] (queries at or beyond x[nb-1] get
+// nb-1 and are extrapolated from the last interval).  The knots are evaluated once per workgroup, exactly as the reference
+// evaluates them, into LDS beside the log row; x[c] <= xi is about c <= j/ratio, and the guess floor(j/ratio) is corrected
+// against those knots, so k and the weights are the reference's bit for bit.  Per output bin: two FP64 divisions (xi and
+// the interpolation weight), one exp; per input bin: one log, one division for its knot.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) modify_warp_sp(ModifyParams p) {
+  DYN_LDS(lds);
+  const int f = blockIdx.x, u = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (f >= p.n_frames[u]) return;
+  const int nb = p.fft_size / 2 + 1;
+  const size_t row = ((size_t)u * p.f_stride + f) * nb;
+  const double *in = p.sp_in + row;
+  double *out = p.sp_out + row;
+  const double ratio = p.ratio[u];
+  if (ratio == 1.0) {                                 // test.cpp without argv[4]: the row as it is
+    if (out != in)
+      for (int j = tid; j < nb; j += nt) out[j] = in[j];
+    return;
+  }
+  double *lg = reinterpret_cast<double *>(lds);       // log row, nb doubles
+  double *kx = lg + nb;                               // knots, nb doubles
+  for (int j = tid; j < nb; j += nt) {
+    lg[j] = log(in[j]);
+    kx[j] = ratio * j / p.fft_size * p.fs;            // test.cpp:237, in this order
+  }
+  __syncthreads();                                    // (in place: every read of the row is done before the first write)
+  // ratio < 1: bins m .. nb-1 take bin m-1's warped value (test.cpp:250-254)
+  const int m = ratio < 1.0 ? static_cast<int>(p.fft_size / 2.0 * ratio) : nb;
+  const double inv_ratio = 1.0 / ratio;               // (the guess only: the knots decide)
+  for (int j = tid; j < nb; j += nt) {
+    const int q = j < m ? j : m - 1;
+    const double xi = static_cast<double>(q) / p.fft_size * p.fs;
+    const double g = q * inv_ratio;
+    int c = g >= nb - 1 ? nb - 1 : static_cast<int>(g);   // the last knot <= xi: a guess ...
+    while (c < nb - 1 && kx[c + 1] <= xi) ++c;
+    while (c > 0 && kx[c] > xi) --c;                      // ... corrected (x[0] = 0 <= xi always)
+    const int k = c + 1 < nb - 1 ? c + 1 : nb - 1;
+    const double s = (xi - kx[k - 1]) / (kx[k] - kx[k - 1]);
+    out[j] = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// F0 map, one workgroup per utterance.  Voiced = finite and > 0.  Statistics (when converting or asked for): mean of
+// ln f0 over the voiced frames (corrected once by the mean of the residuals), then the population standard deviation
+// about it -- the passes re-read the utterance's F0, a few KB from L2; each thread sums a fixed
+// stride of frames and the workgroup reduction has a fixed shape, so the values depend on the utterance alone.
+// Zero voiced frames give {0, 0, 0}.  Then voiced frames (converted) and every other frame are multiplied by the scale:
+// the reference's own multiply (test.cpp:225-227).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool voiced_f0(double v) { return v > 0.0 && __builtin_isfinite(v); }
+
+__global__ void __launch_bounds__(256) modify_f0(ModifyParams p) {
+  DYN_LDS(lds);
+  double *scratch = reinterpret_cast<double *>(lds);  // 96 doubles: three disjoint areas of the block reductions
+  const int u = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int n = p.n_frames[u];
+  const double *in = p.f0_in + (size_t)u * p.f_stride;
+  const bool convert = p.convert[u] != 0;
+  double mu = 0.0, sigma = 0.0;
+  if (convert || p.stats) {
+    double sum = 0.0, count = 0.0;
+    for (int i = tid; i < n; i += nt) {
+      const double v = in[i];
+      if (voiced_f0(v)) { sum += log(v); count += 1.0; }
+    }
+    block_sum2(sum, count, scratch);
+    if (count > 0.0) {
+      mu = sum / count;
+      // one correction of the mean by its residuals: a constant track then has mu exactly its ln f0, hence sigma_s = 0
+      double res = 0.0;
+      for (int i = tid; i < n; i += nt) {
+        const double v = in[i];
+        if (voiced_f0(v)) res += log(v) - mu;
+      }
+      mu += block_sum(res, scratch + 64) / count;
+      double ss = 0.0;
+      for (int i = tid; i < n; i += nt) {
+        const double v = in[i];
+        if (voiced_f0(v)) { const double d = log(v) - mu; ss += d * d; }
+      }
+      ss = block_sum(ss, scratch + 80);
+      sigma = sqrt(ss / count);
+    }
+    if (p.stats && tid == 0) {
+      p.stats[3 * u] = count; p.stats[3 * u + 1] = mu; p.stats[3 * u + 2] = sigma;
+    }
+  }
+  if (!p.f0_out) return;
+  double *out = p.f0_out + (size_t)u * p.f_stride;
+  const double scale = p.f0_scale[u];
+  const double mu_t = p.target[2 * u], gain = convert && sigma > 0.0 ? p.target[2 * u + 1] / sigma : 0.0;
+  for (int i = tid; i < n; i += nt) {
+    double v = in[i];
+    if (convert && voiced_f0(v)) v = exp(mu_t + (log(v) - mu) * gain);
+    out[i] = v * scale;
+  }
+}
+
+size_t modify_warp_lds_bytes(int fft_size) { return 2 * sizeof(double) * (fft_size / 2 + 1); }
+
+void launch_modify_warp_sp(const ModifyParams &p, int max_frames, hipStream_t stream) {
+  WH_BLOCKS(modify_warp_sp, dim3(max_frames, p.n_utt), 256, modify_warp_lds_bytes(p.fft_size), stream, p);
+}
+void launch_modify_f0(const ModifyParams &p, hipStream_t stream) {
+  WH_BLOCKS(modify_f0, dim3(p.n_utt), 256, sizeof(double) * 128, stream, p);
 }
 
 void launch_code_spectral_envelope(const CodecParams &p, hipStream_t stream) {

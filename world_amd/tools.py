@@ -6,11 +6,15 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
 
     python -m world_amd.tools analysis a.wav b.wav ... --outdir params      # -> params/a.f0 a.sp a.ap ...
     python -m world_amd.tools synthesis params/a.f0 params/a.sp params/a.ap -o a_resynth.wav
+    python -m world_amd.tools transform a.wav b.wav ... --outdir out --f0-scale 1.5 --formant-shift 1.2
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
 are uploaded (decoded on the device), and with --code-sp / --code-ap the envelopes are coded on
 the device before they come back, so the D2H traffic and the files shrink by 10-17x.
+`transform` is the reference test program's analysis -> ParameterModification -> Synthesis (F0 scale, formant shift,
+and a speed change through the synthesis frame period) in one library call per batch; the waveforms are quantised to
+16 bits on the device, so only int16 samples come back.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -23,7 +27,6 @@ from .api import FileAPI, WorldHip, cheaptrick_fft_size
 
 
 def _analysis(a):
-    import torch
     wh, files = WorldHip(), FileAPI()
     os.makedirs(a.outdir, exist_ok=True)
     by_rate = {}
@@ -33,11 +36,7 @@ def _analysis(a):
     for fs, group in sorted(by_rate.items()):
         for at in range(0, len(group), a.batch):
             chunk = group[at:at + a.batch]
-            waves = [wh.wavread(path)[0] for path in chunk]           # PCM bytes up, FP64 made on the device
-            x = torch.zeros((len(chunk), max(w.numel() for w in waves)), dtype=torch.float64, device=wh.device)
-            for row, w in enumerate(waves):
-                x[row, :w.numel()] = w
-            x_len = np.array([w.numel() for w in waves], dtype=np.int32)
+            x, x_len = _load_batch(wh, chunk)
             tpos, f0, sp, ap, nf = wh.analyze(x, fs, x_len=x_len, f0_method=a.f0, frame_period=a.s, f0_floor=a.f,
                                               f0_ceil=a.c, q1=a.q, threshold=a.t)
             fft_size = cheaptrick_fft_size(fs, 71.0)
@@ -80,6 +79,69 @@ def _synthesis(a):
     print(f"{n} frames -> {a.o} ({y_length} samples at {fs} Hz)")
 
 
+def _load_batch(wh, chunk):
+    """WAV files of one sampling rate -> (x [B, L] on the device, x_len): PCM bytes up, FP64 made on the device"""
+    import torch
+    waves = [wh.wavread(path)[0] for path in chunk]
+    x = torch.zeros((len(chunk), max(w.numel() for w in waves)), dtype=torch.float64, device=wh.device)
+    for row, w in enumerate(waves):
+        x[row, :w.numel()] = w
+    return x, np.array([w.numel() for w in waves], dtype=np.int32)
+
+
+def _same_file(a, b):
+    if os.path.realpath(a) == os.path.realpath(b):
+        return True
+    try:
+        return os.path.samefile(a, b)                       # (hard links)
+    except OSError:
+        return False
+
+
+def transform_outputs(wavs, outdir):
+    """The file `transform` writes for each input: outdir/<the input's name>.  Refused, before anything is read or
+    written, when an output would be one of the inputs or two inputs would share an output."""
+    outs = [os.path.join(outdir, os.path.basename(path)) for path in wavs]
+    seen = {}
+    for path, out in zip(wavs, outs):
+        key = os.path.realpath(out)
+        if key in seen:
+            raise ValueError(f"{path} and {seen[key]} would both be written to {out}")
+        seen[key] = path
+        for src in wavs:
+            if _same_file(out, src):
+                raise ValueError(f"{out} is an input file: choose an --outdir that holds none of the inputs")
+    return outs
+
+
+def _transform(a):
+    try:
+        outs = transform_outputs(a.wav, a.outdir)
+    except ValueError as e:
+        sys.exit(f"transform: {e}")
+    wh = WorldHip()
+    os.makedirs(a.outdir, exist_ok=True)
+    out_of = dict(zip(a.wav, outs))
+    by_rate = {}
+    for path in a.wav:
+        by_rate.setdefault(wh.wav_layout(path)[0], []).append(path)
+    samples = 0
+    for fs, group in sorted(by_rate.items()):
+        for at in range(0, len(group), a.batch):
+            chunk = group[at:at + a.batch]
+            x, x_len = _load_batch(wh, chunk)
+            y, y_len = wh.resynthesize(x, fs, x_len=x_len, f0_scale=a.f0_scale, formant_shift=a.formant_shift,
+                                       time_scale=a.time_scale, frame_period=a.s, f0_floor=a.f, f0_ceil=a.c)
+            q = wh.double_to_pcm16(y).cpu().numpy()              # quantised on the device: int16 crosses PCIe
+            for row, path in enumerate(chunk):
+                n, name = int(y_len[row]), out_of[path]
+                pcm = np.ascontiguousarray(q[row, :n])
+                if wh.lib.world_hip_wav_write_pcm16(os.fsencode(name), fs, n, pcm.ctypes.data) != 1:
+                    sys.exit(f"transform: {name} cannot be written")
+                samples += n
+    print(f"{len(a.wav)} file(s), {samples} samples -> {a.outdir}")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m world_amd.tools", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="tool", required=True)
@@ -103,6 +165,17 @@ def main(argv=None):
     sy.add_argument("ap")
     sy.add_argument("-o", default="output.wav")
     sy.set_defaults(run=_synthesis)
+    tr = sub.add_parser("transform", help="WAV files -> analysed, modified and resynthesised WAV files")
+    tr.add_argument("wav", nargs="+")
+    tr.add_argument("--outdir", required=True, help="written under the input files' names; must hold none of the inputs")
+    tr.add_argument("--f0-scale", type=float, default=1.0, help="F0 multiplier (test.cpp's third argument)")
+    tr.add_argument("--formant-shift", type=float, default=1.0, help="spectral envelope stretch (test.cpp's fourth argument)")
+    tr.add_argument("--time-scale", type=float, default=1.0, help="duration multiplier (synthesis frame period * T)")
+    tr.add_argument("-f", type=float, default=71.0, help="floor of the F0 range (Hz)")
+    tr.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
+    tr.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
+    tr.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
+    tr.set_defaults(run=_transform)
     a = p.parse_args(argv)
     a.run(a)
 
