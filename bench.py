@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- analysis frames/sec of the MI355X WORLD analysis path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints the result line.  --full adds everything else described below (the run's checks of
+itself, the CPU baselines, the other BASELINE configs, the per-kernel and roofline figures, the side legs and the machine
+probes), each of which takes runs of its own.
 
 N = 1 (the default, what the driver's BENCH run executes)
     `value` = BASELINE.json configs[1]: one 48 kHz x 10 s utterance per step (2001 frames), Harvest + CheapTrick +
@@ -11,10 +16,10 @@ N = 1 (the default, what the driver's BENCH run executes)
     --dump-outputs DIR writes the last timed step's results (tpos, f0, sp, ap, nf) to DIR/<name>.npy as float64
     (a fixed, seeded sample of the spectral rows past 64 MB); the inputs depend on the arguments alone, so two builds
     run with the same arguments can be compared output for output.
-    After the timed region the run checks itself (`parity_in_run`): every in-flight slot's
+    With --full, after the timed region the run checks itself (`parity_in_run`): every in-flight slot's
     (f0, sp, ap) must be bit-identical to a serial single-context run, and that run must agree with the CPU
     reference computed for `cpu_baseline` to the contract's 1e-4 -- otherwise the process exits non-zero.
-    Beside `value` the line carries `value_single_job` (1 / latency of a lone job) and a `configs` object with one
+    Beside `value` the --full line carries `value_single_job` (1 / latency of a lone job) and a `configs` object with one
     timed leg per remaining single-GPU BASELINE config: configs[2] (256 x 5 s, Harvest only), the per-GPU share of
     configs[3] (128 x 5 s, full pipeline) and configs[4] (64 x 16 kHz x 5 s, DIO + StoneMask + CheapTrick + D4C),
     each run for >= --min-wall seconds with its dominant kernel and HBM / FP64 roofline fractions.
@@ -23,9 +28,10 @@ N > 1 (the driver's SCALE run; one rank per GPU over RCCL)
     BASELINE.json configs[3]: ONE job of 1024 x (48 kHz, 5 s) utterances per step, split 1024/N per rank by
     world_amd.distributed.analyze_sharded (longest-first partition, batched analysis in sub-batches, one packed
     [frames][2 + 2*1025] block per rank, ONE all-gather).  Total work is fixed: "scaling": "strong".  Compute and
-    exchange are timed separately on every rank (`phases`).
+    exchange are timed separately on every rank (`phases`).  With --full the run also checks utterances received from
+    other ranks against a lone analysis (`parity_in_run`) and times the all-gather alone, the roofline and the CPU baseline.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the kernel that dominates a configs[1] step (HIP-event timing on
+Rank 0 prints ONE JSON line.  (--full:) `roofline` describes the kernel that dominates a configs[1] step (HIP-event timing on
 the launch stream, taken in a separate profiled pass); `cpu_baseline*` are the unmodified reference timed on this
 box's host cores (1 core at -O1 = the reference's own flags, 1 core at -O3, and every core).
 """
@@ -395,16 +401,18 @@ def main():
                          "(default 0: exactly K timed steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="N = 1: write the last timed step's results of the headline leg to DIR/<name>.npy (float64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the configs[2] / [3]-share / [4] legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the run's checks of itself, CPU baselines, the other "
+                         "configs, per-kernel / roofline figures, side legs and machine probes (default: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="N = 1, with --full: skip the legs of the other BASELINE configs")
     ap.add_argument("--only-config", type=int, default=0,
                     help="N = 1: run ONLY the leg of this BASELINE config (2, 3 or 4) -- the profiling entry point")
     ap.add_argument("--contexts", type=int, default=2,
                     help="N = 1: batched jobs in flight in the configs[2] / [3] / [4] legs (1 = per-kernel durations free of queueing: profiles)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the result all-gather")
-    ap.add_argument("--no-extras", action="store_true", help="skip the codec / synthesis / host-pointer legs and the environment microprobe")
-    ap.add_argument("--inflight-only", action="store_true",
-                    help="N = 1: run the headline's timed region and stop (for a kernel trace of the in-flight mode alone)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the graph / codec / synthesis / host-pointer legs and the environment microprobe")
     ap.add_argument("--job-utterances", type=int, default=1024, help="N > 1: utterances of the configs[3] job")
     ap.add_argument("--sub-batch", type=int, default=32,
                     help="configs[3] job (N > 1, and the N = 1 anchor configs['3_full']): utterances per batched call = per all-gather")
@@ -449,12 +457,14 @@ def main():
         args.wire = "f64"                                       # no exchange to hide: the bit-identical records
     props = torch.cuda.get_device_properties(local)
     environment = {"device": props.name, "arch": getattr(props, "gcnArchName", None), "compute_units": props.multi_processor_count,
-                   "hbm_bytes": props.total_memory, "rocm_smi_at_start": smi_snapshot() if rank == 0 else None,
+                   "hbm_bytes": props.total_memory,
                    "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
                    "hsa_ipc": {"HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"),
                                "exported_by_the_box": HSA_IPC_EXPORTED is not None},
                    "launcher": "bench.py itself (torch.distributed.run)" if os.environ.get("WORLD_HIP_BENCH_SELF_SPAWNED") else
                                ("external" if "WORLD_SIZE" in os.environ else "none")}
+    if args.full:
+        environment["rocm_smi_at_start"] = smi_snapshot() if rank == 0 else None
 
     def environment_done(wh_probe=None):
         """the line's `environment` object: rocm-smi before and after the run, and the library's microprobe of the machine
@@ -637,7 +647,7 @@ def main():
         # the run checks itself: utterances analysed on OTHER ranks, as this rank received them, against a lone
         # analysis made here (bit-identical: batched == single, and the exchange must not touch a bit)
         parity = None
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             res, checked, same = last[0], [], True
             for i in sorted({(rank * 7 + 1) % n_job, n_job // 2, (n_job - 1 - rank) % n_job}):
                 tp1, f01, sp1, ap1, nf1 = wh.analyze(synth.utterance(i, FS, sec, device=dev).unsqueeze(0), FS)
@@ -655,10 +665,10 @@ def main():
         # The all-gather by itself: blocking in-place all-gathers of the job's largest sub-batch buffer, HIP events around
         # them -- the rate RCCL achieves on this node when nothing else runs, beside the rate the overlap NEEDS
         # (bytes a rank receives per step / the step's time) and the bytes of the one exchange the overlap cannot hide.
-        gather_gbs = None if args.no_gather else measure_gather(last[0].blocks)
+        gather_gbs = measure_gather(last[0].blocks) if args.full and not args.no_gather else None
         # roofline of the dominant kernel of ONE batched call of this rank's share (rank 0; HIP events per kernel)
         roofline = None
-        if rank == 0 and mine:
+        if args.full and rank == 0 and mine:
             idx = mine[:args.sub_batch]
             xb = torch.stack([xs[i] for i in idx]).contiguous()
             kernels = kernel_profile(wh, lambda: wh.analyze(xb, FS, frame_period=FRAME_PERIOD), 1)
@@ -673,15 +683,13 @@ def main():
                                        "uuid": str(getattr(props, "uuid", "")) or None})
         # the CPU baseline beside it (rank 0, one utterance of the job on one host core; the other ranks wait at the barrier)
         cpu = None
-        if rank == 0 and not args.no_cpu_baseline and mine:
+        if args.full and rank == 0 and not args.no_cpu_baseline and mine:
             cpu, _ = cpu_baseline(xs[mine[0]].cpu().numpy(), optimized=False)
         barrier()
         dist.destroy_process_group()
         if rank == 0:
-            env_n = environment_done(wh)
-            measured_peak(env_n, roofline)
             nb = FFT_SIZE // 2 + 1
-            print(json.dumps({
+            line = {
                 "metric": "analysis frames/sec (Harvest+CheapTrick+D4C, 48 kHz, 5 ms hop)",
                 "value": frames_per_step * nsteps / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
                 "repeats": repeats, "warmup": args.warmup, "ms_per_step": dt / nsteps * 1e3, "timed_wall_s": dt,
@@ -706,9 +714,12 @@ def main():
                            "wire": args.wire, "wire_choice": wire_choice,
                            "note": "chunk k's all-gather runs while chunk k+1 is analysed; exposed = device time the compute stream "
                                    "waited for all-gathers after its last analysis (HIP events), compute = the rest of the step"},
-                "parity_in_run": parity, "roofline": roofline, "cpu_baseline": cpu,
                 "rccl_ranks_seen": ranks_seen, "backend": os.environ.get("WORLD_HIP_BENCH_BACKEND", "nccl"), "ranks": names,
-                "environment": env_n}))
+                "environment": environment}
+            if args.full:
+                measured_peak(environment_done(wh), roofline)
+                line.update({"parity_in_run": parity, "roofline": roofline, "cpu_baseline": cpu})
+            print(json.dumps(line))
             if parity is not None and not (parity["every_rank_bit_identical_to_lone_analysis"] and parity["randn_table_intact"]):
                 sys.stderr.write("bench.py: parity_in_run failed: " + json.dumps(parity) + "\n")
                 sys.exit(1)
@@ -936,11 +947,20 @@ def main():
         tpos_l, f0_l, sp_l, ap_l, nf_l = last[(counter[0] - 1) % S]
         dump_outputs(args.dump_outputs, {"tpos": tpos_l, "f0": f0_l, "sp": sp_l, "ap": ap_l, "nf": nf_l})
 
-    if args.inflight_only:
-        torch.cuda.synchronize()
-        print(json.dumps({"metric": "analysis frames/sec (Harvest+CheapTrick+D4C, 48 kHz, 5 ms hop)", "value": value, "unit": "frames/s",
-                          "n_gpus": 1, "steps": args.steps, "repeats": repeats, "ms_per_step": dt / nsteps * 1e3,
-                          "note": "--inflight-only: the timed region alone, nothing checked"}))
+    line = {
+        "metric": "analysis frames/sec (Harvest+CheapTrick+D4C, 48 kHz, 5 ms hop)",
+        "value": value, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "repeats": repeats, "warmup": args.warmup,
+        "ms_per_step": dt / nsteps * 1e3, "timed_wall_s": dt, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"configs[1]: {B} x (48 kHz, {args.seconds:g} s) utterance(s) per step, "
+                               f"Harvest+CheapTrick+D4C, fft_size=2048, frame_period=5 ms, inputs/outputs in HBM, "
+                               f"{S} independent jobs in flight (one HIP stream + context each, a different utterance per job)",
+                   "frames_per_step": frames_per_step, "utterances_per_gpu": B, "jobs_in_flight": S,
+                   "parallelism": "single GPU, no collective"},
+        "environment": environment,
+    }
+    if not args.full:
+        print(json.dumps(line))
         return
 
     # ---- the run checks itself: every slot of the timed mode against a serial single-context run ---------
@@ -1189,16 +1209,7 @@ def main():
 
     env_1 = environment_done(WorldHip(device=local))
     measured_peak(env_1, roofline, *[(leg or {}).get("roofline") for leg in (configs or {}).values()])
-    out = {
-        "metric": "analysis frames/sec (Harvest+CheapTrick+D4C, 48 kHz, 5 ms hop)",
-        "value": value, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "repeats": repeats, "warmup": args.warmup,
-        "ms_per_step": dt / nsteps * 1e3, "timed_wall_s": dt, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"configs[1]: {B} x (48 kHz, {args.seconds:g} s) utterance(s) per step, "
-                               f"Harvest+CheapTrick+D4C, fft_size=2048, frame_period=5 ms, inputs/outputs in HBM, "
-                               f"{S} independent jobs in flight (one HIP stream + context each, a different utterance per job)",
-                   "frames_per_step": frames_per_step, "utterances_per_gpu": B, "jobs_in_flight": S,
-                   "parallelism": "single GPU, no collective"},
+    line.update({
         "value_single_job": frames_per_step / (lat * 1e-3), "single_job_latency_ms": lat,
         "parity_in_run": parity,
         "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_o3": cpu_o3,
@@ -1209,9 +1220,8 @@ def main():
         "first_call_ms": None if not host_to_host else host_to_host.get("cold_start", {}).get("first_call_ms"),
         "randn_table_first_build_ms": None if not host_to_host else host_to_host.get("cold_start", {}).get("randn_table_build_ms"),
         "workspace_bytes": workspace, "randn_table_bytes": table_bytes, "csrc_hash": csrc_hash(),
-        "environment": env_1,
-    }
-    print(json.dumps(out))
+    })
+    print(json.dumps(line))
     if not ok:
         sys.stderr.write("bench.py: parity_in_run failed: " + json.dumps(parity) + "\n")
         sys.exit(1)

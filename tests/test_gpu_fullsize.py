@@ -280,6 +280,23 @@ def test_voiced_section_longer_than_the_lds_is_smoothed_out_of_hbm(wh, ref):
     assert_f0_close(f0[0, :n].cpu().numpy(), f0_r, what="24 s tone f0")
 
 
+def test_plain_bench_run_times_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline's timed steps, the dumped outputs of the last one and the result
+    line -- none of the checks, legs and baselines that --full adds"""
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["unit"] == "frames/s" and line["config"]["frames_per_step"] == 2001
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 2001) < 1e-6
+    assert not {"parity_in_run", "cpu_baseline", "configs", "roofline", "kernels_ms_per_step"} & set(line)
+    assert np.load(tmp_path / "nf.npy").tolist() == [2001.0]
+    sp = np.load(tmp_path / "sp.npy")
+    assert sp.shape == (1, 2001, 1025) and np.all(np.isfinite(sp)) and np.all(sp > 0)
+
+
 def test_bench_multi_rank_path_on_one_gpu():
     """bench.py --gpus 2 end to end (the SCALE run's code path): two ranks share this box's one GPU, the all-gather
     goes through gloo with host staging (a functional check, never a number of record): partition, batched analysis
@@ -288,7 +305,7 @@ def test_bench_multi_rank_path_on_one_gpu():
     env = dict(os.environ, WORLD_HIP_BENCH_BACKEND="gloo")
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "1",
+           "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--full", "--steps", "1",
            "--warmup", "1", "--job-utterances", "10", "--sub-batch", "3", "--min-wall", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
@@ -306,7 +323,7 @@ def test_bare_bench_command_spawns_its_own_ranks():
     communicator reports it, `cpu_baseline` timed on rank 0, every rank's device named."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["WORLD_HIP_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "1",
            "--job-utterances", "8", "--sub-batch", "2", "--min-wall", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]

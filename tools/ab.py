@@ -29,7 +29,7 @@ def build(name, flags):
 def bench(name, extra):
     lib = os.path.join(ROOT, "world_amd", "libworld_hip.so") if name == "tree" else os.path.join(VAR_DIR, f"libworld_hip_{name}.so")
     env = dict(os.environ, WORLD_HIP_LIB=lib)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", *extra], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", *extra], capture_output=True, text=True,
                        env=env, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:

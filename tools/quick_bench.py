@@ -6,7 +6,7 @@ import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pre = tuple((sys.argv[2] if len(sys.argv) > 2 else 'd4c,ct_').split(','))
 cfg = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-cmd = [sys.executable, os.path.join(root, 'bench.py'), '--no-cpu-baseline', '--min-wall', '0.5']
+cmd = [sys.executable, os.path.join(root, 'bench.py'), '--full', '--no-cpu-baseline', '--min-wall', '0.5']
 cmd += ['--only-config', str(cfg)] if cfg != 1 else ['--no-configs', '--no-extras']
 out = subprocess.run(cmd, capture_output=True, text=True).stdout.strip().splitlines()[-1]
 d = json.loads(out); k = d['kernels_ms_per_step']
