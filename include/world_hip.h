@@ -599,6 +599,54 @@ WORLD_HIP_API int world_hip_resynthesize_batch(WorldHipContext *ctx, int n_utt, 
                                                const WorldHipModification *mods, double time_scale, const int *y_length,
                                                int y_stride, double *d_y);
 
+/* Frame-wise modification behind a time map: what world_hip_modify_batch does with one value per utterance, with one
+ * value per OUTPUT frame, and output frames placed anywhere between the source frames.  Each curve is a DEVICE array
+ * [n_utt][o_stride] of doubles, or NULL ("not given"); curves == NULL gives none.  Utterance u has n_frames[u] source
+ * frames (arrays [n_utt][f_stride]...) and n_out[u] >= 1 output frames (arrays [n_utt][o_stride]...; both counts HOST).
+ * Output frame j:
+ *   1. source position s = d_time_map[u][j] in source frames, clamped to [0, n_frames[u] - 1] (a value that is not > 0,
+ *      NaN included, reads frame 0); without a map s = j and n_out[u] must equal n_frames[u].  k = floor(s), w = s - k,
+ *      k1 = min(k + 1, n_frames[u] - 1).
+ *   2. spectrogram and aperiodicity rows: w == 0 or k1 == k takes row k bit for bit; otherwise
+ *      (1.0 - w) * row[k][i] + w * row[k1][i], the reference synthesiser's blend between two frames.
+ *   3. F0 (voiced = finite and > 0): w == 0 or k1 == k takes f0[k] bit for bit (NaN / Inf pass through); both neighbours
+ *      voiced: the same blend; exactly one voiced: that frame's F0 if its weight (1 - w for k, w for k1) is above 0.5,
+ *      else 0 (the reference's interpolated_vuv > 0.5); none voiced: 0.
+ *   4. mods[u].convert_log_f0 acts on the SOURCE track before step 3, with the source utterance's statistics.
+ *   5. d_f0_target: a frame that is voiced after step 3 takes d_f0_target[u][j] where that is finite and > 0.
+ *   6. F0 *= d_f0_scale[u][j] if given, else mods[u].f0_scale.
+ *   7. the row of step 2 is warped by d_formant_shift[u][j] if given, else mods[u].formant_shift: the arithmetic of
+ *      world_hip_modify_batch bit for bit; a ratio of 1 leaves the row out of log / exp.
+ *   8. d_ap_gain: ap = min(max(ap * g, 0.001), 1 - 1e-12) (GetSafeAperiodicity's bounds); without it the row of step 2.
+ * Curve values cannot be checked before the launch: a scale, ratio or gain that world_hip_modify_batch would refuse in
+ * mods (not finite, a negative scale or gain, a ratio <= 0 or with fft_size / 2 * ratio < 1) counts as 1 for that frame
+ * and touches no other frame.  Everything on the host is checked before any GPU work (mods, shapes, n_out[u] in
+ * [1, o_stride]); a refused call has written nothing.  Each in / out pair is optional as in world_hip_modify_batch.
+ * With a time map no output may be its input (refused); without one, in place (o_stride == f_stride) and out of place
+ * give the same bits.  Output frames and rows at or beyond n_out[u] are never written.  A log-F0 conversion takes
+ * n_utt * f_stride doubles of the workspace; in steady state nothing is copied from the host and the call can be
+ * captured. */
+typedef struct {
+  const double *d_time_map, *d_f0_target, *d_f0_scale, *d_formant_shift, *d_ap_gain;
+} WorldHipFrameCurves;
+WORLD_HIP_API int world_hip_modify_frames_batch(WorldHipContext *ctx, int n_utt, int fs, int fft_size, const int *n_frames,
+                                                int f_stride, const int *n_out, int o_stride,
+                                                const WorldHipModification *mods, const WorldHipFrameCurves *curves,
+                                                const double *d_f0_in, double *d_f0_out, const double *d_sp_in,
+                                                double *d_sp_out, const double *d_ap_in, double *d_ap_out);
+/* Harvest -> CheapTrick + D4C -> world_hip_modify_frames_batch -> Synthesis in one call, at the analysis frame period
+ * (the time map carries every change of duration).  Utterance u gives n_out[u] >= 2 output frames (curves
+ * [n_utt][o_stride]) and y_length[u] == world_hip_resynthesis_length(fs, n_out[u], frame_period, 1.0) samples.  The
+ * analysis and the modified frames live in the context's workspace.  Bit for bit what analyze_batch, modify_frames_batch
+ * and synthesis_batch produce in sequence; pulse capacity and refusals as world_hip_resynthesize_batch. */
+WORLD_HIP_API int world_hip_resynthesize_frames_batch(WorldHipContext *ctx, int n_utt, int fs, const double *d_x,
+                                                      int x_stride, const int *x_length,
+                                                      const HarvestOption *harvest_option,
+                                                      const CheapTrickOption *cheaptrick_option,
+                                                      const D4COption *d4c_option, const WorldHipModification *mods,
+                                                      const WorldHipFrameCurves *curves, const int *n_out, int o_stride,
+                                                      const int *y_length, int y_stride, double *d_y);
+
 /* Real-time synthesis, batched (reference src/synthesisrealtime.cpp; the drop-in WorldSynthesizer above is built on it).
  * One object serves n_streams independent streams with one fs, frame_period (ms), fft_size, buffer_size and ring size
  * number_of_pointers; every stream behaves exactly as one reference synthesiser: same pulses, same return values, its own

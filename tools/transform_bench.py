@@ -6,7 +6,15 @@ world_hip_resynthesize_batch), timed with HIP events on one GPU.
 Default shape: BASELINE.json configs[1], 12 utterances of 10 s at 48 kHz.  Prints one JSON line:
   analyze_ms, modify_ms (F0 scale + formant shift of every frame, out of place), synthesis_ms, resynthesize_ms (the one call),
   modify_share = modify / analyze, overhead = resynthesize / (analyze + modify + synthesis) - 1.
-Every figure is the median of --reps timed repetitions after two warm-up calls of the same shape."""
+Every figure is the median of --reps timed repetitions after two warm-up calls of the same shape.
+
+    python tools/transform_bench.py --frames [--rounds 5] [--only c]
+
+times the frame-wise route (world_hip_modify_frames_batch) beside the per-utterance one on the same analysis, in
+alternating rounds of one process: (a) modify_batch with constant ratios, (b) modify_frames_batch with the same constants
+as curves behind an identity map, (c) a 1.5 x uniform time map with ratios that vary per frame (c_with_ap: the
+aperiodicity rows retimed as well).  a_spread is (max - min) / median of (a)'s per-round medians: what a difference
+between (a) and (b) has to exceed to mean anything.  --only runs one of them alone (for a kernel trace)."""
 import argparse
 import ctypes as C
 import json
@@ -24,6 +32,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--fs", type=int, default=48000)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--frames", action="store_true", help="time modify_frames_batch beside modify_batch")
+    ap.add_argument("--rounds", type=int, default=5, help="--frames: alternating rounds")
+    ap.add_argument("--only", choices=("a", "b", "c", "c_with_ap"), default=None, help="--frames: run this one alone")
     a = ap.parse_args()
     import torch
     from world_amd import synth
@@ -79,6 +90,42 @@ def main():
             raise RuntimeError("pulses dropped: the timed synthesis is not the whole synthesis")
         return float(np.median(ms))
 
+    if a.frames:
+        analyze()
+        O = int((F - 1) * 1.5) + 1
+        dev = x.device
+        ident = torch.arange(F, dtype=torch.float64, device=dev).repeat(B, 1)      # ([B, O] curves: the wrapper copies nothing)
+        const = lambda v: torch.full((B, F), v, dtype=torch.float64, device=dev)
+        gen = torch.Generator(device="cpu").manual_seed(1)
+        vary = lambda lo, hi: (lo + (hi - lo) * torch.rand((B, O), dtype=torch.float64, generator=gen)).to(dev)
+        stretch = (torch.arange(O, dtype=torch.float64, device=dev) * ((F - 1) / (O - 1))).repeat(B, 1)
+        b_curves = dict(time_map=ident, f0_scale=const(1.5), formant_shift=const(1.2))
+        c_curves = dict(time_map=stretch, f0_scale=vary(0.8, 1.6), formant_shift=vary(0.8, 1.3))
+        c_gain = vary(0.8, 1.2)
+        b_out = (torch.empty_like(f0), torch.empty_like(sp), None)
+        c_out = (torch.empty((B, O), dtype=torch.float64, device=dev), torch.empty((B, O, sp.shape[2]), dtype=torch.float64, device=dev))
+        c_ap = torch.empty_like(c_out[1])
+        runs = {"a": modify,
+                "b": lambda: wh.modify_frames(f0, sp, None, nf, fs, fft, out=b_out, validate=False, **b_curves),
+                "c": lambda: wh.modify_frames(f0, sp, None, nf, fs, fft, out=(*c_out, None), validate=False, **c_curves),
+                "c_with_ap": lambda: wh.modify_frames(f0, sp, aper, nf, fs, fft, out=(*c_out, c_ap), validate=False,
+                                                      ap_gain=c_gain, **c_curves)}
+        if a.only:
+            runs = {a.only: runs[a.only]}
+        per_round = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                per_round[k].append(timed(fn))
+        row = 8 * (fft // 2 + 1)
+        out = {"shape": f"{B} x {a.seconds:g} s at {fs} Hz", "frames": int(nf.sum()), "out_frames_c": B * O,
+               "sp_bytes_a_b": 2 * int(nf.sum()) * row, "sp_bytes_c": 3 * B * O * row}
+        for k, v in per_round.items():
+            out[k + "_ms"] = round(float(np.median(v)), 4)
+            out[k + "_rounds"] = [round(t, 4) for t in v]
+        if "a" in per_round:
+            out["a_spread"] = round((max(per_round["a"]) - min(per_round["a"])) / float(np.median(per_round["a"])), 4)
+        print(json.dumps(out))
+        return
     t_an = timed(analyze)
     t_mod = timed(modify)
     t_syn = timed(synthesis)

@@ -65,6 +65,34 @@ def modifications(n_utt, f0_scale=1.0, formant_shift=1.0, log_f0_target=None):
     return mods
 
 
+class WorldHipFrameCurves(C.Structure):    # include/world_hip.h: device arrays [n_utt][o_stride], or NULL
+    _fields_ = [(name, C.c_void_p) for name in ("d_time_map", "d_f0_target", "d_f0_scale", "d_formant_shift", "d_ap_gain")]
+
+
+def uniform_time_map(n_src, n_out, device="cuda"):
+    """Time map [n_out] (float64, on `device`) that spreads n_src source frames evenly over n_out output frames: first
+    onto first, last onto last."""
+    import torch
+    step = (n_src - 1) / (n_out - 1) if n_out > 1 else 0.0
+    return (torch.arange(n_out, dtype=torch.float64, device=device) * step).clamp_(0.0, float(max(n_src - 1, 0)))
+
+
+def hold_time_map(n_src, segments, device="cuda"):
+    """Piecewise-linear time map through the anchors `segments` = [(src_frame, out_frame), ...] (out_frame strictly
+    increasing from 0): [last out_frame + 1] source positions (float64, on `device`), clamped to [0, n_src - 1].  Two
+    anchors with the same src_frame hold that frame; a steeper stretch plays its frames faster."""
+    import torch
+    src = np.asarray([a[0] for a in segments], dtype=np.float64)
+    dst = np.asarray([a[1] for a in segments], dtype=np.float64)
+    if len(segments) < 2 or dst[0] != 0 or np.any(np.diff(dst) <= 0) or np.any(dst != np.floor(dst)):
+        raise ValueError("hold_time_map: at least two anchors, out_frame whole, starting at 0 and strictly increasing")
+    xs, xd = torch.from_numpy(src).to(device), torch.from_numpy(dst).to(device)
+    j = torch.arange(int(dst[-1]) + 1, dtype=torch.float64, device=device)
+    k = torch.searchsorted(xd, j, right=True).clamp_(1, len(segments) - 1)
+    w = (j - xd[k - 1]) / (xd[k] - xd[k - 1])
+    return (xs[k - 1] + w * (xs[k] - xs[k - 1])).clamp_(0.0, float(max(n_src - 1, 0)))
+
+
 # -- the real-time synthesiser (reference synthesisrealtime.h; include/world_hip.h declares the same layout) --
 class RandnState(C.Structure):       # reference matlabfunctions.h
     _fields_ = [("g_randn_x", C.c_uint32), ("g_randn_y", C.c_uint32), ("g_randn_z", C.c_uint32), ("g_randn_w", C.c_uint32)]
@@ -314,6 +342,13 @@ def load_library(path=LIB_PATH):
         lib.world_hip_resynthesize_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                                      C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, C.c_double,
                                                      _ip, C.c_int, vp]
+    if hasattr(lib, "world_hip_modify_frames_batch"):                # (likewise)
+        mp, cp = C.POINTER(WorldHipModification), C.POINTER(WorldHipFrameCurves)
+        lib.world_hip_modify_frames_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, C.c_int, mp, cp,
+                                                      vp, vp, vp, vp, vp, vp]
+        lib.world_hip_resynthesize_frames_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
+                                                            C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, cp, _ip,
+                                                            C.c_int, _ip, C.c_int, vp]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -885,6 +920,147 @@ class WorldHip:
                 run()
                 if self.synthesis_pulses_dropped():
                     raise RuntimeError("resynthesize: pulses dropped even at the requested capacity")
+            finally:
+                self.set_synthesis_pulse_capacity(0)
+        return y, yl
+
+    # ---- frame-wise modification behind a time map (include/world_hip.h: world_hip_modify_frames_batch) ----
+    def _frames_lib(self):
+        if not hasattr(self.lib, "world_hip_modify_frames_batch"):
+            raise RuntimeError("this libworld_hip.so has no frame-wise modification (world_hip_modify_frames_batch)")
+        return self.lib
+
+    def _frame_curves(self, B, time_map, f0_target, f0_scale, formant_shift, ap_gain):
+        """(the curves given, by WorldHipFrameCurves field; per-utterance f0_scale; per-utterance formant_shift; their
+        common width O or None).  f0_scale / formant_shift given as tensors are curves; anything else is one value per
+        utterance.  Curves are [B, O] float64 device tensors ([O]: shared by the batch)."""
+        t = self.torch
+        curves = dict(d_time_map=time_map, d_f0_target=f0_target, d_ap_gain=ap_gain,
+                      d_f0_scale=f0_scale if t.is_tensor(f0_scale) else None,
+                      d_formant_shift=formant_shift if t.is_tensor(formant_shift) else None)
+        keep, O = {}, None
+        for name, a in curves.items():
+            if a is None:
+                continue
+            assert a.dtype == t.float64 and a.device == self.device, f"{name[2:]}: a float64 tensor on {self.device}"
+            if a.dim() == 1:
+                a = a[None].expand(B, -1)
+            assert a.dim() == 2 and a.shape[0] == B, f"{name[2:]}: [B, O] or [O]"
+            O = a.shape[1] if O is None else O
+            assert a.shape[1] == O, "the curves disagree about the number of output frames"
+            keep[name] = a.contiguous()
+        return (keep, 1.0 if "d_f0_scale" in keep else f0_scale, 1.0 if "d_formant_shift" in keep else formant_shift, O)
+
+    def _validate_curves(self, keep, n_out, fft_size):
+        """The curve values of the frames below n_out, checked on the device (one reduction, one synchronisation): a value
+        the library would replace by 1 raises instead.  f0_target is free: not finite or <= 0 means "keep this frame"."""
+        t = self.torch
+        bad = t.zeros((), dtype=t.bool, device=self.device)
+        for name, a in keep.items():
+            if name == "d_time_map":
+                wrong = t.isnan(a)
+            elif name == "d_f0_target":
+                continue
+            elif name == "d_formant_shift":
+                wrong = ~t.isfinite(a) | ~(a > 0) | ~(fft_size / 2.0 * a >= 1.0)
+            else:
+                wrong = ~t.isfinite(a) | (a < 0)
+            live = t.arange(a.shape[1], device=self.device)[None] < t.as_tensor(n_out, device=self.device)[:, None]
+            bad = bad | (wrong & live).any()
+        if keep and bool(bad):
+            raise ValueError("a curve holds a value outside its range (time_map: NaN; f0_scale, ap_gain: not finite or < 0; "
+                             "formant_shift: not finite, <= 0 or below 2 / fft_size)")
+
+    def modify_frames(self, f0, sp, ap, n_frames, fs, fft_size, n_out=None, time_map=None, f0_target=None, f0_scale=1.0,
+                      formant_shift=1.0, ap_gain=None, log_f0_target=None, out=None, validate=True):
+        """Per-frame modification and time warping in one pass: f0 [B, F], sp / ap [B, F, fft/2+1] (float64, device; any
+        may be None) -> (f0', sp', ap') with n_out[u] output frames each ([B, O] / [B, O, fft/2+1]).  time_map [B, O] or
+        [O]: the source position of every output frame, in source frames (uniform_time_map, hold_time_map); None keeps
+        the frames where they are (n_out = n_frames).  f0_target, ap_gain: curves or None; f0_scale, formant_shift: a
+        curve (tensor), or one value per utterance as in modify().  n_out: frames per utterance, default all O.  out: None
+        = new tensors (zero beyond n_out), "inplace" (without a time map only), or an (f0_out, sp_out, ap_out) triple."""
+        t = self.torch
+        L = self._frames_lib()
+        ref = next((a for a in (f0, sp, ap) if a is not None), None)
+        assert ref is not None, "modify_frames: nothing to modify"
+        B, F = ref.shape[0], ref.shape[1]
+        nb = fft_size // 2 + 1
+        for a, dims in ((f0, 2), (sp, 3), (ap, 3)):
+            if a is not None:
+                assert a.dtype == t.float64 and a.dim() == dims and a.is_contiguous() and a.device == self.device
+                assert a.shape[:2] == (B, F) and (dims == 2 or a.shape[2] == nb)
+        nf = np.ascontiguousarray(np.broadcast_to(n_frames, (B,)), dtype=np.int32)
+        keep, scale, ratio, O = self._frame_curves(B, time_map, f0_target, f0_scale, formant_shift, ap_gain)
+        O = F if O is None else O
+        if n_out is None:
+            n_out = nf if time_map is None else O
+        no = np.ascontiguousarray(np.broadcast_to(n_out, (B,)), dtype=np.int32)
+        if validate:
+            self._validate_curves(keep, no, fft_size)
+        cv = WorldHipFrameCurves(**{name: a.data_ptr() for name, a in keep.items()})
+        if out == "inplace":
+            outs = (f0, sp, ap)
+        elif out is not None:
+            outs = tuple(out)
+        else:
+            shape = lambda a: (B, O) + tuple(a.shape[2:])
+            outs = tuple(t.zeros(shape(a), dtype=t.float64, device=self.device) if a is not None else None
+                         for a in (f0, sp, ap))
+        for a, o in zip((f0, sp, ap), outs):
+            assert (a is None) == (o is None)
+            if o is not None:
+                assert o.dtype == t.float64 and o.is_contiguous() and o.device == self.device
+                assert o.shape == (B, O) + tuple(a.shape[2:])
+        mods = modifications(B, scale, ratio, log_f0_target)
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        self._check(L.world_hip_modify_frames_batch(self._context(), B, int(fs), int(fft_size), nf.ctypes.data_as(_ip), F,
+                                                    no.ctypes.data_as(_ip), O, mods, C.byref(cv), ptr(f0), ptr(outs[0]),
+                                                    ptr(sp), ptr(outs[1]), ptr(ap), ptr(outs[2])), "modify_frames")
+        return outs
+
+    def resynthesize_frames(self, x, fs, x_len=None, n_out=None, time_map=None, f0_target=None, f0_scale=1.0,
+                            formant_shift=1.0, ap_gain=None, log_f0_target=None, frame_period=5.0, f0_floor=71.0,
+                            f0_ceil=800.0, q1=-0.15, threshold=0.85, out=None, validate=True):
+        """analyze -> modify_frames -> synthesis in one library call (world_hip_resynthesize_frames_batch): x [B, L] ->
+        (y [B, max(y_length)], y_length).  The curves are as in modify_frames(), over the output frames; the duration
+        comes from the time map alone (synthesis runs at frame_period).  Pulses that did not fit: as resynthesize()."""
+        t = self.torch
+        L = self._frames_lib()
+        B, Lx, xl = self._prep(x, x_len)
+        fft_size = cheaptrick_fft_size(fs, 71.0)
+        nf = np.array([frame_count(fs, int(n), frame_period) for n in xl], dtype=np.int32)
+        keep, scale, ratio, O = self._frame_curves(B, time_map, f0_target, f0_scale, formant_shift, ap_gain)
+        O = int(nf.max()) if O is None else O
+        if n_out is None:
+            n_out = nf if time_map is None else O
+        no = np.ascontiguousarray(np.broadcast_to(n_out, (B,)), dtype=np.int32)
+        if validate:
+            self._validate_curves(keep, no, fft_size)
+        cv = WorldHipFrameCurves(**{name: a.data_ptr() for name, a in keep.items()})
+        yl = np.array([L.world_hip_resynthesis_length(int(fs), int(n), float(frame_period), 1.0) for n in no], dtype=np.int32)
+        if int(yl.min()) < 1:
+            raise ValueError(f"resynthesize_frames: invalid frame_period {frame_period} / n_out {no}")
+        Y = int(yl.max())
+        y = out if out is not None else t.zeros((B, Y), dtype=t.float64, device=x.device)
+        assert y.dtype == t.float64 and y.is_contiguous() and y.shape == (B, Y) and y.device == x.device
+        mods = modifications(B, scale, ratio, log_f0_target)
+        hopt, copt, dopt = HarvestOption(f0_floor, f0_ceil, frame_period), CheapTrickOption(q1, 71.0, fft_size), D4COption(threshold)
+
+        def run():
+            self._check(L.world_hip_resynthesize_frames_batch(self._context(), B, int(fs), x.data_ptr(), Lx,
+                                                              xl.ctypes.data_as(_ip), C.byref(hopt), C.byref(copt),
+                                                              C.byref(dopt), mods, C.byref(cv), no.ctypes.data_as(_ip), O,
+                                                              yl.ctypes.data_as(_ip), Y, y.data_ptr()), "resynthesize_frames")
+        run()
+        need = self.synthesis_pulses_dropped()          # (synchronises) -- as resynthesize(): one repeat at the asked capacity
+        if need:
+            if need > Y:
+                raise RuntimeError(f"resynthesize_frames: {need} pitch pulses for {Y} output samples")
+            self.set_synthesis_pulse_capacity(need + 16)
+            try:
+                run()
+                if self.synthesis_pulses_dropped():
+                    raise RuntimeError("resynthesize_frames: pulses dropped even at the requested capacity")
             finally:
                 self.set_synthesis_pulse_capacity(0)
         return y, yl

@@ -1489,6 +1489,138 @@ static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double 
   }
 }
 
+// Frame-wise modification behind a time map (include/world_hip.h: world_hip_modify_frames_batch; codec.hip's
+// modify_frames_sp / _ap / _f0).  Everything the host can know is checked before any GPU work; the curves' values live on
+// the device and are made harmless in the kernels.  f0, sp and ap independently optional, as in run_modify.
+static void run_modify_frames(WorldHipContext *c, int n_utt, int fs, int fft_size, const int *n_frames, int f_stride,
+                              const int *n_out, int o_stride, const WorldHipModification *mods,
+                              const WorldHipFrameCurves *curves, const double *d_f0_in, double *d_f0_out,
+                              const double *d_sp_in, double *d_sp_out, const double *d_ap_in, double *d_ap_out) {
+  if (n_utt <= 0) fail("n_utt must be positive");
+  if (!n_frames || !n_out) fail("null n_frames / n_out");
+  if (!d_f0_in != !d_f0_out) fail("modify_frames: give both d_f0_in and d_f0_out, or neither");
+  if (!d_sp_in != !d_sp_out) fail("modify_frames: give both d_sp_in and d_sp_out, or neither");
+  if (!d_ap_in != !d_ap_out) fail("modify_frames: give both d_ap_in and d_ap_out, or neither");
+  const bool with_sp = d_sp_in != nullptr, with_ap = d_ap_in != nullptr, with_f0 = d_f0_in != nullptr;
+  if (with_sp || with_ap) {
+    if (fs <= 0) fail("fs must be positive");
+    const int lg = ilog2_exact(fft_size);
+    if (lg < 7 || lg > 13) fail("modify_frames: fft_size %d unsupported (128..8192)", fft_size);
+  }
+  check_modifications(mods, n_utt, with_sp ? fft_size : 0);
+  max_frame_count(n_frames, n_utt, f_stride);
+  const WorldHipFrameCurves none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  const WorldHipFrameCurves &cv = curves ? *curves : none;
+  const bool in_place = (with_f0 && d_f0_in == d_f0_out) || (with_sp && d_sp_in == d_sp_out) || (with_ap && d_ap_in == d_ap_out);
+  if (cv.d_time_map && in_place) fail("modify_frames: a time map needs output arrays of their own (in == out)");
+  if (in_place && o_stride != f_stride) fail("modify_frames: in place needs o_stride == f_stride");
+  int max_out = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_out[u] < 1 || n_out[u] > o_stride) fail("n_out[%d]=%d outside [1, o_stride=%d]", u, n_out[u], o_stride);
+    if (cv.d_time_map && n_frames[u] < 1) fail("modify_frames: utterance %d has no source frame to read", u);
+    if (!cv.d_time_map && n_out[u] != n_frames[u])
+      fail("modify_frames: utterance %d: without a time map n_out (%d) must equal n_frames (%d)", u, n_out[u], n_frames[u]);
+    max_out = std::max(max_out, n_out[u]);
+  }
+  if (!with_sp && !with_ap && !with_f0) return;
+  std::vector<double> ratio(n_utt, 1.0), scale(n_utt, 1.0), one(n_utt, 1.0), target(2 * (size_t)n_utt, 0.0);
+  std::vector<int> convert(n_utt, 0);
+  bool converts = false;
+  for (int u = 0; mods && u < n_utt; ++u) {
+    ratio[u] = mods[u].formant_shift; scale[u] = mods[u].f0_scale; convert[u] = mods[u].convert_log_f0;
+    target[2 * u] = mods[u].log_f0_mean; target[2 * u + 1] = mods[u].log_f0_std;
+    converts |= with_f0 && convert[u] != 0;
+  }
+  // the log-F0 conversion acts on the SOURCE track, before the frames are blended: modify_f0 as it is (scale 1) into a
+  // temporary, which modify_frames_f0 then reads
+  double *f0_conv = nullptr;
+  if (converts)
+    begin_stage(c, [&](Arena &a) { f0_conv = a.take<double>((size_t)n_utt * f_stride); });
+  else
+    open_uploads(c);                                        // (no workspace: prepared offsets stay valid)
+  ModifyFramesParams p;
+  p.m.n_utt = n_utt; p.m.f_stride = f_stride; p.m.fs = fs; p.m.fft_size = fft_size;
+  p.m.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.m.ratio = upload(c, ratio); p.m.sp_in = d_sp_in; p.m.sp_out = d_sp_out;
+  p.m.f0_scale = upload(c, scale); p.m.convert = upload(c, convert); p.m.target = upload(c, target);
+  p.m.f0_in = d_f0_in; p.m.f0_out = d_f0_out; p.m.stats = nullptr;
+  p.o_stride = o_stride;
+  p.n_out = upload(c, std::vector<int>(n_out, n_out + n_utt));
+  p.time_map = cv.d_time_map; p.f0_target = cv.d_f0_target; p.f0_scale = cv.d_f0_scale;
+  p.formant_shift = cv.d_formant_shift; p.ap_gain = cv.d_ap_gain;
+  p.ap_in = d_ap_in; p.ap_out = d_ap_out;
+  p.f0_src = d_f0_in;
+  if (converts) {
+    ModifyParams conv = p.m;
+    conv.f0_scale = upload(c, one); conv.f0_out = f0_conv;
+    launch_modify_f0(conv, c->stream);
+    p.f0_src = f0_conv;
+  }
+  if (with_sp) launch_modify_frames_sp(p, max_out, c->stream);
+  if (with_ap) launch_modify_frames_ap(p, max_out, c->stream);
+  if (with_f0) launch_modify_frames_f0(p, max_out, c->stream);
+}
+
+// Harvest -> CheapTrick + D4C -> run_modify_frames -> Synthesis at the analysis frame period.  As run_resynthesis, with
+// the n_out modified frames held at the bottom of the arena beside the analysis they are made from.
+static void run_resynthesis_frames(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
+                                   const HarvestOption *hopt, const CheapTrickOption *copt, const D4COption *dopt,
+                                   const WorldHipModification *mods, const WorldHipFrameCurves *curves, const int *n_out,
+                                   int o_stride, const int *y_length, int y_stride, double *d_y) {
+  check_batch(n_utt, fs, d_x, x_stride, x_length);
+  if (!hopt || !copt || !dopt) fail("null option");
+  if (!(hopt->f0_floor > 0) || !(hopt->f0_ceil > hopt->f0_floor) || !(hopt->frame_period > 0) ||
+      !std::isfinite(hopt->frame_period) || !std::isfinite(hopt->f0_ceil))
+    fail("bad HarvestOption");
+  if (!n_out || !y_length || !d_y) fail("null buffer");
+  const int fft_size = copt->fft_size;
+  const std::string lim = shape_limit(6, fs, fft_size);
+  if (!lim.empty()) fail("%s", lim.c_str());
+  check_modifications(mods, n_utt, fft_size);
+  const bool mapped = curves && curves->d_time_map;
+  std::vector<int> nf(n_utt);
+  int f_stride = 1;
+  for (int u = 0; u < n_utt; ++u) {
+    nf[u] = frame_count(fs, x_length[u], hopt->frame_period);
+    if (nf[u] < 2) fail("resynthesize_frames: utterance %d has %d frame(s); synthesis needs 2", u, nf[u]);
+    if (n_out[u] < 2 || n_out[u] > o_stride) fail("resynthesize_frames: n_out[%d]=%d outside [2, o_stride=%d]", u, n_out[u], o_stride);
+    if (!mapped && n_out[u] != nf[u])
+      fail("resynthesize_frames: utterance %d: without a time map n_out must equal its %d frames (n_out %d)", u, nf[u], n_out[u]);
+    if (y_length[u] != resynthesis_length(fs, n_out[u], hopt->frame_period, 1.0) || y_length[u] > y_stride)
+      fail("y_length[%d]=%d is not the length of %d frames within y_stride=%d", u, y_length[u], n_out[u], y_stride);
+    f_stride = std::max(f_stride, nf[u]);
+  }
+  const size_t fr = (size_t)n_utt * f_stride, fo = (size_t)n_utt * o_stride, nb = fft_size / 2 + 1;
+  double *tpos = nullptr, *f0 = nullptr, *sp = nullptr, *ap = nullptr, *f0m = nullptr, *spm = nullptr, *apm = nullptr;
+  auto carve = [&](Arena &a) {
+    tpos = a.take<double>(fr); f0 = a.take<double>(fr);
+    sp = a.take<double>(fr * nb); ap = a.take<double>(fr * nb);
+    f0m = a.take<double>(fo); spm = a.take<double>(fo * nb); apm = a.take<double>(fo * nb);
+  };
+  struct Release {                                          // the floor never outlives the call, whatever happens in it
+    WorldHipContext *c;
+    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
+  } release{c};
+  size_t want = 0;
+  for (int attempt = 0;; ++attempt) {
+    c->arena.floor = 0;
+    ensure_arena(c, std::max(measure(carve), want));
+    arena_reset(c);
+    carve(c->arena);
+    c->arena.floor = c->arena.used;
+    try {
+      run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
+      run_modify_frames(c, n_utt, fs, fft_size, nf.data(), f_stride, n_out, o_stride, mods, curves, f0, f0m, sp, spm, ap, apm);
+      run_synthesis(c, n_utt, fs, hopt->frame_period, fft_size, n_out, o_stride, f0m, spm, apm, y_length, y_stride, d_y);
+      return;
+    } catch (const ArenaRegrow &r) {
+      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
+      if (attempt >= 4) fail("resynthesize_frames: the workspace did not settle");
+      want = std::max(want, r.bytes);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2119,6 +2251,25 @@ int world_hip_modify_batch(WorldHipContext *c, int n_utt, int fs, int fft_size, 
                            double *d_sp_out) {
   return guarded(c, [&] {
     run_modify(c, n_utt, fs, fft_size, n_frames, f_stride, mods, d_f0_in, d_f0_out, d_sp_in, d_sp_out);
+  });
+}
+int world_hip_modify_frames_batch(WorldHipContext *c, int n_utt, int fs, int fft_size, const int *n_frames, int f_stride,
+                                  const int *n_out, int o_stride, const WorldHipModification *mods,
+                                  const WorldHipFrameCurves *curves, const double *d_f0_in, double *d_f0_out,
+                                  const double *d_sp_in, double *d_sp_out, const double *d_ap_in, double *d_ap_out) {
+  return guarded(c, [&] {
+    run_modify_frames(c, n_utt, fs, fft_size, n_frames, f_stride, n_out, o_stride, mods, curves, d_f0_in, d_f0_out, d_sp_in,
+                      d_sp_out, d_ap_in, d_ap_out);
+  });
+}
+int world_hip_resynthesize_frames_batch(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride,
+                                        const int *x_length, const HarvestOption *harvest_option,
+                                        const CheapTrickOption *cheaptrick_option, const D4COption *d4c_option,
+                                        const WorldHipModification *mods, const WorldHipFrameCurves *curves, const int *n_out,
+                                        int o_stride, const int *y_length, int y_stride, double *d_y) {
+  return guarded(c, [&] {
+    run_resynthesis_frames(c, n_utt, fs, d_x, x_stride, x_length, harvest_option, cheaptrick_option, d4c_option, mods, curves,
+                           n_out, o_stride, y_length, y_stride, d_y);
   });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {

@@ -53,4 +53,26 @@ size_t modify_warp_lds_bytes(int fft_size);
 void launch_modify_warp_sp(const ModifyParams &p, int max_frames, hipStream_t stream);
 void launch_modify_f0(const ModifyParams &p, hipStream_t stream);
 
+// Frame-wise modification with a time map (world_hip_modify_frames_batch): output frame j of utterance u is made from the
+// source frames floor(s) and floor(s) + 1 around its source position s, then modified by that frame's own values.  A curve
+// is a device array [n_utt][o_stride] or nullptr ("not given": the per-utterance value of `m` holds, or no time map / target
+// / gain at all).  m.n_frames / m.f_stride describe the source, n_out / o_stride the output; m.sp_in, m.f0_in are source
+// arrays, m.sp_out, m.f0_out output arrays.  Curve values that the per-utterance checks would refuse count as 1.
+struct ModifyFramesParams {
+  ModifyParams m;
+  int o_stride;
+  const int *n_out;              // output frames of each utterance; rows / frames beyond are never written
+  const double *time_map;        // source position in frames, clamped to [0, n_frames - 1]; nullptr: s = j
+  const double *f0_target;       // replaces the F0 of voiced output frames where finite and > 0
+  const double *f0_scale;        // replaces m.f0_scale[u]
+  const double *formant_shift;   // replaces m.ratio[u]
+  const double *ap_gain;         // ap = min(max(ap * g, 0.001), 1 - 1e-12); nullptr: the rows as they are
+  const double *ap_in;
+  double *ap_out;
+  const double *f0_src;          // the source track modify_frames_f0 reads: m.f0_in, or its log-F0 conversion (a temporary)
+};
+void launch_modify_frames_sp(const ModifyFramesParams &p, int max_out, hipStream_t stream);
+void launch_modify_frames_ap(const ModifyFramesParams &p, int max_out, hipStream_t stream);
+void launch_modify_frames_f0(const ModifyFramesParams &p, int max_out, hipStream_t stream);
+
 }  // namespace world_hip

@@ -16,6 +16,9 @@
 //   modify_warp_sp : log row -> interp1 from the axis ratio*i/fft*fs onto i/fft*fs -> exp, bins from
 //                    int(fft/2*ratio) up filled with the bin below when ratio < 1   (one workgroup per row)
 //   modify_f0      : optional log-F0 statistics conversion, then f0 *= scale     (one workgroup per utterance)
+// and their frame-wise form behind a time map, with per-frame values (world_hip_modify_frames_batch):
+//   modify_frames_sp / _ap / _f0 : output frame j = the blend of the two source frames around its source position,
+//                    then the warp / gain / target and scale of that frame
 // The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
 #include "codec.h"
 #include "fft.h"
@@ -131,6 +134,34 @@ __global__ void codec_decode_ap(CodecParams p) {
 // against those knots, so k and the weights are the reference's bit for bit.  Per output bin: two FP64 divisions (xi and
 // the interpolation weight), one exp; per input bin: one log, one division for its knot.
 // ---------------------------------------------------------------------------------------------------------------------
+// One row through the warp, by the whole workgroup: `load(j)` is bin j of the row to warp (read once), `lds` holds 2 nb doubles.
+template <class Load>
+__device__ __forceinline__ void warp_sp_row(Load load, double *out, double ratio, int fft_size, int fs, char *lds) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int nb = fft_size / 2 + 1;
+  double *lg = reinterpret_cast<double *>(lds);       // log row, nb doubles
+  double *kx = lg + nb;                               // knots, nb doubles
+  for (int j = tid; j < nb; j += nt) {
+    lg[j] = log(load(j));
+    kx[j] = ratio * j / fft_size * fs;                // test.cpp:237, in this order
+  }
+  __syncthreads();                                    // (in place: every read of the row is done before the first write)
+  // ratio < 1: bins m .. nb-1 take bin m-1's warped value (test.cpp:250-254)
+  const int m = ratio < 1.0 ? static_cast<int>(fft_size / 2.0 * ratio) : nb;
+  const double inv_ratio = 1.0 / ratio;               // (the guess only: the knots decide)
+  for (int j = tid; j < nb; j += nt) {
+    const int q = j < m ? j : m - 1;
+    const double xi = static_cast<double>(q) / fft_size * fs;
+    const double g = q * inv_ratio;
+    int c = g >= nb - 1 ? nb - 1 : static_cast<int>(g);   // the last knot <= xi: a guess ...
+    while (c < nb - 1 && kx[c + 1] <= xi) ++c;
+    while (c > 0 && kx[c] > xi) --c;                      // ... corrected (x[0] = 0 <= xi always)
+    const int k = c + 1 < nb - 1 ? c + 1 : nb - 1;
+    const double s = (xi - kx[k - 1]) / (kx[k] - kx[k - 1]);
+    out[j] = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
+  }
+}
+
 __global__ void __launch_bounds__(256) modify_warp_sp(ModifyParams p) {
   DYN_LDS(lds);
   const int f = blockIdx.x, u = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
@@ -145,26 +176,86 @@ __global__ void __launch_bounds__(256) modify_warp_sp(ModifyParams p) {
       for (int j = tid; j < nb; j += nt) out[j] = in[j];
     return;
   }
-  double *lg = reinterpret_cast<double *>(lds);       // log row, nb doubles
-  double *kx = lg + nb;                               // knots, nb doubles
-  for (int j = tid; j < nb; j += nt) {
-    lg[j] = log(in[j]);
-    kx[j] = ratio * j / p.fft_size * p.fs;            // test.cpp:237, in this order
+  warp_sp_row([&](int j) { return in[j]; }, out, ratio, p.fft_size, p.fs, lds);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Frame-wise modification (world_hip_modify_frames_batch).  Output frame j of utterance u sits at the source position
+// s = time_map[u][j] (j without a map), clamped to [0, n_frames - 1] (not > 0, NaN included: 0): k = floor(s), w = s - k,
+// k1 = min(k + 1, n_frames - 1).  w == 0 or k1 == k: row k as it is; else (1 - w) row[k] + w row[k1], the expression
+// of the reference's synthesiser between two frames (synthesis.cpp:141-180).
+//   modify_frames_sp : one workgroup per output row; the blend happens as the bins are loaded, so the warp sees one row
+//                      and its LDS stays the log row and the knots.  Two source rows read, one written.
+//   modify_frames_ap : the same blend, then the optional gain within GetSafeAperiodicity's bounds.  A kernel of its own:
+//                      it streams (no LDS, no search), so it runs at full occupancy and leaves modify_frames_sp with
+//                      modify_warp_sp's registers and LDS.
+//   modify_frames_f0 : one thread per output frame.
+// A curve value the per-utterance checks would refuse (api.hip: check_modifications) counts as 1.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SourcePosition { int k, k1; double w; bool blend; };
+__device__ __forceinline__ SourcePosition source_position(const double *time_map, size_t at, int j, int n_src) {
+  double s = time_map ? time_map[at] : static_cast<double>(j);
+  if (!(s > 0.0)) s = 0.0;
+  if (s > n_src - 1) s = n_src - 1;
+  SourcePosition sp;
+  sp.k = static_cast<int>(s);                         // (s >= 0: the floor)
+  sp.w = s - sp.k;
+  sp.k1 = sp.k + 1 < n_src - 1 ? sp.k + 1 : n_src - 1;
+  sp.blend = sp.w != 0.0 && sp.k1 != sp.k;
+  return sp;
+}
+__device__ __forceinline__ double valid_scale(double v) { return __builtin_isfinite(v) && v >= 0.0 ? v : 1.0; }
+__device__ __forceinline__ double valid_ratio(double r, int fft_size) {
+  return __builtin_isfinite(r) && r > 0.0 && fft_size / 2.0 * r >= 1.0 ? r : 1.0;
+}
+
+__global__ void __launch_bounds__(256) modify_frames_sp(ModifyFramesParams p) {
+  DYN_LDS(lds);
+  const int j = blockIdx.x, u = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  const int nb = p.m.fft_size / 2 + 1;
+  // j < gridDim.x <= o_stride: the frame's curve values exist whether or not the frame does, so they are fetched beside
+  // n_out[u] instead of behind it (one round trip to memory less at the head of every workgroup)
+  const size_t at = (size_t)u * p.o_stride + j;
+  const SourcePosition s = source_position(p.time_map, at, j, p.m.n_frames[u]);
+  const double ratio = p.formant_shift ? valid_ratio(p.formant_shift[at], p.m.fft_size) : p.m.ratio[u];
+  if (j >= p.n_out[u]) return;
+  const double *a = p.m.sp_in + ((size_t)u * p.m.f_stride + s.k) * nb;
+  const double *b = p.m.sp_in + ((size_t)u * p.m.f_stride + s.k1) * nb;
+  double *out = p.m.sp_out + at * nb;
+  const double w = s.w;
+  if (ratio == 1.0) {                                 // no log / exp round trip
+    if (s.blend)
+      for (int i = tid; i < nb; i += nt) out[i] = (1.0 - w) * a[i] + w * b[i];
+    else if (out != a)
+      for (int i = tid; i < nb; i += nt) out[i] = a[i];
+    return;
   }
-  __syncthreads();                                    // (in place: every read of the row is done before the first write)
-  // ratio < 1: bins m .. nb-1 take bin m-1's warped value (test.cpp:250-254)
-  const int m = ratio < 1.0 ? static_cast<int>(p.fft_size / 2.0 * ratio) : nb;
-  const double inv_ratio = 1.0 / ratio;               // (the guess only: the knots decide)
-  for (int j = tid; j < nb; j += nt) {
-    const int q = j < m ? j : m - 1;
-    const double xi = static_cast<double>(q) / p.fft_size * p.fs;
-    const double g = q * inv_ratio;
-    int c = g >= nb - 1 ? nb - 1 : static_cast<int>(g);   // the last knot <= xi: a guess ...
-    while (c < nb - 1 && kx[c + 1] <= xi) ++c;
-    while (c > 0 && kx[c] > xi) --c;                      // ... corrected (x[0] = 0 <= xi always)
-    const int k = c + 1 < nb - 1 ? c + 1 : nb - 1;
-    const double s = (xi - kx[k - 1]) / (kx[k] - kx[k - 1]);
-    out[j] = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
+  if (s.blend)
+    warp_sp_row([&](int i) { return (1.0 - w) * a[i] + w * b[i]; }, out, ratio, p.m.fft_size, p.m.fs, lds);
+  else
+    warp_sp_row([&](int i) { return a[i]; }, out, ratio, p.m.fft_size, p.m.fs, lds);
+}
+
+__global__ void __launch_bounds__(256) modify_frames_ap(ModifyFramesParams p) {
+  const int j = blockIdx.x, u = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  const int nb = p.m.fft_size / 2 + 1;
+  const size_t at = (size_t)u * p.o_stride + j;                                   // (in bounds: see modify_frames_sp)
+  const SourcePosition s = source_position(p.time_map, at, j, p.m.n_frames[u]);
+  const double g = p.ap_gain ? valid_scale(p.ap_gain[at]) : 1.0;
+  if (j >= p.n_out[u]) return;
+  const double *a = p.ap_in + ((size_t)u * p.m.f_stride + s.k) * nb;
+  const double *b = p.ap_in + ((size_t)u * p.m.f_stride + s.k1) * nb;
+  double *out = p.ap_out + at * nb;
+  const double w = s.w;
+  if (!p.ap_gain && !s.blend && out == a) return;
+  for (int i = tid; i < nb; i += nt) {
+    double v = s.blend ? (1.0 - w) * a[i] + w * b[i] : a[i];
+    if (p.ap_gain) {                                  // GetSafeAperiodicity's bounds (common.cpp); NaN: the lower one
+      v *= g;
+      v = v > 0.001 ? v : 0.001;
+      v = v < 1.0 - kTiny ? v : 1.0 - kTiny;
+    }
+    out[i] = v;
   }
 }
 
@@ -225,6 +316,31 @@ __global__ void __launch_bounds__(256) modify_f0(ModifyParams p) {
   }
 }
 
+// The F0 of the output frames, from the source track p.f0_src (already through the log-F0 conversion where one is asked
+// for).  Between two frames: both voiced, the blend; one voiced, that frame's F0 while its weight is above 0.5, else 0 --
+// the reference's interpolated_vuv > 0.5 (synthesis.cpp:301-308); none, 0.  Then the target, then the scale.
+__global__ void modify_frames_f0(ModifyFramesParams p) {
+  const int j = flat_thread_x(), u = blockIdx.y;
+  if (j >= p.n_out[u]) return;
+  const size_t at = (size_t)u * p.o_stride + j;
+  const SourcePosition s = source_position(p.time_map, at, j, p.m.n_frames[u]);
+  const double *src = p.f0_src + (size_t)u * p.m.f_stride;
+  double v = src[s.k];
+  if (s.blend) {
+    const double v1 = src[s.k1], w = s.w;
+    const bool a = voiced_f0(v), b = voiced_f0(v1);
+    if (a && b) v = (1.0 - w) * v + w * v1;
+    else if (a) v = 1.0 - w > 0.5 ? v : 0.0;
+    else if (b) v = w > 0.5 ? v1 : 0.0;
+    else v = 0.0;
+  }
+  if (p.f0_target && voiced_f0(v)) {
+    const double t = p.f0_target[at];
+    if (voiced_f0(t)) v = t;
+  }
+  p.m.f0_out[at] = v * (p.f0_scale ? valid_scale(p.f0_scale[at]) : p.m.f0_scale[u]);
+}
+
 size_t modify_warp_lds_bytes(int fft_size) { return 2 * sizeof(double) * (fft_size / 2 + 1); }
 
 void launch_modify_warp_sp(const ModifyParams &p, int max_frames, hipStream_t stream) {
@@ -232,6 +348,15 @@ void launch_modify_warp_sp(const ModifyParams &p, int max_frames, hipStream_t st
 }
 void launch_modify_f0(const ModifyParams &p, hipStream_t stream) {
   WH_BLOCKS(modify_f0, dim3(p.n_utt), 256, sizeof(double) * 128, stream, p);
+}
+void launch_modify_frames_sp(const ModifyFramesParams &p, int max_out, hipStream_t stream) {
+  WH_BLOCKS(modify_frames_sp, dim3(max_out, p.m.n_utt), 256, modify_warp_lds_bytes(p.m.fft_size), stream, p);
+}
+void launch_modify_frames_ap(const ModifyFramesParams &p, int max_out, hipStream_t stream) {
+  WH_BLOCKS(modify_frames_ap, dim3(max_out, p.m.n_utt), 256, 0, stream, p);
+}
+void launch_modify_frames_f0(const ModifyFramesParams &p, int max_out, hipStream_t stream) {
+  WH_THREADS(modify_frames_f0, max_out, p.m.n_utt, 1, stream, p);
 }
 
 void launch_code_spectral_envelope(const CodecParams &p, hipStream_t stream) {

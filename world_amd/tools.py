@@ -7,6 +7,7 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools analysis a.wav b.wav ... --outdir params      # -> params/a.f0 a.sp a.ap ...
     python -m world_amd.tools synthesis params/a.f0 params/a.sp params/a.ap -o a_resynth.wav
     python -m world_amd.tools transform a.wav b.wav ... --outdir out --f0-scale 1.5 --formant-shift 1.2
+    python -m world_amd.tools transform a.wav --outdir out --duration 2.5 --f0-from melody.f0
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -14,7 +15,8 @@ are uploaded (decoded on the device), and with --code-sp / --code-ap the envelop
 the device before they come back, so the D2H traffic and the files shrink by 10-17x.
 `transform` is the reference test program's analysis -> ParameterModification -> Synthesis (F0 scale, formant shift,
 and a speed change through the synthesis frame period) in one library call per batch; the waveforms are quantised to
-16 bits on the device, so only int16 samples come back.
+16 bits on the device, so only int16 samples come back.  With --duration or --f0-from the modification is per frame
+(world_hip_resynthesize_frames_batch): a uniform time map to the asked length, and the F0 track of another file as target.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -23,7 +25,7 @@ import sys
 
 import numpy as np
 
-from .api import FileAPI, WorldHip, cheaptrick_fft_size
+from .api import FileAPI, WorldHip, cheaptrick_fft_size, frame_count, uniform_time_map
 
 
 def _analysis(a):
@@ -119,6 +121,15 @@ def _transform(a):
         outs = transform_outputs(a.wav, a.outdir)
     except ValueError as e:
         sys.exit(f"transform: {e}")
+    frames = a.duration is not None or a.f0_from is not None    # the per-frame route; without them, exactly as before
+    if a.duration is not None and not a.duration * 1000.0 / a.s >= 1.0:
+        sys.exit(f"transform: --duration {a.duration} is shorter than one frame shift")
+    track = None
+    if a.f0_from is not None:
+        read = FileAPI().read_f0(a.f0_from)
+        if read is None or len(read[1]) < 1:
+            sys.exit(f"transform: {a.f0_from} is not a readable F0 file")
+        track = read[1]
     wh = WorldHip()
     os.makedirs(a.outdir, exist_ok=True)
     out_of = dict(zip(a.wav, outs))
@@ -130,8 +141,11 @@ def _transform(a):
         for at in range(0, len(group), a.batch):
             chunk = group[at:at + a.batch]
             x, x_len = _load_batch(wh, chunk)
-            y, y_len = wh.resynthesize(x, fs, x_len=x_len, f0_scale=a.f0_scale, formant_shift=a.formant_shift,
-                                       time_scale=a.time_scale, frame_period=a.s, f0_floor=a.f, f0_ceil=a.c)
+            if frames:
+                y, y_len = _resynthesize_frames(wh, a, x, fs, x_len, track)
+            else:
+                y, y_len = wh.resynthesize(x, fs, x_len=x_len, f0_scale=a.f0_scale, formant_shift=a.formant_shift,
+                                           time_scale=a.time_scale, frame_period=a.s, f0_floor=a.f, f0_ceil=a.c)
             q = wh.double_to_pcm16(y).cpu().numpy()              # quantised on the device: int16 crosses PCIe
             for row, path in enumerate(chunk):
                 n, name = int(y_len[row]), out_of[path]
@@ -140,6 +154,33 @@ def _transform(a):
                     sys.exit(f"transform: {name} cannot be written")
                 samples += n
     print(f"{len(a.wav)} file(s), {samples} samples -> {a.outdir}")
+
+
+def _resynthesize_frames(wh, a, x, fs, x_len, track):
+    """--duration / --f0-from: every utterance spread over its output frames by a uniform time map (--duration seconds, or
+    its own length times --time-scale), the F0 file's track spread over the same frames as the target F0"""
+    import torch
+    n_src = [frame_count(fs, int(n), a.s) for n in x_len]
+    if a.duration is not None:
+        n_out = [int(a.duration * 1000.0 / a.s) + 1] * len(n_src)
+    else:
+        n_out = [max(int((n - 1) * a.time_scale) + 1, 2) for n in n_src]
+    O = max(n_out)
+    time_map = torch.zeros((len(n_src), O), dtype=torch.float64, device=wh.device)
+    for row, (n, m) in enumerate(zip(n_src, n_out)):
+        time_map[row, :m] = uniform_time_map(n, m, device=wh.device)
+    f0_target = None
+    if track is not None:
+        src = torch.from_numpy(np.ascontiguousarray(track, dtype=np.float64)).to(wh.device)[None].contiguous()
+        f0_target = torch.zeros_like(time_map)
+        for m in sorted(set(n_out)):                              # (the track between two of its frames: modify_frames' F0 rules)
+            spread = wh.modify_frames(src, None, None, [len(track)], fs, cheaptrick_fft_size(fs, 71.0),
+                                      time_map=uniform_time_map(len(track), m, device=wh.device))[0][0]
+            for row in (r for r, k in enumerate(n_out) if k == m):
+                f0_target[row, :m] = spread
+    return wh.resynthesize_frames(x, fs, x_len=x_len, n_out=n_out, time_map=time_map, f0_target=f0_target,
+                                  f0_scale=a.f0_scale, formant_shift=a.formant_shift, frame_period=a.s, f0_floor=a.f,
+                                  f0_ceil=a.c)
 
 
 def main(argv=None):
@@ -171,6 +212,10 @@ def main(argv=None):
     tr.add_argument("--f0-scale", type=float, default=1.0, help="F0 multiplier (test.cpp's third argument)")
     tr.add_argument("--formant-shift", type=float, default=1.0, help="spectral envelope stretch (test.cpp's fourth argument)")
     tr.add_argument("--time-scale", type=float, default=1.0, help="duration multiplier (synthesis frame period * T)")
+    tr.add_argument("--duration", type=float, default=None, metavar="SECONDS",
+                    help="every output lasts SECONDS: the frames are spread by a uniform time map (replaces --time-scale)")
+    tr.add_argument("--f0-from", default=None, metavar="FILE.f0",
+                    help="voiced frames take their F0 from this F0 file's track, spread over the output frames")
     tr.add_argument("-f", type=float, default=71.0, help="floor of the F0 range (Hz)")
     tr.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
     tr.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
