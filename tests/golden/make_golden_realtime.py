@@ -75,6 +75,20 @@ def cases():
     out["refresh_midstream"] = dict(fs=16000, frame_period=5.0, fft_size=1024, buffer_size=80, number_of_pointers=5,
                                     f0=np.concatenate([fa[:25], fb]), sp=np.concatenate([sa[:25], sb]),
                                     ap=np.concatenate([aa[:25], ab]), chunks=[5] * 5 + [4] * 10, refresh_before=5)
+    # 7., 8. fft_size off the rate's default (tests/test_gpu_offdefault_fft.py).  The real-time reference has no lowest_f0:
+    # every non-zero frame is voiced, so the pulse spacing fs / f0 must itself stay within fft_size, and a voiced stretch
+    # starts and ends at twice that or more (F0 is interpolated towards 0 at its boundaries).
+    f0, sp, ap = (v[12:] for v in synth_params(16000, 32, 4096, seed=6))          # 15 voiced frames, 5 unvoiced
+    out["fs16k_fft4096"] = dict(fs=16000, frame_period=5.0, fft_size=4096, buffer_size=96, number_of_pointers=4,
+                                f0=f0, sp=sp, ap=ap, chunks=[4, 1, 7, 3, 5])
+    # 48 kHz / 512: Synthesis' lowest_f0 would be 48000 / 512 + 1 = 94 Hz; frames at 93.9 and 93.8 Hz lie below it and
+    # still space their pulses 512 samples apart (fs / fft_size = 93.75 Hz), frames at 96 Hz and up lie above
+    _, sp, ap = synth_params(48000, 20, 512, seed=7)
+    f0 = np.array([0.0, 0.0, 220.0, 180.0, 150.0, 110.0, 96.0, 93.9, 93.9, 96.0, 120.0, 93.8, 100.0, 160.0, 220.0, 0.0, 0.0,
+                   200.0, 0.0, 0.0])
+    ap = np.where((f0 == 0.0)[:, None], 1.0 - 1e-12, np.minimum(ap, 1.0 - 1e-6))
+    out["fs48k_fft512"] = dict(fs=48000, frame_period=5.0, fft_size=512, buffer_size=200, number_of_pointers=5,
+                               f0=f0, sp=sp, ap=ap, chunks=[2, 5, 1, 6, 3, 3])
     return out
 
 

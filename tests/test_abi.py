@@ -167,6 +167,15 @@ def test_shape_limits_are_answered_on_the_host():
     assert lib.world_hip_check_shape(200000, 8192, why, 256) == 1 and b"D4C" in why.value and b"192 kHz" in why.value
     assert lib.world_hip_check_shape(8000, 512, why, 256) == 1 and b"15.8" in why.value
     assert lib.world_hip_check_shape(96000, 4096, why, 256) == 0
+    # the pair (fs, fft_size): an unvoiced frame's 500 Hz window, 2 round(1.5 fs / 500) + 1 samples, and the unvoiced pulse
+    # spacing, fs / 500 + 1, must fit fft_size (the reference writes past its fft_size-long buffers otherwise)
+    for fs, fft, smallest in ((48000, 256, 512), (192000, 1024, 2048), (44100, 256, 512), (96000, 128, 1024)):
+        assert lib.world_hip_check_shape(fs, fft, why, 256) == 1, (fs, fft)
+        assert b"CheapTrick" in why.value and b"smallest fft_size for this fs is %d" % smallest in why.value, why.value
+    for fs, fft in ((48000, 512), (192000, 2048), (16000, 128), (16000, 256), (16000, 8192), (22050, 4096), (44100, 512)):
+        assert lib.world_hip_check_shape(fs, fft, why, 256) == 0 and why.value == b"", (fs, fft, why.value)
+    assert lib.world_hip_check_shape(42499, 256, why, 256) == 0      # a 255-sample window
+    assert lib.world_hip_check_shape(42500, 256, why, 256) == 1      # 2 * 128 + 1 = 257
 
 
 def test_abi_version_and_hint_are_exported_and_consistent(lib_path):

@@ -7,6 +7,7 @@
 2. The accuracy criterion of tests/util.py (e_H against W, bounded by e_R against W) on the emulated kernel units that
    tests/emu compiles as the GPU does (D4C, StoneMask, Synthesis), at 16 and 48 kHz, so that the metric itself is
    exercised without a GPU.  tests/test_gpu_accuracy.py runs it on the MI355X at every dispatch branch.
+3. The same criterion with fft_size off the rate's default (CheapTrick on the classic emulation).
 """
 import ctypes as C
 import os
@@ -15,7 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from util import ACC_A, ACC_C, ULP, assert_accurate, discrete_agreement, rel_errors
+from util import ACC_A, ACC_C, ULP, assert_accurate, ct_floor, discrete_agreement, rel_errors
+from util import offdefault_f0 as _f0, synth_inputs as _synth_inputs, utterance as _signal
 
 EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
 mpmath = pytest.importorskip("mpmath")
@@ -250,6 +252,56 @@ def test_emulated_units_against_wide_oracle(emu, ref_oracle, fs, f0_kind):
 
     y = {k: o.synthesis(f0, sp, ap["R"], fft, 5.0, fs, len(x)) for k, o in (("H", emu), ("R", ref_oracle), ("W", wide))}
     assert_accurate(f"emu synthesis {fs} {f0_kind}", y["H"][None], y["R"][None], y["W"][None], peak=True)
+
+
+# ---- fft_size off the rate's default (tests/test_gpu_offdefault_fft.py runs every template on the MI355X) ----
+@pytest.mark.parametrize("fs,fft,kinds", [(16000, 128, ("harvest", "floor_edge")), (16000, 2048, ("harvest", "floor_edge"))])
+def test_emulated_cheaptrick_off_default(emu, ref_oracle, wide, fs, fft, kinds):
+    x = _signal(fs, 0.2)
+    for kind in kinds:
+        tp, f0 = _f0(kind, ref_oracle, x, fs, fft)
+        if kind == "floor_edge":
+            assert np.any(f0 <= ct_floor(fs, fft)) and np.any(f0 > ct_floor(fs, fft))
+        h, r, w = (o.cheaptrick(x, fs, tp, f0, fft_size=fft) for o in (emu, ref_oracle, wide))
+        assert_accurate(f"emu cheaptrick off-default {fs}/{fft} {kind}", h, r, w)
+
+
+@pytest.mark.parametrize("threshold", [0.85, 0.0])
+@pytest.mark.parametrize("fs,fft", [(16000, 128), (16000, 4096)])
+def test_emulated_d4c_off_default(emu, ref_oracle, wide, fs, fft, threshold):
+    x = _signal(fs, 0.2)
+    tp, f0 = ref_oracle.harvest(x, fs)
+    ap = {k: o.d4c(x, fs, tp, f0, fft, threshold=threshold) for k, o in (("H", emu), ("R", ref_oracle), ("W", wide))}
+    w_only = discrete_agreement(f"d4c exits {fs}/{fft} {threshold}", *(d4c_exit_rows(ap[k]) for k in "HRW"))
+    assert_accurate(f"emu d4c off-default {fs}/{fft} th={threshold}", ap["H"], ap["R"], ap["W"], exclude_rows=w_only)
+
+
+def test_emulated_d4c_grids_nest_bit_for_bit(emu, ref_oracle, wide):
+    """bin i of the fft_size N grid and bin 2 i of the 2 N grid are the same double i fs / N: ap_2N[:, ::2] == ap_N; and the
+    cached grid follows fs at one fft_size"""
+    fs = 16000
+    x = _signal(fs, 0.2)
+    tp, f0 = ref_oracle.harvest(x, fs)
+    ap = {}
+    for fft in (512, 1024, 2048, 512):
+        got = emu.d4c(x, fs, tp, f0, fft)
+        assert fft not in ap or np.array_equal(got, ap[fft])
+        ap[fft] = got
+    assert not np.all(d4c_exit_rows(ap[512]))
+    assert np.array_equal(ap[1024][:, ::2], ap[512]) and np.array_equal(ap[2048][:, ::2], ap[1024])
+    x2 = _signal(24000, 0.12)
+    tp2, f02 = ref_oracle.harvest(x2, 24000)
+    h, r, w = (o.d4c(x2, 24000, tp2, f02, 512) for o in (emu, ref_oracle, wide))       # the size of the last call, another rate
+    w_only = discrete_agreement("d4c exits 24000/512", *(d4c_exit_rows(v) for v in (h, r, w)))
+    assert_accurate("emu d4c off-default 24000/512 after 16000/512", h, r, w, exclude_rows=w_only)
+    assert np.array_equal(emu.d4c(x, fs, tp, f0, 512), ap[512])
+
+
+@pytest.mark.parametrize("fs,fft", [(16000, 256), (16000, 4096)])
+def test_emulated_synthesis_off_default(emu, ref_oracle, wide, fs, fft):
+    x, f0, sp, ap = _synth_inputs(ref_oracle, fs, fft, 0.2)        # (asserts voiced and default-F0 pulses)
+    y = {k: o.synthesis(f0, sp, ap, fft, 5.0, fs, len(x)) for k, o in (("H", emu), ("R", ref_oracle), ("W", wide))}
+    assert_accurate(f"emu synthesis off-default {fs}/{fft}", y["H"][None], y["R"][None], y["W"][None], peak=True)
 
 
 def test_criterion_catches_a_float_slip(ref_oracle):

@@ -168,6 +168,75 @@ def test_emulated_error_handler_receives_shape_refusals():
     _check_error_handler(_emu())
 
 
+# (fs, fft_size) pairs on both sides of the rule of DESIGN.md 7: the reference sizes its buffers by fft_size and fills
+# them by fs, so an unvoiced frame's 500 Hz window (CheapTrick) and the unvoiced pulse spacing (Synthesis, the real-time
+# synthesiser) must fit fft_size.  Refused pairs name the smallest fft_size that works.
+CT_REFUSED = [(48000, 256, 512), (192000, 1024, 2048), (44100, 256, 512)]
+CT_ACCEPTED = [(48000, 512), (16000, 128), (8000, 128)]
+SY_REFUSED = [(96000, 128, 256), (192000, 256, 512)]
+SY_ACCEPTED = [(96000, 256), (16000, 128)]
+
+
+def _check_pair_refusals(H):
+    """CheapTrick(), Synthesis() and InitializeSynthesizer() refuse the pairs the reference leaves undefined, through the
+    error handler and with the outputs untouched, and serve the pairs next to them"""
+    from world_amd.api import CheapTrickOption, WorldSynthesizer, _p, _rows
+    seen = []
+    cb = HANDLER(lambda fn, msg, user: seen.append((fn.decode(), msg.decode())))
+    H.lib.world_hip_set_error_handler.argtypes = [HANDLER, C.c_void_p]
+    H.lib.world_hip_set_error_handler(cb, None)
+    try:
+        nf = 8
+        tp = np.arange(nf) * 0.005
+        f0 = np.array([0.0, 0.0, 150.0, 160.0, 0.0, 170.0, 0.0, 0.0])
+        for fs, fft, smallest in CT_REFUSED:
+            x = _signal(fs, 0.04, 3)
+            opt = CheapTrickOption(); H.lib.InitializeCheapTrickOption(fs, C.byref(opt)); opt.fft_size = fft
+            sp = np.full((nf, fft // 2 + 1), -7.0)
+            del seen[:]
+            H.lib.CheapTrick(_p(x), len(x), fs, _p(tp), _p(f0), nf, C.byref(opt), _rows(sp))
+            assert len(seen) == 1 and seen[0][0] == "CheapTrick", (fs, fft, seen)
+            assert f"smallest fft_size for this fs is {smallest}" in seen[0][1], seen
+            assert np.all(sp == -7.0)
+        for fs, fft in CT_ACCEPTED:
+            x = _signal(fs, 0.04, 3)
+            del seen[:]
+            sp = H.cheaptrick(x, fs, tp, f0, fft_size=fft)
+            assert not seen and np.isfinite(sp).all() and np.all(sp > 0), (fs, fft, seen)
+        for fs, fft, smallest in SY_REFUSED:
+            nb = fft // 2 + 1
+            y = np.full(int(fs * 0.03), -7.0)
+            del seen[:]
+            H.lib.Synthesis(_p(f0), nf, _rows(np.full((nf, nb), 1e-4)), _rows(np.full((nf, nb), 0.5)), fft, 5.0, fs, len(y), _p(y))
+            assert len(seen) == 1 and seen[0][0] == "Synthesis", (fs, fft, seen)
+            assert f"smallest fft_size for this fs is {smallest}" in seen[0][1], seen
+            assert np.all(y == -7.0)
+            s = WorldSynthesizer()
+            H._rt().InitializeSynthesizer(fs, 5.0, fft, 64, 8, C.byref(s))
+            assert len(seen) == 2 and seen[1][0] == "InitializeSynthesizer" and f"is {smallest}" in seen[1][1], seen
+        for fs, fft in SY_ACCEPTED:
+            nb = fft // 2 + 1
+            del seen[:]
+            y = H.synthesis(f0, np.full((nf, nb), 1e-4), np.full((nf, nb), 0.5), fft, 5.0, fs, int(fs * 0.03))
+            assert not seen and np.isfinite(y).all() and np.any(y != 0.0), (fs, fft, seen)
+            s = H.initialize_synthesizer(fs, 5.0, fft, 64, 8)
+            assert not seen
+            H.destroy_synthesizer(s)
+    finally:
+        H.lib.world_hip_set_error_handler(HANDLER(0), None)
+    return cb
+
+
+def test_emulated_pairs_of_fs_and_fft_size_the_reference_leaves_undefined_are_refused():
+    H = _emu()
+    _check_pair_refusals(H)
+    H.lib.world_hip_check_shape.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
+    why = C.create_string_buffer(256)
+    for fs, fft, smallest in CT_REFUSED:
+        assert H.lib.world_hip_check_shape(fs, fft, why, 256) == 1 and str(smallest).encode() in why.value
+    assert H.lib.world_hip_check_shape(48000, 512, why, 256) == 0 and H.lib.world_hip_check_shape(16000, 128, why, 256) == 0
+
+
 def test_default_error_policy_prints_and_aborts():
     """no handler installed: the reason on stderr, then abort() -- never a silent CPU result"""
     _emu()
@@ -319,6 +388,12 @@ def test_separate_rows_match_dense_rows_on_the_gpu(ref_oracle):
 def test_error_handler_receives_shape_refusals_on_the_gpu():
     from world_amd.api import HostAPI
     _check_error_handler(HostAPI())
+
+
+@pytest.mark.gpu
+def test_pairs_of_fs_and_fft_size_the_reference_leaves_undefined_are_refused_on_the_gpu():
+    from world_amd.api import HostAPI
+    _check_pair_refusals(HostAPI())
 
 
 @pytest.mark.gpu

@@ -242,9 +242,9 @@ def check_padding(outs, no):
 
 
 # ---- the cases ----------------------------------------------------------------------------------------------------------
-def case_identity_map_and_constant_curves(be, fs):
+def case_identity_map_and_constant_curves(be, fs, fft=None):
     """1a: an identity map plus constant curves is world_hip_modify_batch with the same constants, bit for bit"""
-    fft = fft_of(fs)
+    fft = fft or fft_of(fs)                   # (an explicit fft_size: off the rate's default)
     nf = np.array([9, 3, 7, 1, 6], dtype=np.int32)
     ratios, scales = [0.8, 1.25, 0.87, 2.0, 1.0], [1.5, 0.7, 1.0, 2.0, 1.2]
     f0, sp, ap = ragged(fs, fft, nf, seed=fs // 1000)
@@ -324,10 +324,10 @@ def case_blend_only(be, fs):
     assert np.all(g_f0[2, :5] == f0[2, 0]) or np.isnan(f0[2, 0])
 
 
-def case_blend_and_per_frame_warp(be, fs):
+def case_blend_and_per_frame_warp(be, fs, fft=None):
     """3: a fractional map and a formant ratio per frame: 1e-13 against the statement; the top-bin fill of r < 1 and the
     rows with r == 1 exact"""
-    fft = fft_of(fs)
+    fft = fft or fft_of(fs)                   # (an explicit fft_size: off the rate's default)
     nb = fft // 2 + 1
     nf = np.array([7, 4], dtype=np.int32)
     _, sp, _ = ragged(fs, fft, nf, seed=33)
@@ -426,6 +426,22 @@ def test_blend_and_per_frame_warp(be, fs):
     case_blend_and_per_frame_warp(be, fs)
 
 
+# fft_size off the rate's default: the smallest transform at 16 kHz, the largest at 48 kHz (fft_of gives 1024 and 2048)
+OFF_DEFAULT = [(16000, 128), (48000, 8192)]
+
+
+@pytest.mark.parametrize("fs,fft", OFF_DEFAULT)
+def test_identity_map_and_constant_curves_off_default_fft(be, fs, fft):
+    assert fft != fft_of(fs)
+    case_identity_map_and_constant_curves(be, fs, fft)
+
+
+@pytest.mark.parametrize("fs,fft", OFF_DEFAULT)
+def test_blend_and_per_frame_warp_off_default_fft(be, fs, fft):
+    assert fft != fft_of(fs)
+    case_blend_and_per_frame_warp(be, fs, fft)
+
+
 def test_padding_refusals_and_invalid_curve_values(be):
     case_padding_and_refusals(be, 16000)
 
@@ -504,7 +520,7 @@ def test_resynthesize_frames_equals_the_separate_calls(lib, be):
     ip = lambda a: a.ctypes.data_as(_ip)
     vp = lambda a: C.c_void_p(a.ctypes.data)
 
-    def one_call(y, n_out=no, y_len=yl, curves=cv):
+    def one_call(y, n_out=no, y_len=yl, curves=cv, fs=fs, copt=copt):
         return lib.world_hip_resynthesize_frames_batch(be.ctx, 2, fs, vp(x), x.shape[1], ip(xl), C.byref(hopt), C.byref(copt),
                                                        C.byref(dopt), mods, curves, ip(n_out), O, ip(y_len), Y, vp(y))
     y = np.zeros((2, Y))
@@ -524,6 +540,13 @@ def test_resynthesize_frames_equals_the_separate_calls(lib, be):
                dict(n_out=np.array([O + 1, no[1]], dtype=np.int32)), dict(curves=None)):    # (no map: n_out != n_frames)
         assert one_call(canary, **kw) != 0 and be.error(), kw
         assert np.all(canary == 3.0), kw
+    # a pair (fs, fft_size) the reference leaves undefined is refused by the chain too, before any work ...
+    assert one_call(canary, fs=48000, copt=CheapTrickOption(-0.15, 71.0, 256)) != 0
+    assert "smallest fft_size for this fs is 512" in be.error() and np.all(canary == 3.0)
+    # ... and an fft_size off the rate's default is served
+    y3 = np.zeros((2, Y))
+    assert one_call(y3, copt=CheapTrickOption(-0.15, 71.0, 256)) == 0, be.error()
+    assert np.isfinite(y3).all() and np.max(np.abs(y3)) > 0 and not np.array_equal(y3, y)
 
 
 # ---- the Python helpers (no library needed) ------------------------------------------------------------------------------

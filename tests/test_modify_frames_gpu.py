@@ -73,6 +73,16 @@ def test_blend_and_per_frame_warp(be, fs):
     cpu.case_blend_and_per_frame_warp(be, fs)
 
 
+@pytest.mark.parametrize("fs,fft", cpu.OFF_DEFAULT)
+def test_identity_map_and_constant_curves_off_default_fft(be, fs, fft):
+    cpu.case_identity_map_and_constant_curves(be, fs, fft)
+
+
+@pytest.mark.parametrize("fs,fft", cpu.OFF_DEFAULT)
+def test_blend_and_per_frame_warp_off_default_fft(be, fs, fft):
+    cpu.case_blend_and_per_frame_warp(be, fs, fft)
+
+
 @pytest.mark.parametrize("fs", RATES)
 def test_padding_refusals_and_invalid_curve_values(be, fs):
     cpu.case_padding_and_refusals(be, fs)

@@ -221,3 +221,87 @@ def assert_f0_tight(what, h, r, rtol=1e-10):
     _log_accuracy(what, np.quantile(e, ACC_QUANTILES), np.zeros(3), 0, int(v.sum()))
     i = int(np.argmax(e))
     assert e[i] <= rtol, f"{what}: F0 rel err {e[i]:.3e} at frame {int(np.flatnonzero(v)[i])} (H {h[v][i]!r}, R {r[v][i]!r})"
+
+
+# ---- fft_size off the rate's default (tests/test_gpu_offdefault_fft.py, tests/test_accuracy_cpu.py): signals, F0 tracks ----
+def utterance(fs, seconds, index=2):
+    from world_amd import synth
+    return synth.utterance(index, fs, seconds).numpy()
+
+
+def offdefault_seconds(fs):
+    return 0.2 if fs < 100000 else 0.12
+
+
+def ct_floor(fs, fft):
+    return 3.0 * fs / (fft - 3.0)
+
+
+def offdefault_track(kind, fs, fft, nf, seed):
+    """caller-made F0 tracks as in tests/test_gpu_accuracy.py, and `floor_edge`: frames alternating between just below the
+    floor 3 fs / (fft - 3) (analysed at the 500 Hz default), just above it (the longest window fft_size admits) and 1 %
+    above, so that the default-F0 switch falls between adjacent frames"""
+    rng = np.random.default_rng(seed)
+    if kind == "floor_edge":
+        floor = ct_floor(fs, fft)
+        return np.resize([floor * (1 - 1e-12), floor * (1 + 1e-12), floor * 1.01], nf).astype(np.float64)
+    if kind == "steps":
+        f0 = np.repeat(rng.uniform(60.0, 600.0, nf // 7 + 1), 7)[:nf]
+    elif kind == "low":
+        f0 = rng.uniform(20.0, 90.0, nf)
+    else:                                                              # "nyquist"
+        f0 = rng.uniform(0.3 * fs, 0.4999 * fs, nf)
+    f0[rng.random(nf) < 0.15] = 0.0
+    return f0
+
+
+def offdefault_f0(kind, ref, x, fs, fft):
+    tp, f0 = ref.harvest(x, fs)
+    return tp, (f0 if kind == "harvest" else offdefault_track(kind, fs, fft, len(tp), fs + fft + len(kind)))
+
+
+def lowest_f0(fs, fft):
+    return fs // fft + 1.0                                             # integer division (synthesis.cpp:361)
+
+
+def synth_track(fs, fft, nf):
+    """Frames on both sides of lowest_f0.  Below it (0.9 L) a frame is unvoiced by Synthesis' own rule.  `mid` lies between
+    the integer-division L and fs / fft + 1 computed in floating point (voiced only under the reference's rule), on frames
+    whose neighbours are voiced, so that every pulse spacing stays below fft_size: at a voiced / unvoiced boundary the
+    reference interpolates F0 towards 0 and keeps the samples above half the voiced value, hence boundary frames at >= 2.5 L.
+    High boundary and shoulder values also give voiced pulses within a short signal when L is a few Hz."""
+    L, Lf = lowest_f0(fs, fft), fs / fft + 1.0
+    mid = (L + Lf) / 2.0 if Lf > L else L * 1.003
+    assert L <= mid and fs / mid < fft
+    B, M = max(2.5 * L, 140.0), max(1.6 * L, 100.0)
+    f0 = np.resize([0.9 * L, 0.9 * L, B, M, mid, mid, M, B, 0.0, 0.0], nf).astype(np.float64)
+    f0[-3:] = 0.0
+    return f0
+
+
+def pulse_kinds(f0, fs, fft, n, frame_period=0.005):
+    """(voiced pulses, default-F0 pulses) of the reference's time base (synthesis.cpp:224-321), in plain numpy"""
+    L = lowest_f0(fs, fft)
+    cf0 = np.where(f0 < L, 0.0, f0)
+    cf0 = np.append(cf0, 2 * cf0[-1] - cf0[-2])
+    vuv = (cf0 != 0).astype(np.float64)
+    vuv[-1] = 2 * vuv[-2] - vuv[-3]
+    t, ct = np.arange(n) / fs, np.arange(len(cf0)) * frame_period
+    iv = np.interp(t, ct, vuv) > 0.5
+    if0 = np.where(iv, np.interp(t, ct, cf0), 500.0)
+    wrap = np.fmod(np.cumsum(2 * np.pi * if0 / fs), 2 * np.pi)
+    at = np.flatnonzero(np.abs(np.diff(wrap)) > np.pi)
+    gaps = np.diff(at)
+    assert gaps.size and gaps.max() <= fft, "the case leaves the reference's noise buffer"
+    return int(iv[at].sum()), int((~iv[at]).sum())
+
+
+def synth_inputs(ref, fs, fft, seconds, index=2):
+    x = utterance(fs, seconds, index)
+    tp, _ = ref.harvest(x, fs)
+    f0 = synth_track(fs, fft, len(tp))
+    voiced, default = pulse_kinds(f0, fs, fft, len(x))
+    assert voiced > 0 and default > 0, (voiced, default)
+    sp = ref.cheaptrick(x, fs, tp, f0, fft_size=fft)
+    ap = ref.d4c(x, fs, tp, f0, fft)
+    return x, f0, sp, ap

@@ -1110,12 +1110,12 @@ class WorldHip:
         return Graph(self, ctx, g)
 
     def analyze_packed(self, x, fs, block, first_row=0, x_len=None, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0,
-                       q1=-0.15, threshold=0.85):
+                       q1=-0.15, threshold=0.85, fft_size=None):
         """Harvest -> CheapTrick -> D4C of one batch written straight into packed records (no dense sp / ap, no pack
         pass): utterance u's n_frames[u] records start at block[first_row + sum(n_frames[:u])].  Returns n_frames."""
         t = self.torch
         B, L, xl = self._prep(x, x_len)
-        fft_size = cheaptrick_fft_size(fs, 71.0)
+        fft_size = fft_size or cheaptrick_fft_size(fs, 71.0)
         nb = fft_size // 2 + 1
         nf = [frame_count(fs, int(n), frame_period) for n in xl]
         cols = block.shape[-1]                       # 2 + 2 nb: f64 records; 2 + nb: the spectra as float32 (narrow wire)
@@ -1128,13 +1128,13 @@ class WorldHip:
         return nf
 
     def analyze_coded(self, x, fs, block, first_row=0, x_len=None, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0,
-                      q1=-0.15, threshold=0.85, number_of_dimensions=60):
+                      q1=-0.15, threshold=0.85, number_of_dimensions=60, fft_size=None):
         """Harvest -> CheapTrick -> D4C of one batch written as CODED records [tpos, f0, mel-cepstrum[D], band
         aperiodicity[nap]] (include/world_hip.h: world_hip_analyze_coded -- the reference's CodeSpectralEnvelope /
         CodeAperiodicity of the analysis, 31 x fewer bytes per frame at 48 kHz).  Returns n_frames."""
         t = self.torch
         B, L, xl = self._prep(x, x_len)
-        fft_size = cheaptrick_fft_size(fs, 71.0)
+        fft_size = fft_size or cheaptrick_fft_size(fs, 71.0)
         nf = [frame_count(fs, int(n), frame_period) for n in xl]
         cols = block.shape[-1]
         assert block.dtype == t.float64 and block.is_contiguous() and block.device == x.device
@@ -1309,8 +1309,9 @@ class WorldHip:
         return {k: round(float(x), 2) for k, x in zip(keys, v)}
 
     def analyze(self, x, fs, x_len=None, f0_method="harvest", frame_period=5.0, f0_floor=71.0, f0_ceil=800.0,
-                q1=-0.15, threshold=0.85, sp_out=None, ap_out=None, tpos_out=None, f0_out=None):
+                q1=-0.15, threshold=0.85, sp_out=None, ap_out=None, tpos_out=None, f0_out=None, fft_size=None):
         """The north-star pipeline: F0 (Harvest, or DIO+StoneMask) -> CheapTrick -> D4C.
+        fft_size: CheapTrick's transform and both matrices' bins (default: the natural size of fs at a 71 Hz floor).
         sp_out / ap_out / tpos_out / f0_out (Harvest route): caller-owned result buffers of the right shape, reused from
         call to call -- the library writes every frame below an utterance's count and nothing else, so what lies beyond
         (the padding of a ragged batch) is the caller's."""
@@ -1318,7 +1319,7 @@ class WorldHip:
             # one library call: Harvest, then CheapTrick beside D4C on two streams of the context
             t = self.torch
             B, L, xl = self._prep(x, x_len)
-            fft_size = cheaptrick_fft_size(fs, 71.0)
+            fft_size = fft_size or cheaptrick_fft_size(fs, 71.0)
             nb = fft_size // 2 + 1
             nf = np.array([frame_count(fs, int(n), frame_period) for n in xl], dtype=np.int32)
             F = int(nf.max())
@@ -1342,7 +1343,7 @@ class WorldHip:
             f0 = self.stonemask(x, fs, tpos, f0_raw, nf, x_len)
         else:
             raise ValueError(f0_method)
-        fft_size = cheaptrick_fft_size(fs, 71.0)
+        fft_size = fft_size or cheaptrick_fft_size(fs, 71.0)
         sp = self.cheaptrick(x, fs, tpos, f0, nf, x_len, q1=q1, fft_size=fft_size, out=sp_out)
         ap = self.d4c(x, fs, tpos, f0, nf, fft_size, x_len, threshold=threshold, out=ap_out)
         return tpos, f0, sp, ap, nf

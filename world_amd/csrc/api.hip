@@ -440,13 +440,15 @@ static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c,
 // ---------------------------------------------------------------------------
 // CheapTrick
 // ---------------------------------------------------------------------------
+static std::string shape_limit(int what, int fs, int fft_size);       // below: "Shape limits of the GPU path"
 static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride,
                                  const int *x_length, const int *n_frames, int f_stride, const double *d_tpos,
                                  const double *d_f0, const CheapTrickOption *opt, double *d_sp, const RowLayout &lay,
                                  int *max_frames_out) {
   check_batch(n_utt, fs, d_x, x_stride, x_length);
   const int lg = ilog2_exact(opt->fft_size);
-  if (lg < 7 || lg > 13) fail("CheapTrick fft_size %d unsupported (128..8192: one frame must fit LDS)", opt->fft_size);
+  const std::string lim = shape_limit(2, fs, opt->fft_size);            // before any upload or launch
+  if (!lim.empty()) fail("%s", lim.c_str());
   const int max_frames = *max_frames_out = max_frame_count(n_frames, n_utt, f_stride);
   CtParams p;
   p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, n_frames, f_stride);
@@ -1067,7 +1069,8 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
   if (fs <= 0 || frame_period <= 0) fail("fs and frame_period must be positive");
   if (!d_f0 || !d_sp || !d_ap || !d_y || !n_frames || !y_length) fail("null buffer");
   const int lg = ilog2_exact(fft_size);
-  if (lg < 7 || lg > 13) fail("Synthesis: fft_size %d unsupported (128..8192: one pulse's transform must fit LDS)", fft_size);
+  const std::string lim = shape_limit(8, fs, fft_size);                 // before any upload or launch
+  if (!lim.empty()) fail("%s", lim.c_str());
   int max_y = 0;
   for (int u = 0; u < n_utt; ++u) {
     if (n_frames[u] < 2 || n_frames[u] > f_stride) fail("n_frames[%d]=%d outside [2, f_stride]", u, n_frames[u]);
@@ -1316,8 +1319,46 @@ static void run_spectral_packed_range(WorldHipContext *c, int n_utt, int fs, con
 // ---------------------------------------------------------------------------
 // Shape limits of the GPU path (the reference has none: it allocates whatever fs asks for).  One function states them,
 // the stages and world_hip_check_shape ask it, and the drop-in entries ask it BEFORE any upload or launch.
-// what: bit 0 StoneMask, bit 1 CheapTrick (needs fft_size), bit 2 D4C.  Returns nullptr or the reason.
+// what: bit 0 StoneMask, bit 1 CheapTrick (needs fft_size), bit 2 D4C, bit 3 Synthesis and the real-time synthesiser
+// (needs fft_size).  Returns an empty string or the reason.
+//
+// The pair (fs, fft_size).  The reference sizes its per-frame buffers by fft_size alone and fills them by fs:
+//  * CheapTrick analyses every frame at or below its floor 3 fs / (fft_size - 3) -- every unvoiced frame -- at the
+//    500 Hz default, with a window of 2 round(1.5 fs / 500) + 1 samples written into the fft_size-long waveform
+//    (cheaptrick.cpp:115-137, :218).  A voiced frame above the floor has a window of at most fft_size - 2.
+//  * Synthesis places the pulses of unvoiced stretches 500 Hz apart and fills noise_size = the distance to the next pulse
+//    samples of the fft_size-long waveform (synthesis.cpp:19-31, :307, :371; synthesisrealtime.cpp likewise).  The phase
+//    advances by 2 pi 500 / fs per sample, so two such pulses are floor(fs / 500) or one more samples apart (also where
+//    fs / 500 is whole: the accumulated phase reaches 2 pi only to rounding).
+// Beyond either the reference writes past its buffers; here the pair is refused.
 // ---------------------------------------------------------------------------
+static int ct_default_window(int fs) { return 2 * static_cast<int>(1.5 * fs / 500.0 + 0.5) + 1; }   // (matlab_round, positive)
+static int synth_default_spacing(int fs) { return fs / 500 + 1; }
+static int smallest_fft_for(int need) {
+  int n = 128;
+  while (n < need && n < (1 << 30)) n *= 2;
+  return n;
+}
+
+// a stage's fft_size: a power of two in 128..8192 (`why`) that holds the `need` samples the 500 Hz default asks for at fs
+// (`needs`: a format with one %d for that count)
+static std::string fft_size_limit(const char *stage, const char *why, int fs, int fft_size, int need, const char *needs) {
+  char msg[320], count[96];
+  int lg = 0;
+  while (lg < 30 && (1 << lg) < fft_size) ++lg;
+  if (fft_size < 1 || (1 << lg) != fft_size || lg < 7 || lg > 13) {
+    snprintf(msg, sizeof msg, "%s: fft_size %d unsupported (a power of two, 128..8192: %s)", stage, fft_size, why);
+    return msg;
+  }
+  if (need > fft_size) {
+    snprintf(count, sizeof count, needs, need);
+    snprintf(msg, sizeof msg, "%s: fft_size %d is too small for fs=%d: %s (the reference writes past its buffer there); the smallest fft_size for this fs is %d",
+             stage, fft_size, fs, count, smallest_fft_for(need));
+    return msg;
+  }
+  return std::string();
+}
+
 static std::string shape_limit(int what, int fs, int fft_size) {
   char msg[256];
   if (fs <= 0) return "fs must be positive";
@@ -1329,12 +1370,14 @@ static std::string shape_limit(int what, int fs, int fft_size) {
     }
   }
   if (what & 2) {
-    int lg = 0;
-    while ((1 << lg) < fft_size) ++lg;
-    if ((1 << lg) != fft_size || lg < 7 || lg > 13) {
-      snprintf(msg, sizeof msg, "CheapTrick: fft_size %d unsupported (a power of two, 128..8192: one frame must fit LDS; fs <= 192 kHz at the default f0 floor)", fft_size);
-      return msg;
-    }
+    const std::string r = fft_size_limit("CheapTrick", "one frame must fit LDS; fs <= 192 kHz at the default f0 floor", fs, fft_size,
+                                         ct_default_window(fs), "an unvoiced frame's 500 Hz window has %d samples");
+    if (!r.empty()) return r;
+  }
+  if (what & 8) {
+    const std::string r = fft_size_limit("Synthesis", "one pulse's transform must fit LDS", fs, fft_size,
+                                         synth_default_spacing(fs), "unvoiced pulses lie up to %d samples apart");
+    if (!r.empty()) return r;
   }
   if (what & 4) {
     const int fft_d4c = std::max(d4c_internal_fft(fs), static_cast<int>(pow(2.0, 1.0 + static_cast<int>(log(3.0 * fs / 40.0 + 1) / kLog2))));
@@ -1447,7 +1490,7 @@ static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double 
   if (!std::isfinite(time_scale) || !(time_scale > 0.0)) fail("resynthesize: time_scale %g must be finite and > 0", time_scale);
   if (!y_length || !d_y) fail("null buffer");
   const int fft_size = copt->fft_size;
-  const std::string lim = shape_limit(6, fs, fft_size);
+  const std::string lim = shape_limit(14, fs, fft_size);
   if (!lim.empty()) fail("%s", lim.c_str());
   check_modifications(mods, n_utt, fft_size);
   std::vector<int> nf(n_utt);
@@ -1574,7 +1617,7 @@ static void run_resynthesis_frames(WorldHipContext *c, int n_utt, int fs, const 
     fail("bad HarvestOption");
   if (!n_out || !y_length || !d_y) fail("null buffer");
   const int fft_size = copt->fft_size;
-  const std::string lim = shape_limit(6, fs, fft_size);
+  const std::string lim = shape_limit(14, fs, fft_size);
   if (!lim.empty()) fail("%s", lim.c_str());
   check_modifications(mods, n_utt, fft_size);
   const bool mapped = curves && curves->d_time_map;
@@ -1947,7 +1990,7 @@ int world_hip_graph_destroy(void *graph) {
 // 0: every stage of the analysis path supports (fs, cheaptrick_fft_size); 1: it does not, and why (<= cap bytes) says which
 // stage and limit.  Pure host arithmetic: callers (and the drop-in symbols) ask before any GPU work.
 int world_hip_check_shape(int fs, int cheaptrick_fft_size, char *why, int cap) {
-  const std::string r = shape_limit(7, fs, cheaptrick_fft_size);
+  const std::string r = shape_limit(15, fs, cheaptrick_fft_size);
   if (why && cap > 0) { snprintf(why, (size_t)cap, "%s", r.c_str()); }
   return r.empty() ? 0 : 1;
 }

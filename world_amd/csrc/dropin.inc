@@ -876,6 +876,7 @@ void Synthesis(const double *f0, int f0_length, const double *const *spectrogram
                int fft_size, double frame_period, int fs, int y_length, double *y) {
   using namespace world_hip;
   dropin_guard("Synthesis", [&] {
+    require_shape(8, fs, fft_size);
     DropinSlot &io = *tls_slot;
     WorldHipContext *c = io.ctx;
     const int nb = fft_size / 2 + 1;

@@ -604,11 +604,9 @@ static WorldHipRealtime *rt_create(WorldHipContext *c, int n_streams, int fs, do
   if (!(frame_period_ms > 0.0) || !std::isfinite(frame_period_ms)) fail("frame_period must be positive");
   if (buffer_size < 1) fail("buffer_size must be positive");
   if (number_of_pointers < 1) fail("number_of_pointers must be positive");
-  int lg = 0;
-  while ((1 << lg) < fft_size && lg < 30) ++lg;
-  if (fft_size < 1 || (1 << lg) != fft_size || lg < 7 || lg > 13)
-    fail("realtime synthesis: fft_size %d unsupported (a power of two, 128..8192: one pulse's transform must fit LDS)",
-         fft_size);
+  const std::string lim = shape_limit(8, fs, fft_size);                 // fft_size and the pair (fs, fft_size), before any allocation
+  if (!lim.empty()) fail("realtime synthesis: %s", lim.c_str());
+  const int lg = ilog2_exact(fft_size);
   WorldHipRealtime *rt = new WorldHipRealtime;
   try {
     rt->ctx = c;

@@ -116,13 +116,10 @@ void InitializeSynthesizer(int fs, double frame_period, int fft_size, int buffer
     WorldHipContext *c = nullptr;
     WorldHipRealtime *rt = nullptr;
     // the shape is checked before anything touches the GPU
-    int lg = 0;
-    while ((1 << lg) < fft_size && lg < 30) ++lg;
-    if (fft_size < 1 || (1 << lg) != fft_size || lg < 7 || lg > 13)
-      throw std::runtime_error("fft_size " + std::to_string(fft_size) +
-                               " unsupported (a power of two, 128..8192: one pulse's transform must fit LDS)");
     if (buffer_size < 1 || number_of_pointers < 1 || fs <= 0 || !(frame_period > 0.0))
       throw std::runtime_error("fs, frame_period, buffer_size and number_of_pointers must be positive");
+    const std::string lim = shape_limit(8, fs, fft_size);
+    if (!lim.empty()) throw std::runtime_error(lim);
     hipStream_t st = devrt::stream_create();
     c = world_hip_create(P.device, st);
     if (!c) {
