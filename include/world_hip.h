@@ -303,8 +303,8 @@ WORLD_HIP_API const char *world_hip_last_error(void);
  * header changes incompatibly; a binding built against another major value must refuse to bind (world_amd/api.py does).
  *   5  round 5: world_hip_spectral_packed_range / _cheaptrick_batch_range / _d4c_batch_range take `reuse_offsets`
  *   6  round 6: + world_hip_abi_version itself; no prototype changed.  Later additions keep 6: they add entry points and
- *      change no prototype (the world_hip_realtime_* calls, world_hip_modify_batch and its kin); bindings look for them
- *      by name.
+ *      change no prototype (the world_hip_realtime_* calls, world_hip_modify_batch and its kin, world_hip_synthesis_records
+ *      and world_hip_realtime_add_coded); bindings look for them by name.
  * Libraries older than 6 lack the symbol. */
 #define WORLD_HIP_ABI_VERSION 6
 /* Launch-geometry hints of a context (bits; default 0).  Results never depend on them.
@@ -367,6 +367,34 @@ WORLD_HIP_API int world_hip_synthesis_batch(WorldHipContext *ctx, int n_utt, int
                                             int fft_size, const int *n_frames, int f_stride, const double *d_f0,
                                             const double *d_spectrogram, const double *d_aperiodicity,
                                             const int *y_length, int y_stride, double *d_y);
+
+/* Synthesis straight from the records the analysis writes (world_hip_analyze_packed, world_hip_analyze_coded; also what the
+ * multi-GPU exchange moves and what a vocoder service is handed): no dense arrays, no unpack or decode call, no buffer of the
+ * caller's.  Layout: utterance u's n_frames[u] valid frames occupy rows first_row + sum_{v<u} n_frames[v] ... of d_block
+ * ([rows][cols] doubles, device); a record's tpos is not read.
+ *   wire 0  f64 records, cols = world_hip_record_columns(fft_size, 0).  Read in place by the pulse kernels: nothing is staged.
+ *   wire 1  f32 records, cols = world_hip_record_columns(fft_size, 1).  Widened to f64.
+ *   wire 2  coded records [tpos, f0, mel-cepstrum[number_of_dimensions], band aperiodicity], cols =
+ *           world_hip_coded_columns(fs, number_of_dimensions).  Decoded with the arithmetic of
+ *           world_hip_decode_spectral_envelope / world_hip_decode_aperiodicity (an aperiodic frame -- mean band value above
+ *           -0.5 dB -- gets the 1 - 1e-12 row), both rows in one launch.
+ * number_of_dimensions is ignored for wires 0 and 1.  Wires 1 and 2 stage each frame's rows once as dense f64 in the
+ * context's workspace (8 + 16 (fft_size/2+1) bytes per frame; world_hip_workspace_bytes counts them).  The waveform is, bit
+ * for bit, that of world_hip_unpack_results (wire 1: of the widened records) or the two decode calls followed by
+ * world_hip_synthesis_batch.  Refused before any GPU work, with a message: cols that do not match the wire, a null block,
+ * first_row < 0, n_frames[u] < 2, y_length[u] outside [1, y_stride], a pair (fs, fft_size) world_hip_check_shape refuses,
+ * and for wire 2 what the decoders refuse (number_of_dimensions outside [1, fft_size/4+1], fs without an aperiodicity
+ * band).  The (fs, fft_size) rule is world_hip_check_shape's whole rule -- the analysis stages' limits too, since records
+ * are what the analysis writes -- and so stricter than world_hip_synthesis_batch's own: a pair that only the synthesiser
+ * accepts (e.g. fs below what D4C takes) is refused here; unpack or decode such rows and use world_hip_synthesis_batch.
+ * Pulse capacity: exactly world_hip_synthesis_batch's (world_hip_set_synthesis_pulse_capacity,
+ * world_hip_synthesis_pulses_dropped, world_hip_sync).  Stream order as the other batched calls; after one eager call of
+ * the shape a call neither allocates nor copies from the host and can be captured (the row offsets are small per-call
+ * arrays like n_frames); a replay reads whatever the block holds then. */
+WORLD_HIP_API int world_hip_synthesis_records(WorldHipContext *ctx, int n_utt, int fs, double frame_period, int fft_size,
+                                              const int *n_frames, long long first_row, const double *d_block, int cols,
+                                              int wire, int number_of_dimensions, const int *y_length, int y_stride,
+                                              double *d_y);
 
 /* What box is this?  ~50 ms of microbenchmarks on the context's device (synchronous; allocates and frees 2 GB):
  * values[0] shader clock held under a chip-wide FP64 load (MHz), [1] that load's FMA rate over the whole launch (TFLOP/s; HIP events), [2] / [3] / [4]
@@ -656,6 +684,12 @@ WORLD_HIP_API int world_hip_resynthesize_frames_batch(WorldHipContext *ctx, int 
  *       rows row_stride doubles apart (fft_size / 2 + 1 used), e.g. records of world_hip_analyze_packed.  They are copied
  *       into the stream's frame store on the stream before the call returns, so the caller may reuse its buffers for
  *       later work on the same stream.  Returns 1 (added), 0 (the stream's ring is full), -1 (error: world_hip_last_error).
+ *   _add_coded: _add of one chunk whose rows are CODED: d_coded_sp (number_of_dimensions mel-cepstrum coefficients per row)
+ *       and d_coded_ap (GetNumberOfAperiodicities(fs) band values per row) are DEVICE rows row_stride doubles apart, so both
+ *       may point into the same coded records (columns 2 and 2 + number_of_dimensions of world_hip_analyze_coded's).  The
+ *       rows are decoded straight into the stream's frame store -- the decoders' arithmetic, no dense chunk in between --
+ *       so every later call behaves, bit for bit, as after _add of the rows the two decode calls return.  Refuses what the
+ *       decoders refuse; return values as _add.
  *   _synthesize: Synthesis2 for every stream at once: produced[s] (host) = its return value; d_out [n_streams][buffer_size]
  *       (device) gets each producing stream's buffer, zeros for the others.  When some streams need samples not yet
  *       rendered, their pulses that have a successor are rendered in batches of two kernels and one wait for the download:
@@ -672,6 +706,9 @@ WORLD_HIP_API int world_hip_realtime_create(WorldHipContext *ctx, int n_streams,
 WORLD_HIP_API void world_hip_realtime_destroy(WorldHipRealtime *rt);
 WORLD_HIP_API int world_hip_realtime_add(WorldHipRealtime *rt, int stream, const double *f0, int n_frames,
                                          const double *d_sp, const double *d_ap, int row_stride);
+WORLD_HIP_API int world_hip_realtime_add_coded(WorldHipRealtime *rt, int stream, const double *f0, int n_frames,
+                                               const double *d_coded_sp, int number_of_dimensions,
+                                               const double *d_coded_ap, int row_stride);
 WORLD_HIP_API int world_hip_realtime_synthesize(WorldHipRealtime *rt, double *d_out, int *produced);
 WORLD_HIP_API int world_hip_realtime_is_locked(WorldHipRealtime *rt, int stream);
 WORLD_HIP_API int world_hip_realtime_refresh(WorldHipRealtime *rt, int stream);

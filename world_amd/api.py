@@ -349,6 +349,10 @@ def load_library(path=LIB_PATH):
         lib.world_hip_resynthesize_frames_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                                             C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, cp, _ip,
                                                             C.c_int, _ip, C.c_int, vp]
+    if hasattr(lib, "world_hip_synthesis_records"):                  # (likewise)
+        lib.world_hip_synthesis_records.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_longlong, vp,
+                                                    C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp]
+        lib.world_hip_realtime_add_coded.argtypes = [vp, C.c_int, _dp, C.c_int, vp, C.c_int, vp, C.c_int]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -823,6 +827,43 @@ class WorldHip:
                     run()
                     if self.synthesis_pulses_dropped():
                         raise RuntimeError("synthesis: pulses dropped even at the requested capacity")
+                finally:
+                    self.set_synthesis_pulse_capacity(0)
+        return y
+
+    def synthesize_records(self, block, n_frames, fs, fft_size, frame_period, y_length, wire=0, number_of_dimensions=0,
+                           first_row=0, check_pulses=True):
+        """Synthesis() straight from the records analyze_packed / analyze_coded write (include/world_hip.h:
+        world_hip_synthesis_records): block [rows, cols] float64 on the device, utterance u's n_frames[u] records from row
+        first_row + sum(n_frames[:u]).  wire 0: f64 records, 1: f32 records, 2: coded records with number_of_dimensions
+        coefficients.  Returns y [B, max(y_length)]; check_pulses as synthesis()."""
+        t = self.torch
+        if not hasattr(self.lib, "world_hip_synthesis_records"):
+            raise RuntimeError("this libworld_hip.so has no synthesis from records (world_hip_synthesis_records)")
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32).reshape(-1)
+        B = len(nf)
+        yl = np.ascontiguousarray(np.broadcast_to(y_length, (B,)), dtype=np.int32)
+        Y = int(yl.max())
+        assert block.dtype == t.float64 and block.dim() == 2 and block.is_contiguous() and block.is_cuda
+        assert first_row >= 0 and first_row + int(nf.sum()) <= block.shape[0], "the block holds fewer records than n_frames asks for"
+        y = t.zeros((B, Y), dtype=t.float64, device=block.device)
+
+        def run():
+            self._check(self.lib.world_hip_synthesis_records(self._context(), B, int(fs), float(frame_period), int(fft_size),
+                                                             nf.ctypes.data_as(_ip), int(first_row), block.data_ptr(),
+                                                             int(block.shape[1]), int(wire), int(number_of_dimensions),
+                                                             yl.ctypes.data_as(_ip), Y, y.data_ptr()), "synthesize_records")
+        run()
+        if check_pulses:
+            need = self.synthesis_pulses_dropped()          # (synchronises) -- as synthesis(): one repeat at the asked capacity
+            if need:
+                if need > Y:
+                    raise RuntimeError(f"synthesize_records: {need} pitch pulses for {Y} output samples")
+                self.set_synthesis_pulse_capacity(need + 16)
+                try:
+                    run()
+                    if self.synthesis_pulses_dropped():
+                        raise RuntimeError("synthesize_records: pulses dropped even at the requested capacity")
                 finally:
                     self.set_synthesis_pulse_capacity(0)
         return y
@@ -1380,6 +1421,7 @@ class RealtimeStreams:
 
     add(stream, f0, sp, ap): one chunk; f0 host (numpy / list), sp / ap [frames, fft/2+1] float64 CUDA tensors (copied into
     the stream's frame store on the current stream); returns 1, or 0 when the stream's ring is full.
+    add_coded(stream, f0, coded_sp, coded_ap): the same for coded rows (mel-cepstrum / band aperiodicity), decoded on the way in.
     synthesize(): (out [n_streams, buffer_size] CUDA tensor, produced [n_streams] numpy bool) -- Synthesis2 of every stream.
     is_locked(stream), refresh(stream), close()."""
 
@@ -1406,6 +1448,22 @@ class RealtimeStreams:
         assert sp.shape[0] >= len(f0) and ap.shape[0] >= len(f0) and sp.stride(0) == ap.stride(0)
         return self._ok(self.lib.world_hip_realtime_add(self.h, int(stream), _p(f0), len(f0), C.c_void_p(sp.data_ptr()),
                                                         C.c_void_p(ap.data_ptr()), sp.stride(0)), "world_hip_realtime_add")
+
+    def add_coded(self, stream, f0, coded_sp, coded_ap):
+        """add() of one chunk whose rows are coded: coded_sp [frames, number_of_dimensions] and coded_ap [frames, bands]
+        float64 CUDA tensors with the same row stride (e.g. column slices of analyze_coded's records), decoded straight
+        into the stream's frame store (world_hip_realtime_add_coded)"""
+        t = self.torch
+        if not hasattr(self.lib, "world_hip_realtime_add_coded"):
+            raise RuntimeError("this libworld_hip.so has no world_hip_realtime_add_coded")
+        f0 = _f64(f0)
+        for a in (coded_sp, coded_ap):
+            assert a.dtype == t.float64 and a.is_cuda and a.dim() == 2 and a.stride(1) == 1 and a.shape[0] >= len(f0)
+        assert coded_sp.stride(0) == coded_ap.stride(0), "coded_sp and coded_ap rows must lie the same stride apart"
+        return self._ok(self.lib.world_hip_realtime_add_coded(self.h, int(stream), _p(f0), len(f0),
+                                                              C.c_void_p(coded_sp.data_ptr()), int(coded_sp.shape[1]),
+                                                              C.c_void_p(coded_ap.data_ptr()), coded_sp.stride(0)),
+                        "world_hip_realtime_add_coded")
 
     def synthesize(self):
         t = self.torch

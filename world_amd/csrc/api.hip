@@ -193,9 +193,9 @@ namespace world_hip {
 
 // Thrown by ensure_arena while a floor is held: the arena cannot move under the arrays kept there, so the call that holds
 // the floor grows it to `bytes` (floor included) with the floor released and starts over.  Invariant: a floor is set only
-// inside run_resynthesis's attempt loop, which catches this.  It is not a std::exception, so that no stage's own error
-// handling can swallow it; should it ever escape a call, guarded() turns it into an internal error instead of letting it
-// cross the C boundary.
+// inside an attempt loop that catches this (run_resynthesis, run_synthesis_records).  It is not a std::exception, so that
+// no stage's own error handling can swallow it; should it ever escape a call, guarded() turns it into an internal error
+// instead of letting it cross the C boundary.
 struct ArenaRegrow { size_t bytes; };
 
 static void ensure_arena(WorldHipContext *c, size_t bytes) {
@@ -1062,21 +1062,17 @@ static void run_codec(WorldHipContext *c, CodecOp op, int rows, int fs, int fft_
 // ---------------------------------------------------------------------------
 // Synthesis (reference src/synthesis.cpp:339-399)
 // ---------------------------------------------------------------------------
-static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size, const int *n_frames,
-                          int f_stride, const double *d_f0, const double *d_sp, const double *d_ap,
-                          const int *y_length, int y_stride, double *d_y) {
-  if (n_utt <= 0) fail("n_utt must be positive");
-  if (fs <= 0 || frame_period <= 0) fail("fs and frame_period must be positive");
-  if (!d_f0 || !d_sp || !d_ap || !d_y || !n_frames || !y_length) fail("null buffer");
+// Where the synthesiser finds its frames (SynthParams' row addressing, synthesis.h): the dense arrays of the batched
+// calls, a staging of the same kind, or f64 records read in place.
+struct SynthRows {
+  const double *f0, *sp, *ap;
+  std::vector<long long> first_row;   // [n_utt]
+  size_t row_stride, f0_stride;
+};
+// the synthesis stage itself; every argument has been checked (max_y = the largest y_length)
+static void synthesize_rows(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size, const int *n_frames,
+                            const SynthRows &rows, const int *y_length, int y_stride, int max_y, double *d_y) {
   const int lg = ilog2_exact(fft_size);
-  const std::string lim = shape_limit(8, fs, fft_size);                 // before any upload or launch
-  if (!lim.empty()) fail("%s", lim.c_str());
-  int max_y = 0;
-  for (int u = 0; u < n_utt; ++u) {
-    if (n_frames[u] < 2 || n_frames[u] > f_stride) fail("n_frames[%d]=%d outside [2, f_stride]", u, n_frames[u]);
-    if (y_length[u] < 1 || y_length[u] > y_stride) fail("y_length[%d]=%d outside [1, y_stride]", u, y_length[u]);
-    max_y = std::max(max_y, y_length[u]);
-  }
   if (c->dc_remover_len != fft_size) {                                 // GetDCRemover, synthesis.cpp:320-335
     std::vector<double> rem(fft_size);
     double dc = 0.0;
@@ -1095,7 +1091,8 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
   p.n_utt = n_utt; p.fs = fs; p.fft_size = fft_size; p.lg_fft = lg;
   p.frame_period = frame_period / 1000.0;
   p.lowest_f0 = fs / fft_size + 1.0;                                   // integer division (synthesis.cpp:361)
-  p.f0 = d_f0; p.sp = d_sp; p.ap = d_ap; p.f_stride = f_stride; p.y = d_y; p.y_stride = y_stride;
+  p.f0 = rows.f0; p.sp = rows.sp; p.ap = rows.ap; p.row_stride = rows.row_stride; p.f0_stride = rows.f0_stride;
+  p.y = d_y; p.y_stride = y_stride;
   p.nblk = (max_y + synth_tile_samples() - 1) / synth_tile_samples();
   // Room for a mean pulse rate of 1200 Hz over the longest utterance unless the caller said otherwise (voiced
   // pulses come at f0, unvoiced ones at 500 Hz).  The pulse count is only known on the device; a call that
@@ -1120,10 +1117,34 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
   });
   p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
   p.y_len = upload(c, std::vector<int>(y_length, y_length + n_utt));
+  p.first_row = upload(c, rows.first_row);
   p.dc_remover = c->d_dc_remover;
   p.noise = ensure_noise(c, (size_t)max_y + 8);
   p.tab = c->tab;
   launch_synthesis(p, max_y, c->stream);
+}
+
+static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size, const int *n_frames,
+                          int f_stride, const double *d_f0, const double *d_sp, const double *d_ap,
+                          const int *y_length, int y_stride, double *d_y) {
+  if (n_utt <= 0) fail("n_utt must be positive");
+  if (fs <= 0 || frame_period <= 0) fail("fs and frame_period must be positive");
+  if (!d_f0 || !d_sp || !d_ap || !d_y || !n_frames || !y_length) fail("null buffer");
+  ilog2_exact(fft_size);
+  const std::string lim = shape_limit(8, fs, fft_size);                 // before any upload or launch
+  if (!lim.empty()) fail("%s", lim.c_str());
+  int max_y = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_frames[u] < 2 || n_frames[u] > f_stride) fail("n_frames[%d]=%d outside [2, f_stride]", u, n_frames[u]);
+    if (y_length[u] < 1 || y_length[u] > y_stride) fail("y_length[%d]=%d outside [1, y_stride]", u, y_length[u]);
+    max_y = std::max(max_y, y_length[u]);
+  }
+  SynthRows rows;
+  rows.f0 = d_f0; rows.sp = d_sp; rows.ap = d_ap;
+  rows.row_stride = fft_size / 2 + 1; rows.f0_stride = 1;
+  rows.first_row.resize(n_utt);
+  for (int u = 0; u < n_utt; ++u) rows.first_row[u] = (long long)u * f_stride;
+  synthesize_rows(c, n_utt, fs, frame_period, fft_size, n_frames, rows, y_length, y_stride, max_y, d_y);
 }
 
 // ---------------------------------------------------------------------------
@@ -1275,6 +1296,99 @@ static void run_analyze_coded(WorldHipContext *c, int n_utt, int fs, const doubl
   if (ndim < 1 || ndim > copt->fft_size / 4 + 1) fail("analyze_coded: number_of_dimensions %d outside [1, fft_size/4+1]", ndim);
   if (cols != coded_cols(fs, ndim)) fail("analyze_coded: %d columns, %d coefficients at fs=%d need %d", cols, ndim, fs, coded_cols(fs, ndim));
   analyze_into_records(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, first_row, d_block, cols, ndim);
+}
+
+// ---------------------------------------------------------------------------
+// Synthesis straight from records (include/world_hip.h: world_hip_synthesis_records): the mirror image of analyze_packed /
+// analyze_coded.  wire 0: the f64 records are read in place through SynthParams' row addressing, nothing is staged.
+// wire 1 / 2: sy_stage_records (codec.hip) turns every record into dense f64 rows once -- F0 [rows], sp and ap [rows][nb],
+// the utterances back to back -- carved at the bottom of the arena and held there (Arena::floor) while the synthesis
+// stage carves above them; a stage that needs more arena than is held makes the call grow it and start over, as in
+// run_resynthesis.
+// ---------------------------------------------------------------------------
+static void run_synthesis_records(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size,
+                                  const int *n_frames, long long first_row, const double *d_block, int cols, int wire,
+                                  int ndim, const int *y_length, int y_stride, double *d_y) {
+  if (n_utt <= 0) fail("n_utt must be positive");
+  if (fs <= 0 || frame_period <= 0) fail("fs and frame_period must be positive");
+  if (!d_block) fail("synthesis_records: null block");
+  if (!d_y || !n_frames || !y_length) fail("null buffer");
+  if (first_row < 0) fail("synthesis_records: negative first_row");
+  if (wire < 0 || wire > 2) fail("synthesis_records: wire %d (0: f64 records, 1: f32 records, 2: coded records)", wire);
+  const std::string lim = shape_limit(15, fs, fft_size);                // world_hip_check_shape's rule, before any GPU work
+  if (!lim.empty()) fail("%s", lim.c_str());
+  const int lg = ilog2_exact(fft_size), nb = fft_size / 2 + 1;
+  int nap = 0;
+  if (wire == 2) {                                                      // what the decoders refuse (run_codec)
+    nap = number_of_aperiodicities(fs);
+    if (nap < 1) fail("synthesis_records: fs=%d has no aperiodicity band (needs fs >= 12 kHz)", fs);
+    if (3000.0 * nap > fs / 2.0) fail("synthesis_records: band centre beyond fs/2");
+    if (ndim < 1 || ndim > fft_size / 4 + 1)
+      fail("synthesis_records: number_of_dimensions %d outside [1, fft_size/4+1]", ndim);
+    if (cols != coded_cols(fs, ndim))
+      fail("synthesis_records: %d columns, %d coefficients at fs=%d need %d", cols, ndim, fs, coded_cols(fs, ndim));
+  } else if (cols != record_cols(fft_size, wire)) {
+    fail("synthesis_records: %d columns, wire %d at fft_size %d needs %d", cols, wire, fft_size, record_cols(fft_size, wire));
+  }
+  std::vector<int> src(n_utt), dst(n_utt);
+  long long row = first_row, total = 0;
+  int max_y = 0, max_frames = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_frames[u] < 2) fail("n_frames[%d]=%d: synthesis needs 2 frames", u, n_frames[u]);
+    if (y_length[u] < 1 || y_length[u] > y_stride) fail("y_length[%d]=%d outside [1, y_stride]", u, y_length[u]);
+    if (row + n_frames[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
+    src[u] = static_cast<int>(row); dst[u] = static_cast<int>(total);
+    row += n_frames[u]; total += n_frames[u];
+    max_y = std::max(max_y, y_length[u]);
+    max_frames = std::max(max_frames, n_frames[u]);
+  }
+  SynthRows rows;
+  if (wire == 0) {                                                      // [tpos, f0, sp[nb], ap[nb]] in place
+    rows.f0 = d_block + 1; rows.sp = d_block + 2; rows.ap = d_block + 2 + nb;
+    rows.first_row.assign(src.begin(), src.end()); rows.row_stride = rows.f0_stride = (size_t)cols;
+    synthesize_rows(c, n_utt, fs, frame_period, fft_size, n_frames, rows, y_length, y_stride, max_y, d_y);
+    return;
+  }
+  StageRecordsParams sp;
+  sp.n_utt = n_utt; sp.wire = wire; sp.fft_size = fft_size; sp.lg_md = lg - 1; sp.ndim = ndim; sp.nap = nap;
+  sp.block = d_block; sp.cols = cols;
+  sp.knot_sp = sp.knot_ap = nullptr; sp.frac_sp = sp.frac_ap = sp.w_re = sp.w_im = nullptr;
+  auto carve = [&](Arena &a) {
+    sp.f0 = a.take<double>((size_t)total);
+    sp.sp = a.take<double>((size_t)total * nb); sp.ap = a.take<double>((size_t)total * nb);
+  };
+  struct Release {                                          // the floor never outlives the call, whatever happens in it
+    WorldHipContext *c;
+    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
+  } release{c};
+  size_t want = 0;
+  for (int attempt = 0;; ++attempt) {
+    c->arena.floor = 0;
+    ensure_arena(c, std::max(measure(carve), want));
+    arena_reset(c);
+    carve(c->arena);
+    c->arena.floor = c->arena.used;
+    try {
+      open_uploads(c);
+      if (wire == 2) {
+        const CodecTables &t = codec_tables(c, fs, fft_size);
+        sp.knot_sp = t.d_knot_dec; sp.frac_sp = t.d_frac_dec; sp.w_re = t.d_wd_re; sp.w_im = t.d_wd_im;
+        sp.knot_ap = t.d_knot_ap; sp.frac_ap = t.d_frac_ap;
+      }
+      sp.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+      sp.src_row = upload(c, src); sp.dst_row = upload(c, dst);
+      sp.tab = c->tab;
+      launch_stage_records(sp, max_frames, c->stream);
+      rows.f0 = sp.f0; rows.sp = sp.sp; rows.ap = sp.ap;
+      rows.first_row.assign(dst.begin(), dst.end()); rows.row_stride = (size_t)nb; rows.f0_stride = 1;
+      synthesize_rows(c, n_utt, fs, frame_period, fft_size, n_frames, rows, y_length, y_stride, max_y, d_y);
+      return;
+    } catch (const ArenaRegrow &r) {
+      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
+      if (attempt >= 4) fail("synthesis_records: the workspace did not settle");
+      want = std::max(want, r.bytes);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2001,6 +2115,15 @@ int world_hip_synthesis_batch(WorldHipContext *c, int n_utt, int fs, double fram
   return guarded(c, [&] {
     run_synthesis(c, n_utt, fs, frame_period, fft_size, n_frames, f_stride, d_f0, d_spectrogram, d_aperiodicity,
                   y_length, y_stride, d_y);
+  });
+}
+
+int world_hip_synthesis_records(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size,
+                                const int *n_frames, long long first_row, const double *d_block, int cols, int wire,
+                                int number_of_dimensions, const int *y_length, int y_stride, double *d_y) {
+  return guarded(c, [&] {
+    run_synthesis_records(c, n_utt, fs, frame_period, fft_size, n_frames, first_row, d_block, cols, wire,
+                          number_of_dimensions, y_length, y_stride, d_y);
   });
 }
 

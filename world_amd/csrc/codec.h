@@ -28,6 +28,45 @@ void launch_decode_spectral_envelope(const CodecParams &p, hipStream_t stream);
 void launch_code_aperiodicity(const CodecParams &p, hipStream_t stream);
 void launch_decode_aperiodicity(const CodecParams &p, hipStream_t stream);
 
+// Records -> the dense f64 rows the synthesiser reads (world_hip_synthesis_records; sy_stage_records).  One workgroup per
+// (frame, utterance) reads one record and writes that frame's F0, spectrogram row and aperiodicity row:
+//   wire 2: coded records [tpos, f0, mel-cepstrum[ndim], band aperiodicity[nap]] -- codec_decode_sp's and codec_decode_ap's
+//           arithmetic (the same device functions), both rows in the one launch;
+//   wire 1: [tpos, f0, sp f32[nb], ap f32[nb]] -- widened.
+// Utterance u's records start at row src_row[u] of `block` (`cols` doubles apart), its staged frames at row dst_row[u].
+struct StageRecordsParams {
+  int n_utt, wire;
+  int fft_size, lg_md;           // lg_md = log2(fft_size / 2)
+  int ndim, nap;                 // wire 2: coefficients and aperiodicity bands per record
+  const int *n_frames;           // [n_utt] (device)
+  const int *src_row, *dst_row;  // [n_utt] (device)
+  const double *block;
+  int cols;
+  double *f0;                    // [rows]
+  double *sp, *ap;               // [rows][fft_size/2+1]
+  // wire 2: the decoders' tables of (fs, fft_size) (api.hip: codec_tables)
+  const int *knot_sp, *knot_ap;
+  const double *frac_sp, *frac_ap, *w_re, *w_im;
+  Tables tab;
+};
+void launch_stage_records(const StageRecordsParams &p, int max_frames, hipStream_t stream);
+
+// The same decode into a real-time stream's frame store (world_hip_realtime_add_coded; rt_store_coded_rows): coded row r
+// of a chunk of n (coded_sp / coded_ap: device rows row_stride doubles apart) -> store row (first + r) % cap of dst_sp and
+// dst_ap ([cap][fft_size/2+1]).  rt_store_rows with the decode fused in: no dense chunk exists.
+struct RtCodedRowsParams {
+  double *dst_sp, *dst_ap;
+  int cap, n;
+  long long first;
+  const double *coded_sp, *coded_ap;
+  int row_stride;
+  int fft_size, lg_md, ndim, nap;
+  const int *knot_sp, *knot_ap;
+  const double *frac_sp, *frac_ap, *w_re, *w_im;
+  Tables tab;
+};
+void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream);
+
 // Parameter modification between analysis and synthesis (the reference's test/test.cpp: ParameterModification): F0
 // scaling with an optional log-F0 statistics conversion, and the spectral envelope stretched along frequency.  Every
 // per-utterance value is a device array of the context's small-array slabs ([n_utt] unless noted).

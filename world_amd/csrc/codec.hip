@@ -8,6 +8,9 @@
 //   decode_ap : band values -> interp1 over [0, 3k.., fs/2] -> 10^(x/20), aperiodic
 //               frames (mean band value > -0.5 dB) left at 1 - 1e-12   (codec.cpp:21-56,238-266)
 //
+//   sy_stage_records / rt_store_coded_rows : records -> the dense rows the synthesisers read, the two decoders fused in
+//               (world_hip_synthesis_records, world_hip_realtime_add_coded)
+//
 // Both interp1 calls have fixed knots and fixed queries, so their bin search and weights
 // are tables built once on the host (api.hip: codec_tables).  One 256-thread workgroup
 // per frame for the envelope kernels, one thread per output value for the band kernels.
@@ -58,14 +61,20 @@ __global__ void __launch_bounds__(256) codec_code_sp(CodecParams p) {
   });
 }
 
-__global__ void __launch_bounds__(256) codec_decode_sp(CodecParams p) {
-  DYN_LDS(lds);
-  const int row = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+// DecodeSpectralEnvelope of ONE row by the whole workgroup: `in` = its p.ndim coefficients, `out` = where its
+// fft_size/2+1 bins go, `lds` = decode_sp_lds_bytes(p.lg_md) bytes.  One spelling, three callers (codec_decode_sp,
+// sy_stage_records, rt_store_coded_rows): the rows are the same bits wherever they are written.
+struct DecodeTables {
+  int lg_md, ndim;
+  const int *knot;
+  const double *frac, *w_re, *w_im;
+  Tables tab;
+};
+__device__ __forceinline__ void decode_sp_row(const DecodeTables p, const double *in, double *out, char *lds, int tid, int nt) {
   const int md = 1 << p.lg_md, nb = md + 1;
   cplx *Z = reinterpret_cast<cplx *>(lds);                            // md complex points
   double *mel = reinterpret_cast<double *>(lds) + 2 * md + 16;        // md + 2 values
   const TwLds tw = stage_twiddles(mel + md + 2, p.lg_md, p.tab.tw);
-  const double *in = p.in + (size_t)row * (p.in_stride ? p.in_stride : (size_t)p.ndim);
   const double norm = sqrt(static_cast<double>(md));
   for (int i = tid; i < md; i += nt) {
     cplx v; v.re = 0.0; v.im = 0.0;
@@ -83,12 +92,20 @@ __global__ void __launch_bounds__(256) codec_decode_sp(CodecParams p) {
   __syncthreads();
   if (tid == 0) { mel[0] = mel[1]; mel[md + 1] = mel[md]; }
   __syncthreads();
-  double *out = p.out + (size_t)row * (p.out_stride ? p.out_stride : (size_t)nb);
   for (int j = tid; j < nb; j += nt) {
     const int k = p.knot[j];
     const double v = mel[k - 1] + p.frac[j] * (mel[k] - mel[k - 1]);
     out[j] = exp(v / md);
   }
+}
+
+__global__ void __launch_bounds__(256) codec_decode_sp(CodecParams p) {
+  DYN_LDS(lds);
+  const int row = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int md = 1 << p.lg_md, nb = md + 1;
+  const double *in = p.in + (size_t)row * (p.in_stride ? p.in_stride : (size_t)p.ndim);
+  decode_sp_row(DecodeTables{p.lg_md, p.ndim, p.knot, p.frac, p.w_re, p.w_im, p.tab}, in,
+                p.out + (size_t)row * (p.out_stride ? p.out_stride : (size_t)nb), lds, tid, nt);
 }
 
 __global__ void codec_code_ap(CodecParams p) {
@@ -106,24 +123,73 @@ __global__ void codec_code_ap(CodecParams p) {
   p.out[(size_t)row * (p.out_stride ? p.out_stride : (size_t)p.ndim) + band] = y0 + dy * fr;
 }
 
+// DecodeAperiodicity of ONE row of `ndim` band values `in`: CheckVUV's mean, once per row, then bin j from it.  The
+// callers of decode_sp_row share both.
+__device__ __forceinline__ double decode_ap_mean(const double *in, int ndim) {
+  double mean = 0.0;                                  // CheckVUV, codec.cpp:31-41
+  for (int i = 0; i < ndim; ++i) mean += in[i];
+  return mean / ndim;
+}
+__device__ __forceinline__ double decode_ap_bin(const double *in, int ndim, double mean, const int *knot, const double *frac, int j) {
+  double v = 1.0 - kTiny;                             // InitializeAperiodicity, codec.cpp:21-26
+  if (!(mean > -0.5)) {
+    // coarse = [-60, bands..., -1e-12] over knots [0, 3000.., fs/2]
+    const int k = knot[j];
+    const double lo = k - 1 == 0 ? -60.0 : in[k - 2];
+    const double hi = k == ndim + 1 ? -kTiny : in[k - 1];
+    v = pow(10.0, (lo + frac[j] * (hi - lo)) / 20.0);
+  }
+  return v;
+}
+
 __global__ void codec_decode_ap(CodecParams p) {
   const int nb = p.fft_size / 2 + 1;
   const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= (long)p.rows * nb) return;
   const int row = (int)(item / nb), j = (int)(item - (long)row * nb);
   const double *in = p.in + (size_t)row * (p.in_stride ? p.in_stride : (size_t)p.ndim);
-  double mean = 0.0;                                  // CheckVUV, codec.cpp:31-41
-  for (int i = 0; i < p.ndim; ++i) mean += in[i];
-  mean /= p.ndim;
-  double v = 1.0 - kTiny;                             // InitializeAperiodicity, codec.cpp:21-26
-  if (!(mean > -0.5)) {
-    // coarse = [-60, bands..., -1e-12] over knots [0, 3000.., fs/2]
-    const int k = p.knot[j];
-    const double lo = k - 1 == 0 ? -60.0 : in[k - 2];
-    const double hi = k == p.ndim + 1 ? -kTiny : in[k - 1];
-    v = pow(10.0, (lo + p.frac[j] * (hi - lo)) / 20.0);
-  }
+  const double v = decode_ap_bin(in, p.ndim, decode_ap_mean(in, p.ndim), p.knot, p.frac, j);
   p.out[(size_t)row * (p.out_stride ? p.out_stride : (size_t)nb) + j] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Synthesis from records (world_hip_synthesis_records, world_hip_realtime_add_coded): a record becomes the dense f64 rows
+// the pulse kernels read, ONCE per frame.  (Decoding inside the pulse instead would run the transform about five times per
+// frame -- a pulse reads two frames, an unvoiced stretch has 2.5 pulses per 5 ms frame -- in a kernel that is already bound
+// by vector-ALU issue: DESIGN.md 3.9.)  LDS: decode_sp_lds_bytes, the envelope's transform; the aperiodicity row needs none.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) sy_stage_records(StageRecordsParams p) {
+  DYN_LDS(lds);
+  const int f = blockIdx.x, u = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (f >= p.n_frames[u]) return;
+  const int nb = p.fft_size / 2 + 1;
+  const double *rec = p.block + ((size_t)p.src_row[u] + f) * p.cols;
+  const size_t at = (size_t)p.dst_row[u] + f;
+  double *sp = p.sp + at * nb, *ap = p.ap + at * nb;
+  if (tid == 0) p.f0[at] = rec[1];
+  if (p.wire == 1) {                                  // [tpos, f0, sp f32[nb], ap f32[nb]]
+    const float *rows = reinterpret_cast<const float *>(rec + 2);
+    for (int j = tid; j < nb; j += nt) { sp[j] = rows[j]; ap[j] = rows[nb + j]; }
+    return;
+  }
+  const DecodeTables ts{p.lg_md, p.ndim, p.knot_sp, p.frac_sp, p.w_re, p.w_im, p.tab};
+  decode_sp_row(ts, rec + 2, sp, lds, tid, nt);
+  const double *bands = rec + 2 + p.ndim;
+  const double mean = decode_ap_mean(bands, p.nap);
+  for (int j = tid; j < nb; j += nt) ap[j] = decode_ap_bin(bands, p.nap, mean, p.knot_ap, p.frac_ap, j);
+}
+
+__global__ void __launch_bounds__(256) rt_store_coded_rows(RtCodedRowsParams p) {
+  DYN_LDS(lds);
+  const int r = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  if (r >= p.n) return;
+  const int nb = p.fft_size / 2 + 1;
+  const size_t row = (size_t)((p.first + r) % p.cap) * nb;
+  const DecodeTables ts{p.lg_md, p.ndim, p.knot_sp, p.frac_sp, p.w_re, p.w_im, p.tab};
+  decode_sp_row(ts, p.coded_sp + (size_t)r * p.row_stride, p.dst_sp + row, lds, tid, nt);
+  const double *bands = p.coded_ap + (size_t)r * p.row_stride;
+  const double mean = decode_ap_mean(bands, p.nap);
+  for (int j = tid; j < nb; j += nt) p.dst_ap[row + j] = decode_ap_bin(bands, p.nap, mean, p.knot_ap, p.frac_ap, j);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -370,6 +436,14 @@ void launch_code_aperiodicity(const CodecParams &p, hipStream_t stream) {
 }
 void launch_decode_aperiodicity(const CodecParams &p, hipStream_t stream) {
   WH_THREADS(codec_decode_ap, (long)p.rows * (p.fft_size / 2 + 1), 1, 1, stream, p);
+}
+void launch_stage_records(const StageRecordsParams &p, int max_frames, hipStream_t stream) {
+  if (max_frames <= 0) return;
+  WH_BLOCKS(sy_stage_records, dim3(max_frames, p.n_utt), 256, p.wire == 2 ? decode_sp_lds_bytes(p.lg_md) : 0, stream, p);
+}
+void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) {
+  if (p.n <= 0) return;
+  WH_BLOCKS(rt_store_coded_rows, dim3(p.n), 256, decode_sp_lds_bytes(p.lg_md), stream, p);
 }
 
 }  // namespace world_hip

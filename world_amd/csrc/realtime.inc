@@ -711,6 +711,35 @@ int world_hip_realtime_add(WorldHipRealtime *rt, int stream, const double *f0, i
   });
 }
 
+// AddParameters of a chunk whose rows are coded: rt_store_coded_rows (codec.hip) decodes them straight into the stream's
+// frame store -- the decoders' arithmetic, their refusals
+int world_hip_realtime_add_coded(WorldHipRealtime *rt, int stream, const double *f0, int n_frames, const double *d_coded_sp,
+                                 int number_of_dimensions, const double *d_coded_ap, int row_stride) {
+  return rt_guarded(rt, [&] {
+    WorldHipContext *c = rt->ctx;
+    const int fs = rt->fs, fft_size = rt->fft_size, ndim = number_of_dimensions;
+    if (!d_coded_sp || !d_coded_ap) fail("null coded spectral envelope / aperiodicity rows");
+    const int nap = world_hip::number_of_aperiodicities(fs);
+    if (nap < 1) fail("realtime_add_coded: fs=%d has no aperiodicity band (needs fs >= 12 kHz)", fs);
+    if (3000.0 * nap > fs / 2.0) fail("realtime_add_coded: band centre beyond fs/2");
+    if (ndim < 1 || ndim > fft_size / 4 + 1)
+      fail("realtime_add_coded: number_of_dimensions %d outside [1, fft_size/4+1]", ndim);
+    if (row_stride < std::max(ndim, nap)) fail("row_stride %d < the %d values of a coded row", row_stride, std::max(ndim, nap));
+    return rt_add(rt, stream, f0, n_frames, [&](long long first) {
+      RtStream &st = rt->streams[stream];
+      const CodecTables &t = codec_tables(c, fs, fft_size);
+      RtCodedRowsParams p;
+      p.dst_sp = st.d_sp; p.dst_ap = st.d_ap; p.cap = st.store_cap; p.n = n_frames; p.first = first;
+      p.coded_sp = d_coded_sp; p.coded_ap = d_coded_ap; p.row_stride = row_stride;
+      p.fft_size = fft_size; p.lg_md = rt->lg_fft - 1; p.ndim = ndim; p.nap = nap;
+      p.knot_sp = t.d_knot_dec; p.frac_sp = t.d_frac_dec; p.w_re = t.d_wd_re; p.w_im = t.d_wd_im;
+      p.knot_ap = t.d_knot_ap; p.frac_ap = t.d_frac_ap;
+      p.tab = c->tab;
+      launch_rt_store_coded_rows(p, c->stream);
+    });
+  });
+}
+
 int world_hip_realtime_synthesize(WorldHipRealtime *rt, double *d_out, int *produced) {
   return rt_guarded(rt, [&] {
     if (!d_out || !produced) fail("null output");

@@ -13,9 +13,14 @@ struct SynthParams {
   int n_utt, fs, fft_size, lg_fft;
   double frame_period;      // seconds (the reference divides by 1000 on entry, synthesis.cpp:360,366)
   double lowest_f0;         // fs / fft_size + 1.0 with the reference's integer division (synthesis.cpp:361)
-  const double *f0;         // [n_utt][f_stride]
-  const double *sp, *ap;    // [n_utt][f_stride][fft_size/2+1]
-  int f_stride;
+  // Frame j of utterance u is row first_row[u] + j: its rows are sp / ap + row * row_stride (fft_size/2+1 doubles used), its
+  // F0 is f0[row * f0_stride].  Dense arrays [n_utt][f_stride](...): first_row[u] = u * f_stride, row_stride = fft_size/2+1,
+  // f0_stride = 1.  f64 records read in place (world_hip_synthesis_records, wire 0): the utterance's first record, both
+  // strides the record's columns, the three pointers at the record's f0 / sp / ap columns.
+  const double *f0;
+  const double *sp, *ap;
+  const long long *first_row;   // [n_utt] (device)
+  size_t row_stride, f0_stride;
   const int *n_frames;      // [n_utt] (device)
   const int *y_len;         // [n_utt] (device)
   double *y;                // [n_utt][y_stride]

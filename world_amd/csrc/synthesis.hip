@@ -24,11 +24,19 @@
 
 namespace world_hip {
 
+struct StridedTrack {
+  const double *base;
+  size_t stride;
+  __device__ __forceinline__ double operator[](int j) const { return base[(size_t)j * stride]; }
+};
+
 // interp1 (matlabfunctions.cpp:136-176) of the coarse f0 / vuv tracks at sample i.
 // Knots are i * frame_period, i = 0 .. nf (nf + 1 of them); the value at knot nf is the
 // linear extrapolation 2 v[nf-1] - v[nf-2] (synthesis.cpp:239-243).
-__device__ __forceinline__ void coarse_tracks(const SynthParams &p, const double *f0, int nf, int i, double *f0_out,
+// `track` is the utterance's F0 at frame 0, p.f0_stride doubles from frame to frame.
+__device__ __forceinline__ void coarse_tracks(const SynthParams &p, const double *track, int nf, int i, double *f0_out,
                                               int *vuv_out) {
+  const StridedTrack f0{track, p.f0_stride};
   const double t = i / static_cast<double>(p.fs);
   const double fp = p.frame_period;
   const int n = nf + 1;
@@ -62,7 +70,7 @@ __device__ __forceinline__ void coarse_tracks(const SynthParams &p, const double
 __global__ void __launch_bounds__(kSyThreads) sy_increments(SynthParams p) {
   const int u = blockIdx.y, tid = threadIdx.x;
   const int n = p.y_len[u], nf = p.n_frames[u];
-  const double *f0 = p.f0 + (size_t)u * p.f_stride;
+  const double *f0 = p.f0 + (size_t)p.first_row[u] * p.f0_stride;
   for (int i = blockIdx.x * kSyTile + tid; i < imin(n, (blockIdx.x + 1) * kSyTile); i += kSyThreads) {
     double f; int voiced;
     coarse_tracks(p, f0, nf, i, &f, &voiced);
@@ -355,7 +363,7 @@ __global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
   const int u = blockIdx.y, pi = blockIdx.x;
   const int np = p.np[u];
   if (pi >= np) return;
-  const int lgn = p.lg_fft, N = 1 << lgn, nb = N / 2 + 1;
+  const int lgn = p.lg_fft, N = 1 << lgn;
   double *const slot = p.resp + ((size_t)u * p.pulse_cap + pi) * p.resp_stride;
   const int *pidx = p.pidx + (size_t)u * p.pulse_cap;
   const int idx = pidx[pi];
@@ -369,8 +377,9 @@ __global__ void __launch_bounds__(kSyThreads) sy_pulse(SynthParams p) {
   const int ff = imin(nf - 1, static_cast<int>(floor(t / fp))), fc = imin(nf - 1, static_cast<int>(ceil(t / fp)));
   in.wgt = t / fp - ff;
   in.same = ff == fc;
-  in.sp0 = p.sp + ((size_t)u * p.f_stride + ff) * nb; in.sp1 = p.sp + ((size_t)u * p.f_stride + fc) * nb;
-  in.ap0 = p.ap + ((size_t)u * p.f_stride + ff) * nb; in.ap1 = p.ap + ((size_t)u * p.f_stride + fc) * nb;
+  const size_t row0 = p.first_row[u];
+  in.sp0 = p.sp + (row0 + ff) * p.row_stride; in.sp1 = p.sp + (row0 + fc) * p.row_stride;
+  in.ap0 = p.ap + (row0 + ff) * p.row_stride; in.ap1 = p.ap + (row0 + fc) * p.row_stride;
   in.noise = p.noise + (idx - pidx[0]);
   in.delay_coef = 2.0 * kPi * p.pshift[(size_t)u * p.pulse_cap + pi] * p.fs / N;
   pulse_response<NMAX, false>(lds, slot, lgn, p.tab.tw, p.dc_remover, in);

@@ -67,14 +67,24 @@ def _synthesis(a):
     sp, ap = files.read_spectral_envelope(a.sp), files.read_aperiodicity(a.ap)
     if read is None or sp is None or ap is None:
         sys.exit("synthesis: unreadable parameter file")
+    n = len(read[1])
+    y_length = int(n * frame_period / 1000.0 * fs)              # examples/parameter_io/readandsynthesis.cpp:85
+    if int(files.header(a.sp, "NOD ")) and int(files.header(a.ap, "NOD ")):
+        # both coded: only the coded rows are uploaded; they become coded records [tpos, f0, mel-cepstrum, bands] on the
+        # device and one call synthesises from them (world_hip_synthesis_records, wire 2)
+        block = torch.cat([torch.zeros((n, 1), dtype=torch.float64, device=wh.device),
+                           torch.from_numpy(read[1]).to(wh.device)[:, None], torch.from_numpy(sp).to(wh.device),
+                           torch.from_numpy(ap).to(wh.device)], dim=1).contiguous()
+        y = wh.synthesize_records(block, [n], fs, fft_size, frame_period, [y_length], wire=2, number_of_dimensions=sp.shape[1])
+        wh.wavwrite(a.o, y[0, :y_length], fs)
+        print(f"{n} frames -> {a.o} ({y_length} samples at {fs} Hz)")
+        return
     f0 = torch.from_numpy(read[1]).to(wh.device)[None]
     sp, ap = torch.from_numpy(sp).to(wh.device)[None], torch.from_numpy(ap).to(wh.device)[None]
     if int(files.header(a.sp, "NOD ")):
         sp = wh.decode_spectral_envelope(sp, fs, fft_size)
     if int(files.header(a.ap, "NOD ")):
         ap = wh.decode_aperiodicity(ap, fs, fft_size)
-    n = f0.shape[1]
-    y_length = int(n * frame_period / 1000.0 * fs)              # examples/parameter_io/readandsynthesis.cpp:85
     y = wh.synthesis(f0, sp, ap, np.array([n], dtype=np.int32), fft_size, frame_period, fs,
                      np.array([y_length], dtype=np.int32))
     wh.wavwrite(a.o, y[0, :y_length], fs)
