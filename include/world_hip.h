@@ -675,6 +675,48 @@ WORLD_HIP_API int world_hip_resynthesize_frames_batch(WorldHipContext *ctx, int 
                                                       const WorldHipFrameCurves *curves, const int *n_out, int o_stride,
                                                       const int *y_length, int y_stride, double *d_y);
 
+/* Alignment of two utterances by dynamic time warping: which frame of A belongs to which frame of B, from the coded frames
+ * world_hip_analyze_coded / world_hip_code_spectral_envelope write, as the time map world_hip_modify_frames_batch reads.
+ * Pair u has n_a[u] >= 1 frames of A and n_b[u] >= 1 frames of B (HOST arrays).  Frame i of A is the n_dims doubles at
+ * d_a + (a_row[u] + i) * a_row_stride, B likewise; a_row / b_row are HOST arrays of each pair's first row.  One rule, three
+ * layouts: dense coded arrays (a_row[u] = u * f_stride); blocks of coded records (a_row[u] = the prefix sum of the frame
+ * counts, d_a pointing at column 2, or column 3 to leave out c0, the usual choice); two utterances of one block (d_a and
+ * d_b may alias: the call only reads them).  1 <= n_dims <= the row strides, n_dims <= 256.
+ *   local cost  c(i, j) = sqrt(s), s = the sum over k = 0 .. n_dims - 1, in ascending order, of (a_k - b_k) * (a_k - b_k):
+ *               subtraction, multiplication and addition each rounded on its own (no fused multiply-add), the square
+ *               root IEEE-rounded.
+ *   recurrence  D(0, 0) = c(0, 0); D(i, j) = c(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)) over the predecessors that
+ *               exist; the predecessor taken is the first of (diagonal, i - 1, j - 1) that attains the minimum (a later
+ *               candidate replaces an earlier one only if strictly smaller).  The path is the backtrack from
+ *               (n_a - 1, n_b - 1) to (0, 0); K is its length.
+ * Outputs (DEVICE arrays, each may be NULL):
+ *   d_path [n_pairs][p_stride][2]   the cells (i, j) in ascending order;   d_path_len [n_pairs]   K
+ *   d_summary [n_pairs][3]          {D(n_a-1, n_b-1), K, mcd_db}, mcd_db = (10 / ln 10) * sqrt(2) * D / K: the mel-cepstral
+ *                                   distortion in dB when the rows are WORLD mel-cepstra without c0
+ *   d_map_b [n_pairs][map_stride]   for frame j of B: 0.5 * (i_lo + i_hi) over the path cells of column j (exact).  This
+ *                                   is world_hip_modify_frames_batch's d_time_map with A as the source and n_out = n_b.
+ *   d_map_a [n_pairs][map_stride]   the mirror image, one value per frame of A
+ * Entries beyond a pair's own counts (path rows beyond K, map entries beyond n_b / n_a) are never written.
+ * Refused before any GPU work, with nothing written: n_pairs < 1, a NULL input, a count below 1, n_dims outside [1, 256],
+ * a row stride below n_dims, a negative row, p_stride < n_a[u] + n_b[u] - 1 when d_path is given, map_stride below the
+ * frame count a given map needs, n_a[u] * n_b[u] above world_hip_align_workspace_cells() = 2^26 cells (8192 x 8192; about
+ * 40 s against 40 s at a 5 ms hop).  Feature values cannot be checked before the launch: a pair with NaN or Inf features
+ * still gets a monotone path from (0, 0) to its last cell, of whatever cost, with every index in bounds, and no other pair
+ * is affected.  Workspace: 9 bytes per cell (cost and predecessor; the backward walk reuses the pair's cost bytes) and 8 per
+ * pair, for at most 2^26 cells at a time -- larger batches are walked in groups of pairs -- so never more than 0.61 GB;
+ * world_hip_workspace_bytes counts it.  Time: the cost is parallel, but a pair's n_a + n_b - 1 anti-diagonals are serial
+ * steps in one workgroup -- 0.96 us each as measured on one MI355X: 4 ms at 2001 x 2001, 16 ms at
+ * 8192 x 8192.  The cell limit bounds memory, not that: a degenerate pair such as 1 x 2^26 is admitted and would hold one
+ * compute unit for about a minute -- keep n_a + n_b to what the use needs (an utterance of 40 s has 8192 frames).  Stream
+ * order and errors as the other batched calls; after one eager call of a shape the call neither allocates nor waits and can
+ * be captured. */
+WORLD_HIP_API int world_hip_align_batch(WorldHipContext *ctx, int n_pairs, int n_dims, const double *d_a,
+                                        const long long *a_row, const int *n_a, int a_row_stride, const double *d_b,
+                                        const long long *b_row, const int *n_b, int b_row_stride, int p_stride, int *d_path,
+                                        int *d_path_len, double *d_summary, int map_stride, double *d_map_b,
+                                        double *d_map_a);
+WORLD_HIP_API int world_hip_align_workspace_cells(void);   /* the per-pair cell limit; host arithmetic */
+
 /* Real-time synthesis, batched (reference src/synthesisrealtime.cpp; the drop-in WorldSynthesizer above is built on it).
  * One object serves n_streams independent streams with one fs, frame_period (ms), fft_size, buffer_size and ring size
  * number_of_pointers; every stream behaves exactly as one reference synthesiser: same pulses, same return values, its own

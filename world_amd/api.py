@@ -353,6 +353,11 @@ def load_library(path=LIB_PATH):
         lib.world_hip_synthesis_records.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_longlong, vp,
                                                     C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp]
         lib.world_hip_realtime_add_coded.argtypes = [vp, C.c_int, _dp, C.c_int, vp, C.c_int, vp, C.c_int]
+    if hasattr(lib, "world_hip_align_batch"):                        # (likewise)
+        lp = C.POINTER(C.c_longlong)
+        lib.world_hip_align_batch.argtypes = [vp, C.c_int, C.c_int, vp, lp, _ip, C.c_int, vp, lp, _ip, C.c_int, C.c_int,
+                                              vp, vp, vp, C.c_int, vp, vp]
+        lib.world_hip_align_workspace_cells.argtypes = []
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -1105,6 +1110,54 @@ class WorldHip:
             finally:
                 self.set_synthesis_pulse_capacity(0)
         return y, yl
+
+    # ---- alignment by dynamic time warping (include/world_hip.h: world_hip_align_batch) ----
+    def align(self, a, b, n_a, n_b, a_row=None, b_row=None, want_path=True):
+        """Which frame of A belongs to which frame of B: a, b are float64 device tensors of frames, either dense
+        [P, F, D] (pair u's frames are a[u, :n_a[u]]) or a block of records [rows, D] with a_row / b_row naming each pair's
+        first row.  Both may be views that slice the columns (block[:, 3:3 + 24]: mel-cepstra without c0): the row stride
+        is the tensor's own.  -> (path [P, S, 2] int32 or None, path_len [P] int32, summary [P, 3] = {D, K, MCD in dB},
+        map_b [P, max n_b], map_a [P, max n_a]); map_b[u, :n_b[u]] is modify_frames' time_map with A as the source."""
+        t = self.torch
+        if not hasattr(self.lib, "world_hip_align_batch"):
+            raise RuntimeError("this libworld_hip.so has no alignment (world_hip_align_batch)")
+        na = np.ascontiguousarray(np.atleast_1d(n_a), dtype=np.int32)
+        nb = np.ascontiguousarray(np.atleast_1d(n_b), dtype=np.int32)
+        P = len(na)
+        assert len(nb) == P and P >= 1 and int(na.min()) >= 1 and int(nb.min()) >= 1
+
+        def rows_of(x, first, counts, name):
+            assert x.dtype == t.float64 and x.device == self.device and x.dim() in (2, 3), f"{name}: float64 [P, F, D] or [rows, D] on {self.device}"
+            assert x.shape[-1] >= 1 and (x.shape[-1] == 1 or x.stride(-1) == 1), f"{name}: the columns of a frame must be adjacent"
+            stride = x.stride(-2) if x.shape[-2] > 1 else max(x.shape[-1], x.stride(-2))
+            assert stride >= x.shape[-1], f"{name}: rows overlap"
+            if x.dim() == 3:
+                assert first is None and x.shape[0] == P and int(counts.max()) <= x.shape[1], f"{name}: [P, F, D] with F >= the frame counts"
+                assert P == 1 or x.stride(0) % stride == 0, f"{name}: the utterances must lie whole rows apart"
+                first = np.arange(P, dtype=np.int64) * ((x.stride(0) // stride) if P > 1 else 0)
+            else:
+                first = np.zeros(1, dtype=np.int64) if first is None and P == 1 else first
+                assert first is not None, f"{name}: a block of records needs {name}_row"
+                first = np.ascontiguousarray(first, dtype=np.int64)
+                assert len(first) == P and int(first.min()) >= 0 and int((first + counts).max()) <= x.shape[0]
+            return first, int(stride)
+
+        ar, a_stride = rows_of(a, a_row, na, "a")
+        br, b_stride = rows_of(b, b_row, nb, "b")
+        assert a.shape[-1] == b.shape[-1], "a and b disagree about the number of dimensions"
+        S, Ma, Mb = int((na + nb).max()) - 1, int(na.max()), int(nb.max())
+        M = max(Ma, Mb)
+        path = t.zeros((P, S, 2), dtype=t.int32, device=self.device) if want_path else None
+        path_len = t.zeros((P,), dtype=t.int32, device=self.device)
+        summary = t.zeros((P, 3), dtype=t.float64, device=self.device)
+        maps = t.zeros((2, P, M), dtype=t.float64, device=self.device)
+        lp = C.POINTER(C.c_longlong)
+        self._check(self.lib.world_hip_align_batch(self._context(), P, int(a.shape[-1]), a.data_ptr(), ar.ctypes.data_as(lp),
+                                                   na.ctypes.data_as(_ip), a_stride, b.data_ptr(), br.ctypes.data_as(lp),
+                                                   nb.ctypes.data_as(_ip), b_stride, S,
+                                                   path.data_ptr() if want_path else None, path_len.data_ptr(),
+                                                   summary.data_ptr(), M, maps[0].data_ptr(), maps[1].data_ptr()), "align")
+        return path, path_len, summary, maps[0, :, :Mb], maps[1, :, :Ma]
 
     # ---- the per-frame FFT in isolation (include/world_hip.h: world_hip_probe_rfft) ----
     def probe_rfft(self, x, max_lr=3, threads=0, out=None, static_plan=False):

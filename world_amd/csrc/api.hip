@@ -1778,6 +1778,78 @@ static void run_resynthesis_frames(WorldHipContext *c, int n_utt, int fs, const 
   }
 }
 
+// Alignment of pairs of frame rows by dynamic time warping (include/world_hip.h: world_hip_align_batch; align.inc).
+// Everything the host can know is refused before any GPU work.  The pairs are walked in groups of at most kAlignCells
+// cells, so the workspace is 9 bytes per cell (the cost and the predecessor code) of the largest group, never more than
+// 9 * kAlignCells bytes (+ 8 per pair for D), whatever the batch: the backward walk of a pair, n_a + n_b - 1 <= n_a n_b
+// entries of 8 bytes, is written over the pair's own costs, which are dead once align_dp has run.
+// Time is another matter: a pair takes n_a + n_b - 1 serial diagonal steps of about 1 us, 16 ms at 8192 x 8192 -- but a
+// degenerate 1 x 2^26 pair is within the cell limit too and would keep one CU busy for about a minute (the header says so).
+static const long long kAlignCells = 1LL << 26;
+
+static void run_align(WorldHipContext *c, int n_pairs, int n_dims, const double *d_a, const long long *a_row, const int *n_a,
+                      int a_row_stride, const double *d_b, const long long *b_row, const int *n_b, int b_row_stride,
+                      int p_stride, int *d_path, int *d_path_len, double *d_summary, int map_stride, double *d_map_b,
+                      double *d_map_a) {
+  if (n_pairs < 1) fail("align: n_pairs must be positive");
+  if (!d_a || !d_b || !a_row || !b_row || !n_a || !n_b) fail("align: null input");
+  if (n_dims < 1 || n_dims > 256) fail("align: n_dims %d outside [1, 256]", n_dims);
+  if (a_row_stride < n_dims || b_row_stride < n_dims)
+    fail("align: row strides (%d, %d) below n_dims %d", a_row_stride, b_row_stride, n_dims);
+  for (int u = 0; u < n_pairs; ++u) {
+    if (n_a[u] < 1 || n_b[u] < 1) fail("align: pair %d has %d x %d frames; each side needs one", u, n_a[u], n_b[u]);
+    if (a_row[u] < 0 || b_row[u] < 0) fail("align: pair %d starts at a negative row", u);
+    if ((long long)n_a[u] * n_b[u] > kAlignCells)
+      fail("align: pair %d has %d x %d cells, more than the %lld of world_hip_align_workspace_cells()", u, n_a[u], n_b[u], kAlignCells);
+    if (d_path && (long long)p_stride < (long long)n_a[u] + n_b[u] - 1)
+      fail("align: p_stride %d cannot hold pair %d's longest path (%d + %d - 1)", p_stride, u, n_a[u], n_b[u]);
+    if (d_map_b && map_stride < n_b[u]) fail("align: map_stride %d below n_b[%d]=%d", map_stride, u, n_b[u]);
+    if (d_map_a && map_stride < n_a[u]) fail("align: map_stride %d below n_a[%d]=%d", map_stride, u, n_a[u]);
+  }
+  if (!d_path && !d_path_len && !d_summary && !d_map_b && !d_map_a) return;
+  // groups of consecutive pairs within the cell budget; a pair's place in its group's workspace
+  std::vector<long long> cell0(n_pairs);
+  std::vector<int> first;                                   // first pair of every group, then n_pairs
+  long long cells = 0, max_cells = 0;
+  for (int u = 0; u < n_pairs; ++u) {
+    const long long own = (long long)n_a[u] * n_b[u];
+    if (u == 0 || cells + own > kAlignCells || u - first.back() >= 32768) { first.push_back(u); cells = 0; }
+    cell0[u] = cells;
+    cells += own;
+    max_cells = std::max(max_cells, cells);
+  }
+  first.push_back(n_pairs);
+  AlignParams p;
+  begin_stage(c, [&](Arena &a) {
+    p.cost = a.take<double>((size_t)max_cells);
+    p.code = a.take<unsigned char>((size_t)max_cells);
+    p.dist = a.take<double>((size_t)n_pairs);
+  });
+  p.n_dims = n_dims;
+  p.a = d_a; p.b = d_b; p.a_stride = a_row_stride; p.b_stride = b_row_stride;
+  p.a_row = upload(c, std::vector<long long>(a_row, a_row + n_pairs));
+  p.b_row = upload(c, std::vector<long long>(b_row, b_row + n_pairs));
+  p.n_a = upload(c, std::vector<int>(n_a, n_a + n_pairs));
+  p.n_b = upload(c, std::vector<int>(n_b, n_b + n_pairs));
+  p.cell0 = upload(c, cell0);
+  p.mcd_scale = 10.0 / log(10.0) * sqrt(2.0);
+  p.path = d_path; p.p_stride = p_stride; p.path_len = d_path_len; p.summary = d_summary;
+  p.map_stride = map_stride; p.map_b = d_map_b; p.map_a = d_map_a;
+  for (size_t g = 0; g + 1 < first.size(); ++g) {
+    int tiles = 0, shorter = 0;
+    for (int u = first[g]; u < first[g + 1]; ++u) {
+      tiles = std::max(tiles, align_cost_tiles(n_a[u], n_b[u]));
+      shorter = std::max(shorter, std::min(n_a[u], n_b[u]));
+    }
+    p.first_pair = first[g];
+    p.cap = shorter + 1;
+    const int pairs = first[g + 1] - first[g];
+    launch_align_cost(p, pairs, tiles, c->stream);
+    launch_align_dp(p, pairs, c->stream);
+    launch_align_path(p, pairs, c->stream);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2438,6 +2510,16 @@ int world_hip_resynthesize_frames_batch(WorldHipContext *c, int n_utt, int fs, c
                            n_out, o_stride, y_length, y_stride, d_y);
   });
 }
+int world_hip_align_batch(WorldHipContext *c, int n_pairs, int n_dims, const double *d_a, const long long *a_row,
+                          const int *n_a, int a_row_stride, const double *d_b, const long long *b_row, const int *n_b,
+                          int b_row_stride, int p_stride, int *d_path, int *d_path_len, double *d_summary, int map_stride,
+                          double *d_map_b, double *d_map_a) {
+  return guarded(c, [&] {
+    run_align(c, n_pairs, n_dims, d_a, a_row, n_a, a_row_stride, d_b, b_row, n_b, b_row_stride, p_stride, d_path, d_path_len,
+              d_summary, map_stride, d_map_b, d_map_a);
+  });
+}
+int world_hip_align_workspace_cells(void) { return (int)kAlignCells; }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||
       !(time_scale > 0))

@@ -114,4 +114,36 @@ void launch_modify_frames_sp(const ModifyFramesParams &p, int max_out, hipStream
 void launch_modify_frames_ap(const ModifyFramesParams &p, int max_out, hipStream_t stream);
 void launch_modify_frames_f0(const ModifyFramesParams &p, int max_out, hipStream_t stream);
 
+// Alignment of two rows of frames by dynamic time warping (world_hip_align_batch; align.inc).  Pair u: n_a[u] frames of A
+// from row a_row[u] of `a` (a_stride doubles apart, n_dims of them used), B likewise.  The launches of one GROUP of pairs
+// [first_pair, first_pair + pairs) share the workspace: pair u's cells live at cell0[u] of `cost` / `code`, one anti-diagonal
+// after the other (cell (i, j) of diagonal d = i + j at the diagonal's start + i - max(0, d - (n_b - 1))), so that the DP
+// kernel reads and writes consecutive addresses.  The backward walk ([n_a + n_b - 1][2] ints, far corner first) is written
+// over the pair's own costs once the DP has consumed them: 8 bytes per step, and n_a + n_b - 1 <= n_a n_b.
+struct AlignParams {
+  int n_dims, first_pair;
+  const double *a, *b;
+  int a_stride, b_stride;
+  const long long *a_row, *b_row;   // [n_pairs] (device, as every array below)
+  const int *n_a, *n_b;             // [n_pairs]
+  const long long *cell0;           // [n_pairs]
+  double *cost;                     // local costs c(i, j); after align_dp, the pair's walk
+  unsigned char *code;              // predecessor of every cell: 0 diagonal, 1 (i - 1, j), 2 (i, j - 1), 3 none (the origin)
+  double *dist;                     // [n_pairs] D(n_a - 1, n_b - 1)
+  int cap;                          // slots of each of align_dp's two diagonal buffers in LDS: > min(n_a, n_b) of every pair
+  double mcd_scale;                 // (10 / ln 10) sqrt(2)
+  // outputs, each optional
+  int *path;                        // [n_pairs][p_stride][2]
+  int p_stride;
+  int *path_len;                    // [n_pairs]
+  double *summary;                  // [n_pairs][3]
+  int map_stride;
+  double *map_b, *map_a;            // [n_pairs][map_stride]
+};
+size_t align_cost_lds_bytes(int n_dims);
+void launch_align_cost(const AlignParams &p, int pairs, int max_tiles, hipStream_t stream);
+void launch_align_dp(const AlignParams &p, int pairs, hipStream_t stream);
+void launch_align_path(const AlignParams &p, int pairs, hipStream_t stream);
+int align_cost_tiles(int n_a, int n_b);
+
 }  // namespace world_hip

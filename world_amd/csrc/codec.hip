@@ -23,6 +23,7 @@
 //   modify_frames_sp / _ap / _f0 : output frame j = the blend of the two source frames around its source position,
 //                    then the warp / gain / target and scale of that frame
 // The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
+// And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end.
 #include "codec.h"
 #include "fft.h"
 
@@ -445,5 +446,7 @@ void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) 
   if (p.n <= 0) return;
   WH_BLOCKS(rt_store_coded_rows, dim3(p.n), 256, decode_sp_lds_bytes(p.lg_md), stream, p);
 }
+
+#include "align.inc"
 
 }  // namespace world_hip

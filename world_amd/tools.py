@@ -8,6 +8,8 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools synthesis params/a.f0 params/a.sp params/a.ap -o a_resynth.wav
     python -m world_amd.tools transform a.wav b.wav ... --outdir out --f0-scale 1.5 --formant-shift 1.2
     python -m world_amd.tools transform a.wav --outdir out --duration 2.5 --f0-from melody.f0
+    python -m world_amd.tools transform a.wav --outdir out --align-to b.wav       # a's voice with b's timing
+    python -m world_amd.tools mcd ref1.wav test1.wav ref2.wav test2.wav --dims 25 # mel-cepstral distortion along the DTW path
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -17,6 +19,9 @@ the device before they come back, so the D2H traffic and the files shrink by 10-
 and a speed change through the synthesis frame period) in one library call per batch; the waveforms are quantised to
 16 bits on the device, so only int16 samples come back.  With --duration or --f0-from the modification is per frame
 (world_hip_resynthesize_frames_batch): a uniform time map to the asked length, and the F0 track of another file as target.
+With --align-to the time map is the alignment of each input to another recording (world_hip_align_batch over the
+mel-cepstra of both, c0 left out), one output frame per frame of that recording.  `mcd` analyses pairs of files into coded
+records, aligns each pair on the device and prints the mel-cepstral distortion along the path.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -131,7 +136,11 @@ def _transform(a):
         outs = transform_outputs(a.wav, a.outdir)
     except ValueError as e:
         sys.exit(f"transform: {e}")
-    frames = a.duration is not None or a.f0_from is not None    # the per-frame route; without them, exactly as before
+    if a.align_to is not None and (a.duration is not None or a.time_scale != 1.0):
+        sys.exit("transform: --align-to takes its duration from the other recording; --duration and --time-scale cannot be "
+                 "combined with it")
+    # the per-frame route; without these options, exactly as before
+    frames = a.duration is not None or a.f0_from is not None or a.align_to is not None
     if a.duration is not None and not a.duration * 1000.0 / a.s >= 1.0:
         sys.exit(f"transform: --duration {a.duration} is shorter than one frame shift")
     track = None
@@ -141,6 +150,12 @@ def _transform(a):
             sys.exit(f"transform: {a.f0_from} is not a readable F0 file")
         track = read[1]
     wh = WorldHip()
+    a.other = None                                              # --align-to: the other recording, analysed once (_align_to)
+    if a.align_to is not None:
+        try:
+            a.other = dict(fs=wh.wav_layout(a.align_to)[0])
+        except Exception as e:
+            sys.exit(f"transform: --align-to {a.align_to} is not a readable WAV file ({e})")
     os.makedirs(a.outdir, exist_ok=True)
     out_of = dict(zip(a.wav, outs))
     by_rate = {}
@@ -171,14 +186,18 @@ def _resynthesize_frames(wh, a, x, fs, x_len, track):
     its own length times --time-scale), the F0 file's track spread over the same frames as the target F0"""
     import torch
     n_src = [frame_count(fs, int(n), a.s) for n in x_len]
-    if a.duration is not None:
+    aligned = None
+    if a.align_to is not None:
+        aligned = _align_to(wh, a, x, fs, x_len)
+        n_out = [aligned.shape[1]] * len(n_src)
+    elif a.duration is not None:
         n_out = [int(a.duration * 1000.0 / a.s) + 1] * len(n_src)
     else:
         n_out = [max(int((n - 1) * a.time_scale) + 1, 2) for n in n_src]
     O = max(n_out)
     time_map = torch.zeros((len(n_src), O), dtype=torch.float64, device=wh.device)
     for row, (n, m) in enumerate(zip(n_src, n_out)):
-        time_map[row, :m] = uniform_time_map(n, m, device=wh.device)
+        time_map[row, :m] = uniform_time_map(n, m, device=wh.device) if aligned is None else aligned[row]
     f0_target = None
     if track is not None:
         src = torch.from_numpy(np.ascontiguousarray(track, dtype=np.float64)).to(wh.device)[None].contiguous()
@@ -191,6 +210,88 @@ def _resynthesize_frames(wh, a, x, fs, x_len, track):
     return wh.resynthesize_frames(x, fs, x_len=x_len, n_out=n_out, time_map=time_map, f0_target=f0_target,
                                   f0_scale=a.f0_scale, formant_shift=a.formant_shift, frame_period=a.s, f0_floor=a.f,
                                   f0_ceil=a.c)
+
+
+ALIGN_DIMS = 25       # mel-cepstral coefficients the alignments are made from (c0 is left out unless asked for)
+
+
+def _coded_block(wh, x, fs, x_len, frame_period, dims, f0_floor=71.0, f0_ceil=800.0):
+    """analyze_coded of one batch -> (block [rows, cols], first row of every utterance, frames of every utterance)"""
+    import torch
+    nf = np.array([frame_count(fs, int(n), frame_period) for n in x_len], dtype=np.int64)
+    cols = wh.lib.world_hip_coded_columns(fs, dims)
+    block = torch.zeros((int(nf.sum()), cols), dtype=torch.float64, device=wh.device)
+    wh.analyze_coded(x, fs, block, x_len=x_len, frame_period=frame_period, f0_floor=f0_floor, f0_ceil=f0_ceil,
+                     number_of_dimensions=dims)
+    return block, np.concatenate([[0], np.cumsum(nf)[:-1]]), nf
+
+
+def _cepstra(block, dims, keep_c0):
+    return block[:, 2:2 + dims] if keep_c0 else block[:, 3:2 + dims]
+
+
+def _align_to(wh, a, x, fs, x_len):
+    """--align-to: the time map [B, n_other] that gives every input the timing of the other recording -- the mid-points
+    of the DTW path between the input's and the other's mel-cepstra, per frame of the other"""
+    if a.other["fs"] != fs:
+        sys.exit(f"transform: {a.align_to} has another sampling rate ({a.other['fs']} Hz) than the {fs} Hz inputs")
+    if "block" not in a.other:                                  # (one rate only gets here: once for all batches)
+        other, other_len = _load_batch(wh, [a.align_to])
+        a.other["block"], a.other["row"], a.other["nf"] = _coded_block(wh, other, fs, other_len, a.s, ALIGN_DIMS, a.f, a.c)
+    blk_b, row_b, nf_b = a.other["block"], a.other["row"], a.other["nf"]
+    blk_a, row_a, nf_a = _coded_block(wh, x, fs, x_len, a.s, ALIGN_DIMS, a.f, a.c)
+    B = len(nf_a)
+    _, _, _, map_b, _ = wh.align(_cepstra(blk_a, ALIGN_DIMS, False), _cepstra(blk_b, ALIGN_DIMS, False), nf_a,
+                                 np.repeat(nf_b, B), a_row=row_a, b_row=np.repeat(row_b, B), want_path=False)
+    return map_b
+
+
+def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch=64):
+    """[(ref.wav, test.wav)] -> [(frames of ref, frames of test, path length, MCD in dB)]: every file analysed once into
+    coded records (batches per sampling rate), every pair aligned on the device, one align call per rate"""
+    by_rate, rate_of = {}, {}
+    for path in dict.fromkeys(p for pair in pairs for p in pair):
+        rate_of[path] = wh.wav_layout(path)[0]
+        by_rate.setdefault(rate_of[path], []).append(path)
+    for ref, test in pairs:
+        if rate_of[ref] != rate_of[test]:
+            raise ValueError(f"{ref} and {test} have different sampling rates")
+    out = {}
+    for fs, group in sorted(by_rate.items()):
+        import torch
+        blocks, where, at = [], {}, 0
+        for lo in range(0, len(group), batch):
+            chunk = group[lo:lo + batch]
+            x, x_len = _load_batch(wh, chunk)
+            block, first, nf = _coded_block(wh, x, fs, x_len, frame_period, dims)
+            blocks.append(block)
+            for path, r, n in zip(chunk, first, nf):
+                where[path] = (at + int(r), int(n))
+            at += block.shape[0]
+        block = torch.cat(blocks) if len(blocks) > 1 else blocks[0]
+        mine = [pr for pr in pairs if rate_of[pr[0]] == fs]
+        feats = _cepstra(block, dims, keep_c0)
+        _, path_len, summary, _, _ = wh.align(feats, feats, [where[r][1] for r, _ in mine], [where[t][1] for _, t in mine],
+                                              a_row=[where[r][0] for r, _ in mine], b_row=[where[t][0] for _, t in mine],
+                                              want_path=False)
+        summary = summary.cpu().numpy()
+        for u, pr in enumerate(mine):
+            out[pr] = (where[pr[0]][1], where[pr[1]][1], int(summary[u, 1]), float(summary[u, 2]))
+    return [out[pr] for pr in pairs]
+
+
+def _mcd(a):
+    if len(a.wav) % 2:
+        sys.exit("mcd: the files come in pairs: REF.wav TEST.wav [REF2.wav TEST2.wav ...]")
+    if a.dims < (1 if a.keep_c0 else 2):
+        sys.exit(f"mcd: --dims {a.dims} leaves no coefficient to compare")
+    pairs = list(zip(a.wav[0::2], a.wav[1::2]))
+    try:
+        results = mcd_pairs(WorldHip(), pairs, a.dims, a.keep_c0, a.s, a.batch)
+    except ValueError as e:
+        sys.exit(f"mcd: {e}")
+    for (ref, test), (na, nb, K, mcd) in zip(pairs, results):
+        print(f"{ref} {test}: frames {na} {nb} path {K} mcd {mcd:.6f} dB")
 
 
 def main(argv=None):
@@ -226,11 +327,21 @@ def main(argv=None):
                     help="every output lasts SECONDS: the frames are spread by a uniform time map (replaces --time-scale)")
     tr.add_argument("--f0-from", default=None, metavar="FILE.f0",
                     help="voiced frames take their F0 from this F0 file's track, spread over the output frames")
+    tr.add_argument("--align-to", default=None, metavar="OTHER.wav",
+                    help="every output takes OTHER's timing: the time map is the DTW alignment of the input to OTHER, one "
+                         "output frame per frame of OTHER (composes with --f0-from)")
     tr.add_argument("-f", type=float, default=71.0, help="floor of the F0 range (Hz)")
     tr.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
     tr.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
     tr.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
     tr.set_defaults(run=_transform)
+    mc = sub.add_parser("mcd", help="pairs of WAV files -> mel-cepstral distortion along the DTW path")
+    mc.add_argument("wav", nargs="+", metavar="REF.wav TEST.wav")
+    mc.add_argument("--dims", type=int, default=ALIGN_DIMS, help="mel-cepstral coefficients per frame, c0 included")
+    mc.add_argument("--keep-c0", action="store_true", help="compare c0 too (by default the energy term is left out)")
+    mc.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
+    mc.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
+    mc.set_defaults(run=_mcd)
     a = p.parse_args(argv)
     a.run(a)
 
