@@ -717,6 +717,58 @@ WORLD_HIP_API int world_hip_align_batch(WorldHipContext *ctx, int n_pairs, int n
                                         double *d_map_a);
 WORLD_HIP_API int world_hip_align_workspace_cells(void);   /* the per-pair cell limit; host arithmetic */
 
+/* Morph of two aligned utterances: the frames that lie between A and B -- a time axis part-way along the warping path,
+ * F0 and spectral envelope interpolated geometrically between the aligned frames, aperiodicity blended, each with a rate
+ * of its own that may change from frame to frame.  Rate 0 is A, rate 1 is B.  Pair u has n_a[u] >= 1 frames of A (arrays
+ * [n_pairs][a_stride]..., as world_hip_analyze_batch writes them), n_b[u] >= 1 frames of B ([n_pairs][b_stride]...) and
+ * the path world_hip_align_batch wrote for it (d_path [n_pairs][p_stride][2], d_path_len [n_pairs]; DEVICE).  n_a, n_b and
+ * morphs are HOST arrays of n_pairs.  The output arrays are [n_pairs][o_stride]...; pair u gets
+ * n_out[u] = world_hip_morph_length(n_a[u], n_b[u], morphs[u].time_rate) frames, and o_stride must hold them.
+ *   1. time axis.  Path cell k = (i_k, j_k), k = 0 .. K - 1, lies at t_k = (1.0 - r) * i_k + r * j_k, r = time_rate: each
+ *      operation rounded on its own (no fused multiply-add), so t is non-decreasing in k for every r.
+ *      world_hip_morph_length = floor((1.0 - r) * (n_a - 1) + r * (n_b - 1)) + 1, the same expression at the last cell
+ *      (-1 for a count below 1 or an r outside [0, 1]; host arithmetic).  For n_a == n_b that is n_a, or n_a - 1 at a
+ *      rate where the rounded sum falls short of n_a - 1.
+ *   2. positions.  Output frame m (as a double): lo = the first k with t_k >= m.  If t_lo == m: hi = the last k with
+ *      t_k == m, sA = 0.5 * (i_lo + i_hi), sB = 0.5 * (j_lo + j_hi).  Otherwise w = (m - t_{lo-1}) / (t_lo - t_{lo-1}),
+ *      sA = i_{lo-1} + w * (i_lo - i_{lo-1}), sB likewise.  So r = 0 gives sA = m and sB = world_hip_align_batch's
+ *      d_map_a[m] bit for bit, r = 1 gives sB = m and sA = d_map_b[m].  d_path == NULL: the pair is aligned frame for
+ *      frame, n_a[u] must equal n_b[u], sA = sB = m.  sA and sB are clamped to [0, n_a - 1] and [0, n_b - 1] as
+ *      world_hip_modify_frames_batch clamps a time map (never needed on a path world_hip_align_batch wrote).
+ *   3. rows at a position: row a = world_hip_modify_frames_batch's step 2 at s = sA on A's rows (k = floor(s), w = s - k;
+ *      row k bit for bit when w == 0 or k is the last frame, else (1.0 - w) * row[k][i] + w * row[k + 1][i]); row b the
+ *      same at sB on B's rows.  fA and fB: its step 3 (the F0 between two frames) at sA and sB.
+ *   4. rates.  rho = the curve's value at frame m where that curve is given (DEVICE [n_pairs][o_stride]; a value that is
+ *      not finite counts as 0, any other is clamped to [0, 1]), else the pair's value in morphs.
+ *   5. spectral envelope: rho == 0 gives row a bit for bit, rho == 1 row b; otherwise
+ *      exp((1.0 - rho) * log(a_i) + rho * log(b_i)).  A bin that is not positive gives what IEEE gives, in that bin alone.
+ *   6. aperiodicity: the same end cases; otherwise (1.0 - rho) * a_i + rho * b_i -- a convex combination, so it stays
+ *      within GetSafeAperiodicity's bounds whenever the inputs do.
+ *   7. F0 (voiced = finite and > 0): rho == 0 gives fA, rho == 1 fB, bit for bit; both voiced:
+ *      exp((1.0 - rho) * log(fA) + rho * log(fB)); exactly one voiced: that F0 if its weight (1 - rho for A, rho for B) is
+ *      above 0.5, else 0 (the reference's interpolated_vuv > 0.5); neither: 0.
+ * Each triple (d_f0_a, d_f0_b, d_f0_out), (d_sp_...), (d_ap_...) is optional as a whole: all three pointers or none.
+ * d_pos_a / d_pos_b (DEVICE [n_pairs][o_stride], each may be NULL) receive sA / sB; where one is NULL the positions live
+ * in n_pairs * o_stride doubles of the workspace (world_hip_workspace_bytes counts them).  Frames and rows at or beyond
+ * n_out[u] are never written.  Refused before any GPU work, with nothing written: n_pairs outside [1, 65535], NULL n_a,
+ * n_b or morphs, a count below 1 or above its stride, a rate in morphs outside [0, 1] or not finite, o_stride below an
+ * n_out[u], a path without d_path_len or with p_stride < n_a[u] + n_b[u] - 1, no path and n_a[u] != n_b[u], a triple given
+ * in part, fs < 1 or fft_size not a power of two in [128, 8192] when rows are given, an output that overlaps an input or
+ * another output.  A path read from the device cannot be checked before the launch: K is clamped into [1, p_stride] and
+ * every index into its utterance (should no k have t_k >= m, lo = K - 1; should lo be 0 with t_0 > m, the position is cell
+ * 0), so a path world_hip_align_batch did not write gives positions that mean nothing but stay in bounds, and no other
+ * pair is affected.  Stream order and errors as the other batched calls; the per-pair arrays go through the context's
+ * small-array store, so after one eager call of a shape the call copies nothing from the host and can be captured. */
+typedef struct { double time_rate, f0_rate, sp_rate, ap_rate; } WorldHipMorph;
+typedef struct { const double *d_f0_rate, *d_sp_rate, *d_ap_rate; } WorldHipMorphCurves;
+WORLD_HIP_API int world_hip_morph_length(int n_a, int n_b, double time_rate);
+WORLD_HIP_API int world_hip_morph_batch(WorldHipContext *ctx, int n_pairs, int fs, int fft_size, const int *n_a, int a_stride,
+                                        const double *d_f0_a, const double *d_sp_a, const double *d_ap_a, const int *n_b,
+                                        int b_stride, const double *d_f0_b, const double *d_sp_b, const double *d_ap_b,
+                                        int p_stride, const int *d_path, const int *d_path_len, const WorldHipMorph *morphs,
+                                        const WorldHipMorphCurves *curves, int o_stride, double *d_f0_out, double *d_sp_out,
+                                        double *d_ap_out, double *d_pos_a, double *d_pos_b);
+
 /* Real-time synthesis, batched (reference src/synthesisrealtime.cpp; the drop-in WorldSynthesizer above is built on it).
  * One object serves n_streams independent streams with one fs, frame_period (ms), fft_size, buffer_size and ring size
  * number_of_pointers; every stream behaves exactly as one reference synthesiser: same pulses, same return values, its own

@@ -69,6 +69,23 @@ class WorldHipFrameCurves(C.Structure):    # include/world_hip.h: device arrays 
     _fields_ = [(name, C.c_void_p) for name in ("d_time_map", "d_f0_target", "d_f0_scale", "d_formant_shift", "d_ap_gain")]
 
 
+class WorldHipMorph(C.Structure):          # include/world_hip.h: one pair's rates, each within [0, 1] (0 = A, 1 = B)
+    _fields_ = [(name, C.c_double) for name in ("time_rate", "f0_rate", "sp_rate", "ap_rate")]
+
+
+class WorldHipMorphCurves(C.Structure):    # include/world_hip.h: device arrays [n_pairs][o_stride], or NULL
+    _fields_ = [(name, C.c_void_p) for name in ("d_f0_rate", "d_sp_rate", "d_ap_rate")]
+
+
+def morphs(n_pairs, time_rate=0.5, f0_rate=0.5, sp_rate=0.5, ap_rate=0.5):
+    """WorldHipMorph[n_pairs] from scalars or per-pair sequences"""
+    cols = [np.broadcast_to(np.asarray(v, dtype=np.float64), (n_pairs,)) for v in (time_rate, f0_rate, sp_rate, ap_rate)]
+    out = (WorldHipMorph * n_pairs)()
+    for u in range(n_pairs):
+        out[u].time_rate, out[u].f0_rate, out[u].sp_rate, out[u].ap_rate = (float(c[u]) for c in cols)
+    return out
+
+
 def uniform_time_map(n_src, n_out, device="cuda"):
     """Time map [n_out] (float64, on `device`) that spreads n_src source frames evenly over n_out output frames: first
     onto first, last onto last."""
@@ -358,6 +375,11 @@ def load_library(path=LIB_PATH):
         lib.world_hip_align_batch.argtypes = [vp, C.c_int, C.c_int, vp, lp, _ip, C.c_int, vp, lp, _ip, C.c_int, C.c_int,
                                               vp, vp, vp, C.c_int, vp, vp]
         lib.world_hip_align_workspace_cells.argtypes = []
+    if hasattr(lib, "world_hip_morph_batch"):                        # (likewise)
+        lib.world_hip_morph_length.argtypes = [C.c_int, C.c_int, C.c_double]
+        lib.world_hip_morph_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp, vp, vp, _ip, C.c_int, vp, vp, vp,
+                                              C.c_int, vp, vp, C.POINTER(WorldHipMorph), C.POINTER(WorldHipMorphCurves),
+                                              C.c_int, vp, vp, vp, vp, vp]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -1158,6 +1180,101 @@ class WorldHip:
                                                    path.data_ptr() if want_path else None, path_len.data_ptr(),
                                                    summary.data_ptr(), M, maps[0].data_ptr(), maps[1].data_ptr()), "align")
         return path, path_len, summary, maps[0, :, :Mb], maps[1, :, :Ma]
+
+    # ---- morph of two aligned utterances (include/world_hip.h: world_hip_morph_batch) ----
+    def _morph_lib(self):
+        if not hasattr(self.lib, "world_hip_morph_batch"):
+            raise RuntimeError("this libworld_hip.so has no morph (world_hip_morph_batch)")
+        return self.lib
+
+    def morph_length(self, n_a, n_b, time_rate=0.5):
+        """output frames of a morph of n_a against n_b frames at time_rate (host arithmetic)"""
+        n = self._morph_lib().world_hip_morph_length(int(n_a), int(n_b), float(time_rate))
+        if n < 1:
+            raise ValueError(f"morph_length: {n_a} x {n_b} frames at time_rate {time_rate}")
+        return n
+
+    def morph(self, a, b, n_a, n_b, fs, fft_size, path=None, path_len=None, rate=0.5, time_rate=None, f0_rate=None,
+              sp_rate=None, ap_rate=None, want_positions=False, validate=True, out=None):
+        """The frames between two aligned utterances.  a, b = (f0 [P, F], sp [P, F, fft/2+1], ap likewise) of A and B
+        (float64, device; a member may be None on both sides), n_a / n_b their frame counts, path / path_len what align()
+        returned (None: aligned frame for frame, n_a == n_b).  Rates (0 = A, 1 = B; default: `rate`): time_rate a scalar
+        or one value per pair; f0_rate, sp_rate, ap_rate a scalar, one value per pair, or a curve -- a float64 device
+        tensor [P, O] or [O] with one value per output frame.  -> (f0', sp', ap', n_out) with n_out[u] =
+        morph_length(n_a[u], n_b[u], time_rate[u]) frames each ([P, O] / [P, O, fft/2+1], zero beyond); with
+        want_positions also (pos_a, pos_b) [P, O], the source positions of every output frame.  out: an (f0', sp', ap')
+        triple of the caller's to write into (frames beyond n_out are left as they are)."""
+        t = self.torch
+        L = self._morph_lib()
+        na = np.ascontiguousarray(np.atleast_1d(n_a), dtype=np.int32)
+        nb_ = np.ascontiguousarray(np.atleast_1d(n_b), dtype=np.int32)
+        P = len(na)
+        assert len(nb_) == P and P >= 1
+        bins = fft_size // 2 + 1
+        Fa = Fb = None
+        for x, y, dims in zip(a, b, (2, 3, 3)):
+            assert (x is None) == (y is None), "morph: give a member on both sides or on neither"
+            for z in (x, y):
+                if z is not None:
+                    assert z.dtype == t.float64 and z.dim() == dims and z.is_contiguous() and z.device == self.device
+                    assert z.shape[0] == P and (dims == 2 or z.shape[2] == bins)
+            if x is not None:
+                Fa, Fb = (x.shape[1] if Fa is None else Fa), (y.shape[1] if Fb is None else Fb)
+                assert x.shape[1] == Fa and y.shape[1] == Fb, "morph: the arrays of one side disagree about its frames"
+        assert Fa is not None, "morph: nothing to morph"
+        tr = np.broadcast_to(np.asarray(rate if time_rate is None else time_rate, dtype=np.float64), (P,))
+        no = np.array([L.world_hip_morph_length(int(x), int(y), float(r)) for x, y, r in zip(na, nb_, tr)], dtype=np.int32)
+        if int(no.min()) < 1:
+            raise ValueError("morph: frame counts below 1 or a time_rate outside [0, 1]")
+        O = int(no.max())
+        keep, scalars = {}, {}
+        for name, v in (("f0_rate", f0_rate), ("sp_rate", sp_rate), ("ap_rate", ap_rate)):
+            v = rate if v is None else v
+            if t.is_tensor(v):
+                assert v.dtype == t.float64 and v.device == self.device, f"{name}: a float64 tensor on {self.device}"
+                v = v[None].expand(P, -1) if v.dim() == 1 else v
+                assert v.dim() == 2 and v.shape[0] == P and v.shape[1] >= O, f"{name}: [P, O] or [O] with O >= {O}"
+                keep["d_" + name] = v
+                scalars[name] = 0.0
+            else:
+                scalars[name] = v
+        if keep:
+            O = max(O, max(v.shape[1] for v in keep.values()))
+            assert all(v.shape[1] == O for v in keep.values()), "the curves disagree about the number of output frames"
+            keep = {k: v.contiguous() for k, v in keep.items()}
+            if validate:                                    # one reduction, one synchronisation
+                live = t.arange(O, device=self.device)[None] < t.as_tensor(no, device=self.device)[:, None]
+                bad = t.zeros((), dtype=t.bool, device=self.device)
+                for v in keep.values():
+                    bad = bad | ((~t.isfinite(v) | (v < 0) | (v > 1)) & live).any()
+                if bool(bad):
+                    raise ValueError("a rate curve holds a value outside [0, 1] or not finite")
+        ms = morphs(P, tr, scalars["f0_rate"], scalars["sp_rate"], scalars["ap_rate"])
+        cv = WorldHipMorphCurves(**{k: v.data_ptr() for k, v in keep.items()})
+        if path is not None:
+            assert path_len is not None and path.dtype == t.int32 and path_len.dtype == t.int32
+            assert path.dim() == 3 and path.shape[0] == P and path.shape[2] == 2 and path.is_contiguous() and path_len.is_contiguous()
+            assert path.device == self.device and path_len.device == self.device and path_len.shape == (P,)
+        if out is not None:
+            outs = tuple(out)
+            for x, o in zip(a, outs):
+                assert (x is None) == (o is None)
+                if o is not None:
+                    assert o.dtype == t.float64 and o.is_contiguous() and o.device == self.device
+                    assert o.shape == (P, O) + tuple(x.shape[2:])
+        else:
+            outs = tuple(t.zeros((P, O) + tuple(x.shape[2:]), dtype=t.float64, device=self.device) if x is not None else None
+                         for x in a)
+        pos = t.zeros((2, P, O), dtype=t.float64, device=self.device) if want_positions else None
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        self._check(L.world_hip_morph_batch(self._context(), P, int(fs), int(fft_size), na.ctypes.data_as(_ip), Fa, ptr(a[0]),
+                                            ptr(a[1]), ptr(a[2]), nb_.ctypes.data_as(_ip), Fb, ptr(b[0]), ptr(b[1]), ptr(b[2]),
+                                            path.shape[1] if path is not None else 0, ptr(path),
+                                            ptr(path_len) if path is not None else None, ms, C.byref(cv) if keep else None, O,
+                                            ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+                                            pos[0].data_ptr() if want_positions else None,
+                                            pos[1].data_ptr() if want_positions else None), "morph")
+        return (*outs, no, pos[0], pos[1]) if want_positions else (*outs, no)
 
     # ---- the per-frame FFT in isolation (include/world_hip.h: world_hip_probe_rfft) ----
     def probe_rfft(self, x, max_lr=3, threads=0, out=None, static_plan=False):

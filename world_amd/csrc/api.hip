@@ -1850,6 +1850,106 @@ static void run_align(WorldHipContext *c, int n_pairs, int n_dims, const double 
   }
 }
 
+// Morph of two aligned utterances (include/world_hip.h: world_hip_morph_batch; morph.inc).  Everything the host can know
+// is refused before any GPU work; the path and the curves live on the device and are made harmless in the kernels.
+static int morph_length(int n_a, int n_b, double time_rate) {
+#pragma clang fp contract(off)
+  if (n_a < 1 || n_b < 1 || !(time_rate >= 0.0 && time_rate <= 1.0)) return -1;
+  return static_cast<int>((1.0 - time_rate) * (n_a - 1) + time_rate * (n_b - 1)) + 1;   // (>= 0: the floor)
+}
+
+static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, const int *n_a, int a_stride, const double *d_f0_a,
+                      const double *d_sp_a, const double *d_ap_a, const int *n_b, int b_stride, const double *d_f0_b,
+                      const double *d_sp_b, const double *d_ap_b, int p_stride, const int *d_path, const int *d_path_len,
+                      const WorldHipMorph *morphs, const WorldHipMorphCurves *curves, int o_stride, double *d_f0_out,
+                      double *d_sp_out, double *d_ap_out, double *d_pos_a, double *d_pos_b) {
+  if (n_pairs < 1 || n_pairs > 65535) fail("morph: n_pairs %d outside [1, 65535]", n_pairs);
+  if (!n_a || !n_b || !morphs) fail("morph: null n_a / n_b / morphs");
+  if ((!d_f0_a != !d_f0_b) || (!d_f0_a != !d_f0_out)) fail("morph: give d_f0_a, d_f0_b and d_f0_out, or none of them");
+  if ((!d_sp_a != !d_sp_b) || (!d_sp_a != !d_sp_out)) fail("morph: give d_sp_a, d_sp_b and d_sp_out, or none of them");
+  if ((!d_ap_a != !d_ap_b) || (!d_ap_a != !d_ap_out)) fail("morph: give d_ap_a, d_ap_b and d_ap_out, or none of them");
+  const bool with_f0 = d_f0_a != nullptr, with_sp = d_sp_a != nullptr, with_ap = d_ap_a != nullptr;
+  if (with_sp || with_ap) {
+    if (fs <= 0) fail("morph: fs must be positive");
+    int lg = 0;
+    while ((1 << lg) < fft_size) ++lg;
+    if (fft_size < 128 || fft_size > 8192 || (1 << lg) != fft_size)
+      fail("morph: fft_size %d is not a power of two in [128, 8192]", fft_size);
+  }
+  if (d_path && !d_path_len) fail("morph: a path needs d_path_len (null)");
+  std::vector<int> n_out(n_pairs);
+  std::vector<double> rate(4 * (size_t)n_pairs);
+  int max_out = 0;
+  for (int u = 0; u < n_pairs; ++u) {
+    if (n_a[u] < 1 || n_b[u] < 1) fail("morph: pair %d has %d x %d frames; each side needs one", u, n_a[u], n_b[u]);
+    if (n_a[u] > a_stride || n_b[u] > b_stride)
+      fail("morph: pair %d has %d x %d frames, beyond the strides (%d, %d)", u, n_a[u], n_b[u], a_stride, b_stride);
+    const double r[4] = {morphs[u].time_rate, morphs[u].f0_rate, morphs[u].sp_rate, morphs[u].ap_rate};
+    for (int q = 0; q < 4; ++q) {
+      if (!(r[q] >= 0.0 && r[q] <= 1.0)) fail("morph: pair %d: rate %g outside [0, 1]", u, r[q]);
+      rate[4 * (size_t)u + q] = r[q];
+    }
+    if (d_path && (long long)p_stride < (long long)n_a[u] + n_b[u] - 1)
+      fail("morph: p_stride %d cannot hold pair %d's longest path (%d + %d - 1)", p_stride, u, n_a[u], n_b[u]);
+    if (!d_path && n_a[u] != n_b[u])
+      fail("morph: pair %d: without a path n_a (%d) must equal n_b (%d)", u, n_a[u], n_b[u]);
+    n_out[u] = morph_length(n_a[u], n_b[u], r[0]);
+    if (n_out[u] > o_stride) fail("morph: o_stride %d below pair %d's %d output frames", o_stride, u, n_out[u]);
+    max_out = std::max(max_out, n_out[u]);
+  }
+  // no output may overlap an input or another output: byte ranges of everything the call touches
+  const WorldHipMorphCurves none = {nullptr, nullptr, nullptr};
+  const WorldHipMorphCurves &cv = curves ? *curves : none;
+  {
+    struct Range { const char *lo, *hi; const char *name; };
+    const size_t nbins = (size_t)(fft_size / 2 + 1) * sizeof(double), P = (size_t)n_pairs;
+    auto range = [](const void *p, size_t bytes, const char *name) {
+      return Range{static_cast<const char *>(p), static_cast<const char *>(p) + bytes, name};
+    };
+    std::vector<Range> in, out;
+    auto add = [&](std::vector<Range> &v, const void *p, size_t bytes, const char *name) { if (p) v.push_back(range(p, bytes, name)); };
+    add(in, d_f0_a, P * a_stride * sizeof(double), "d_f0_a"); add(in, d_f0_b, P * b_stride * sizeof(double), "d_f0_b");
+    add(in, d_sp_a, P * a_stride * nbins, "d_sp_a"); add(in, d_sp_b, P * b_stride * nbins, "d_sp_b");
+    add(in, d_ap_a, P * a_stride * nbins, "d_ap_a"); add(in, d_ap_b, P * b_stride * nbins, "d_ap_b");
+    add(in, d_path, P * p_stride * 2 * sizeof(int), "d_path"); add(in, d_path_len, P * sizeof(int), "d_path_len");
+    add(in, cv.d_f0_rate, P * o_stride * sizeof(double), "d_f0_rate"); add(in, cv.d_sp_rate, P * o_stride * sizeof(double), "d_sp_rate");
+    add(in, cv.d_ap_rate, P * o_stride * sizeof(double), "d_ap_rate");
+    add(out, d_f0_out, P * o_stride * sizeof(double), "d_f0_out"); add(out, d_sp_out, P * o_stride * nbins, "d_sp_out");
+    add(out, d_ap_out, P * o_stride * nbins, "d_ap_out");
+    add(out, d_pos_a, P * o_stride * sizeof(double), "d_pos_a"); add(out, d_pos_b, P * o_stride * sizeof(double), "d_pos_b");
+    for (size_t x = 0; x < out.size(); ++x) {
+      for (const Range &r : in)
+        if (out[x].lo < r.hi && r.lo < out[x].hi) fail("morph: %s overlaps %s; no output may alias an input", out[x].name, r.name);
+      for (size_t y = x + 1; y < out.size(); ++y)
+        if (out[x].lo < out[y].hi && out[y].lo < out[x].hi) fail("morph: %s overlaps %s", out[x].name, out[y].name);
+    }
+  }
+  if (!with_f0 && !with_sp && !with_ap && !d_pos_a && !d_pos_b) return;
+  MorphParams p;
+  p.pos_a = d_pos_a; p.pos_b = d_pos_b;
+  if (!d_pos_a || !d_pos_b)
+    begin_stage(c, [&](Arena &a) {
+      if (!d_pos_a) p.pos_a = a.take<double>((size_t)n_pairs * o_stride);
+      if (!d_pos_b) p.pos_b = a.take<double>((size_t)n_pairs * o_stride);
+    });
+  else
+    open_uploads(c);                                        // (no workspace: prepared offsets stay valid)
+  p.n_pairs = n_pairs; p.fft_size = fft_size;
+  p.a_stride = a_stride; p.b_stride = b_stride; p.o_stride = o_stride; p.p_stride = p_stride;
+  p.n_a = upload(c, std::vector<int>(n_a, n_a + n_pairs));
+  p.n_b = upload(c, std::vector<int>(n_b, n_b + n_pairs));
+  p.n_out = upload(c, n_out);
+  p.rate = upload(c, rate);
+  p.path = d_path; p.path_len = d_path_len;
+  p.f0_curve = cv.d_f0_rate; p.sp_curve = cv.d_sp_rate; p.ap_curve = cv.d_ap_rate;
+  p.f0_a = d_f0_a; p.sp_a = d_sp_a; p.ap_a = d_ap_a; p.f0_b = d_f0_b; p.sp_b = d_sp_b; p.ap_b = d_ap_b;
+  p.f0_out = d_f0_out; p.sp_out = d_sp_out; p.ap_out = d_ap_out;
+  launch_morph_positions(p, max_out, c->stream);
+  if (with_sp) launch_morph_frames_sp(p, max_out, c->stream);
+  if (with_ap) launch_morph_frames_ap(p, max_out, c->stream);
+  if (with_f0) launch_morph_frames_f0(p, max_out, c->stream);
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2520,6 +2620,17 @@ int world_hip_align_batch(WorldHipContext *c, int n_pairs, int n_dims, const dou
   });
 }
 int world_hip_align_workspace_cells(void) { return (int)kAlignCells; }
+int world_hip_morph_length(int n_a, int n_b, double time_rate) { return morph_length(n_a, n_b, time_rate); }
+int world_hip_morph_batch(WorldHipContext *c, int n_pairs, int fs, int fft_size, const int *n_a, int a_stride,
+                          const double *d_f0_a, const double *d_sp_a, const double *d_ap_a, const int *n_b, int b_stride,
+                          const double *d_f0_b, const double *d_sp_b, const double *d_ap_b, int p_stride, const int *d_path,
+                          const int *d_path_len, const WorldHipMorph *morphs, const WorldHipMorphCurves *curves, int o_stride,
+                          double *d_f0_out, double *d_sp_out, double *d_ap_out, double *d_pos_a, double *d_pos_b) {
+  return guarded(c, [&] {
+    run_morph(c, n_pairs, fs, fft_size, n_a, a_stride, d_f0_a, d_sp_a, d_ap_a, n_b, b_stride, d_f0_b, d_sp_b, d_ap_b, p_stride,
+              d_path, d_path_len, morphs, curves, o_stride, d_f0_out, d_sp_out, d_ap_out, d_pos_a, d_pos_b);
+  });
+}
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||
       !(time_scale > 0))

@@ -146,4 +146,26 @@ void launch_align_dp(const AlignParams &p, int pairs, hipStream_t stream);
 void launch_align_path(const AlignParams &p, int pairs, hipStream_t stream);
 int align_cost_tiles(int n_a, int n_b);
 
+// Morph of two aligned utterances (world_hip_morph_batch; morph.inc).  Pair u: n_a[u] frames of A ([n_pairs][a_stride]...),
+// n_b[u] of B, n_out[u] output frames ([n_pairs][o_stride]...).  morph_positions turns the pair's warping path into the
+// two source positions of every output frame (pos_a / pos_b: the caller's arrays or workspace); the three row kernels
+// read them as modify_frames reads a time map.  Rates: rate[4 u + {0, 1, 2, 3}] = the pair's time, f0, sp and ap rate
+// (all within [0, 1]: the host refuses anything else); a curve ([n_pairs][o_stride] or nullptr) replaces its rate per frame.
+struct MorphParams {
+  int n_pairs, fft_size;
+  int a_stride, b_stride, o_stride, p_stride;
+  const int *n_a, *n_b, *n_out;     // [n_pairs] (device, as every array below)
+  const int *path;                  // [n_pairs][p_stride][2] as align_path wrote it, or nullptr: frame m of A belongs to frame m of B
+  const int *path_len;              // [n_pairs]
+  const double *rate;               // [n_pairs][4]
+  const double *f0_curve, *sp_curve, *ap_curve;
+  const double *f0_a, *sp_a, *ap_a, *f0_b, *sp_b, *ap_b;
+  double *f0_out, *sp_out, *ap_out;
+  double *pos_a, *pos_b;            // [n_pairs][o_stride]
+};
+void launch_morph_positions(const MorphParams &p, int max_out, hipStream_t stream);
+void launch_morph_frames_sp(const MorphParams &p, int max_out, hipStream_t stream);
+void launch_morph_frames_ap(const MorphParams &p, int max_out, hipStream_t stream);
+void launch_morph_frames_f0(const MorphParams &p, int max_out, hipStream_t stream);
+
 }  // namespace world_hip

@@ -23,7 +23,8 @@
 //   modify_frames_sp / _ap / _f0 : output frame j = the blend of the two source frames around its source position,
 //                    then the warp / gain / target and scale of that frame
 // The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
-// And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end.
+// And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end;
+// behind it morph.inc, the frames between two utterances aligned that way (world_hip_morph_batch).
 #include "codec.h"
 #include "fft.h"
 
@@ -448,5 +449,6 @@ void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) 
 }
 
 #include "align.inc"
+#include "morph.inc"
 
 }  // namespace world_hip

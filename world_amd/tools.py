@@ -10,6 +10,7 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools transform a.wav --outdir out --duration 2.5 --f0-from melody.f0
     python -m world_amd.tools transform a.wav --outdir out --align-to b.wav       # a's voice with b's timing
     python -m world_amd.tools mcd ref1.wav test1.wav ref2.wav test2.wav --dims 25 # mel-cepstral distortion along the DTW path
+    python -m world_amd.tools morph a.wav b.wav -o out.wav --rate 0.3             # 70 % a, 30 % b; --fade: a cross-fades into b
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -21,7 +22,8 @@ and a speed change through the synthesis frame period) in one library call per b
 (world_hip_resynthesize_frames_batch): a uniform time map to the asked length, and the F0 track of another file as target.
 With --align-to the time map is the alignment of each input to another recording (world_hip_align_batch over the
 mel-cepstra of both, c0 left out), one output frame per frame of that recording.  `mcd` analyses pairs of files into coded
-records, aligns each pair on the device and prints the mel-cepstral distortion along the path.
+records, aligns each pair on the device and prints the mel-cepstral distortion along the path.  `morph` analyses two files, aligns them the same way and writes the frames
+between them (world_hip_morph_batch): timing, F0, envelope and aperiodicity each part-way from the first file to the second.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -294,6 +296,55 @@ def _mcd(a):
         print(f"{ref} {test}: frames {na} {nb} path {K} mcd {mcd:.6f} dB")
 
 
+def morph_waves(wh, xa, xb, fs, rate=0.5, time_rate=None, f0_rate=None, sp_rate=None, ap_rate=None, fade=False,
+                frame_period=5.0, f0_floor=71.0, f0_ceil=800.0):
+    """Two waveforms (1-D float64 device tensors of one sampling rate) -> (y [1, Y], Y): both analysed, their envelopes
+    coded to ALIGN_DIMS mel-cepstra and aligned without c0, the frames between them morphed and synthesised at the analysis
+    frame period.  fade: the three feature rates rise linearly from 0 to 1 over the output.  Nothing but the two inputs
+    and the output crosses the bus."""
+    import torch
+    fft_size = cheaptrick_fft_size(fs, 71.0)
+    sides = []
+    for x in (xa, xb):
+        _, f0, sp, ap, nf = wh.analyze(x[None].contiguous(), fs, frame_period=frame_period, f0_floor=f0_floor, f0_ceil=f0_ceil)
+        sides.append(((f0, sp, ap), nf, wh.code_spectral_envelope(sp, fs, fft_size, ALIGN_DIMS)))
+    (a, nf_a, mc_a), (b, nf_b, mc_b) = sides
+    path, path_len, _, _, _ = wh.align(mc_a[:, :, 1:], mc_b[:, :, 1:], nf_a, nf_b)
+    time_rate = rate if time_rate is None else time_rate
+    n_out = wh.morph_length(int(nf_a[0]), int(nf_b[0]), time_rate)
+    if n_out < 2:
+        raise ValueError(f"the morph has {n_out} frame(s); synthesis needs 2")
+    if fade:
+        f0_rate = sp_rate = ap_rate = torch.linspace(0.0, 1.0, n_out, dtype=torch.float64, device=wh.device)
+    f0, sp, ap, no = wh.morph(a, b, nf_a, nf_b, fs, fft_size, path, path_len, rate=rate, time_rate=time_rate, f0_rate=f0_rate,
+                              sp_rate=sp_rate, ap_rate=ap_rate)
+    y_len = wh.resynthesis_length(fs, n_out, frame_period)
+    return wh.synthesis(f0, sp, ap, no, fft_size, frame_period, fs, np.array([y_len], dtype=np.int32)), y_len
+
+
+def _morph(a):
+    for name in ("rate", "time_rate", "f0_rate", "sp_rate", "ap_rate"):
+        v = getattr(a, name)
+        if v is not None and not 0.0 <= v <= 1.0:
+            sys.exit(f"morph: --{name.replace('_', '-')} {v} outside [0, 1]")
+    if a.fade and (a.f0_rate is not None or a.sp_rate is not None or a.ap_rate is not None):
+        sys.exit("morph: --fade sets the F0, envelope and aperiodicity rates itself")
+    wh = WorldHip()
+    try:
+        (fs_a, fs_b) = (wh.wav_layout(path)[0] for path in (a.a, a.b))
+    except Exception as e:
+        sys.exit(f"morph: not a readable WAV file ({e})")
+    if fs_a != fs_b:
+        sys.exit(f"morph: {a.b} has another sampling rate ({fs_b} Hz) than {a.a} ({fs_a} Hz)")
+    xa, xb = wh.wavread(a.a)[0], wh.wavread(a.b)[0]
+    try:
+        y, y_len = morph_waves(wh, xa, xb, fs_a, a.rate, a.time_rate, a.f0_rate, a.sp_rate, a.ap_rate, a.fade, a.s, a.f, a.c)
+    except ValueError as e:
+        sys.exit(f"morph: {e}")
+    wh.wavwrite(a.o, y[0, :y_len], fs_a)
+    print(f"{a.a} {a.b} -> {a.o} ({y_len} samples at {fs_a} Hz)")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m world_amd.tools", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="tool", required=True)
@@ -342,6 +393,20 @@ def main(argv=None):
     mc.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
     mc.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
     mc.set_defaults(run=_mcd)
+    mo = sub.add_parser("morph", help="two WAV files -> the utterance between them")
+    mo.add_argument("a", metavar="A.wav")
+    mo.add_argument("b", metavar="B.wav")
+    mo.add_argument("-o", default="morph.wav")
+    mo.add_argument("--rate", type=float, default=0.5, help="0 = A, 1 = B: the rate of everything not given a rate of its own")
+    mo.add_argument("--time-rate", type=float, default=None, help="timing: part-way along the alignment of A and B")
+    mo.add_argument("--f0-rate", type=float, default=None, help="F0 (geometric)")
+    mo.add_argument("--sp-rate", type=float, default=None, help="spectral envelope (geometric)")
+    mo.add_argument("--ap-rate", type=float, default=None, help="aperiodicity (linear)")
+    mo.add_argument("--fade", action="store_true", help="F0, envelope and aperiodicity go from A to B over the output")
+    mo.add_argument("-f", type=float, default=71.0, help="floor of the F0 range (Hz)")
+    mo.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
+    mo.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
+    mo.set_defaults(run=_morph)
     a = p.parse_args(argv)
     a.run(a)
 
