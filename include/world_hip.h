@@ -317,7 +317,7 @@ WORLD_HIP_API const char *world_hip_last_error(void);
 WORLD_HIP_API int world_hip_set_hint(WorldHipContext *ctx, int hint);
 WORLD_HIP_API int world_hip_abi_version(void);
 WORLD_HIP_API int world_hip_sync(WorldHipContext *ctx);
-/* bytes of device workspace currently held by the context (its arena) */
+/* bytes of device workspace currently held by the context (its arena, and the resampler's coefficient tables) */
 WORLD_HIP_API unsigned long long world_hip_workspace_bytes(WorldHipContext *ctx);
 /* The reference's randn() stream (src/matlabfunctions.cpp:237-264) is a constant of the algorithm: one
  * table per device, shared by every context of the process, checked in full against a sequential host
@@ -557,6 +557,50 @@ WORLD_HIP_API int world_hip_wav_layout(const char *filename, int *fs, int *nbit,
 /* Host-side writer for samples already quantised (e.g. by world_hip_double_to_pcm16 and one D2H of
  * int16): wavwrite()'s 44-byte header + the samples.  Returns 1 on success, 0 if the file cannot be written. */
 WORLD_HIP_API int world_hip_wav_write_pcm16(const char *filename, int fs, long long n, const short *pcm);
+
+/* Sampling-rate conversion on the device: [n_utt][x_stride] doubles at fs_in -> [n_utt][y_stride] doubles
+ * at fs_out, by a polyphase Kaiser-windowed sinc.  The reference has no resampler (its decimate() is Harvest's integer-ratio
+ * IIR, its interp1() is linear); THIS COMMENT IS THE RULE, and the kernel is held to it bit for bit.
+ * g = gcd(fs_in, fs_out), L = fs_out / g, M = fs_in / g, B = max(L, M); all index arithmetic in 64-bit integers.
+ *   length.  world_hip_resample_length(n_in, fs_in, fs_out) = ceil(n_in * L / M); -1 for a count or a rate below 1 or a
+ *            result above INT_MAX.  Utterance u gets n_out[u] = that of x_length[u]; y_stride must hold it.
+ *   grid.    Output sample m lies at the input time m * M / L: k0 = (m * M) div L, p = (m * M) mod L.
+ *   option.  zeros = zero crossings of the sinc on each side (in units of the lower rate's samples), rolloff = the cut-off as
+ *            a fraction of the lower Nyquist rate, kaiser_beta = the window's shape.  world_hip_resample_option fills a preset
+ *            (any other quality value: BEST); a NULL option in any call means BEST.
+ *              WORLD_HIP_RESAMPLE_BEST  {64, 0.9475937167399596, 14.769656459379492}
+ *              WORLD_HIP_RESAMPLE_FAST  {16, 0.85, 8.555504641634386}
+ *   taps.    W = ceil(zeros * B / L) taps on each side, 2 W in all.  Tap i = 0 .. 2 W - 1 reads input sample
+ *            k = k0 - W + 1 + i with the coefficient c[p][i] = h(q), q = p + (W - 1 - i) * L: the distance between the output
+ *            time and sample k in units of 1 / L sample, an integer.  h(q) is exactly 0.0 where |q| >= zeros * B; otherwise
+ *              h(q) = s * sinc(rolloff * q / B) * I0(kaiser_beta * sqrt(1 - u * u)) / I0(kaiser_beta),
+ *              u = q / (zeros * B),  s = rolloff * min(L, M) / M,  sinc(x) = sin(pi x) / (pi x),  sinc(0) = 1.
+ *            The phases are not renormalised.  The table is made on the host (evaluated in long double, every entry rounded
+ *            once to double); world_hip_resample_taps returns it as [L][2 W] (row p), the very doubles the device uses.
+ *   sum.     y[m] = x[k] * c[p][i] summed over i = 0 .. 2 W - 1 in ascending i, starting from +0.0, the multiplication and
+ *            the addition each rounded on its own (no fused multiply-add).  A sample outside [0, x_length[u]) counts as +0.0.
+ *            So the result depends on nothing but the row: not on the batch, the launch shape or a graph replay; a NaN or
+ *            an Inf sample spreads to the outputs whose 2 W taps reach it (times-zero coefficients included) and no further.
+ *   equal rates.  fs_in == fs_out copies every row's x_length[u] samples bit for bit; no filter is involved.
+ * Samples at or beyond n_out[u] are never written.  Refused, before any GPU work and with nothing written: n_utt < 1, a NULL
+ * pointer, a length below 1 or above x_stride, y_stride below an n_out[u], a rate below 1, zeros outside [1, 256], rolloff
+ * outside (0, 1], kaiser_beta not finite or outside [0, 40], 2 W > 4096, L * 2 W > 2^21 coefficients (rates without a large
+ * common divisor, such as 44100 -> 48001: the message names L), an output range that overlaps the input range.
+ * world_hip_resample_option / _length / _shape / _taps are host arithmetic and need no GPU; _shape and _taps return 0, or 1
+ * with the reason in world_hip_last_error.  world_hip_resample_batch: stream order and errors as the other batched calls;
+ * x_length goes through the context's small-array store and the coefficient table stays with the context's device tables
+ * (a few (fs_in, fs_out, option) keys are kept; world_hip_workspace_bytes counts them), so after one eager call of a shape
+ * the call neither allocates nor copies from the host nor waits, and can be captured. */
+#define WORLD_HIP_RESAMPLE_BEST 0
+#define WORLD_HIP_RESAMPLE_FAST 1
+typedef struct { int zeros; double rolloff; double kaiser_beta; } WorldHipResampleOption;
+WORLD_HIP_API void world_hip_resample_option(int quality, WorldHipResampleOption *opt);
+WORLD_HIP_API int world_hip_resample_length(int n_in, int fs_in, int fs_out);
+WORLD_HIP_API int world_hip_resample_shape(int fs_in, int fs_out, const WorldHipResampleOption *opt, int *L, int *M, int *W);
+WORLD_HIP_API int world_hip_resample_taps(int fs_in, int fs_out, const WorldHipResampleOption *opt, double *table /* host, [L][2W] */);
+WORLD_HIP_API int world_hip_resample_batch(WorldHipContext *ctx, int n_utt, int fs_in, int fs_out,
+                                           const WorldHipResampleOption *opt, const double *d_x, int x_stride,
+                                           const int *x_length /* host */, double *d_y, int y_stride);
 
 /* Coders on dense device rows (reference src/codec.cpp:217-324).  Rows are independent:
  *   spectrogram / aperiodicity  [rows][fft_size/2+1]

@@ -77,6 +77,13 @@ class WorldHipMorphCurves(C.Structure):    # include/world_hip.h: device arrays 
     _fields_ = [(name, C.c_void_p) for name in ("d_f0_rate", "d_sp_rate", "d_ap_rate")]
 
 
+class WorldHipResampleOption(C.Structure):  # include/world_hip.h: the resampler's filter design
+    _fields_ = [("zeros", C.c_int), ("rolloff", C.c_double), ("kaiser_beta", C.c_double)]
+
+
+RESAMPLE_QUALITIES = {"best": 0, "fast": 1}    # WORLD_HIP_RESAMPLE_BEST / _FAST
+
+
 def morphs(n_pairs, time_rate=0.5, f0_rate=0.5, sp_rate=0.5, ap_rate=0.5):
     """WorldHipMorph[n_pairs] from scalars or per-pair sequences"""
     cols = [np.broadcast_to(np.asarray(v, dtype=np.float64), (n_pairs,)) for v in (time_rate, f0_rate, sp_rate, ap_rate)]
@@ -380,6 +387,14 @@ def load_library(path=LIB_PATH):
         lib.world_hip_morph_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp, vp, vp, _ip, C.c_int, vp, vp, vp,
                                               C.c_int, vp, vp, C.POINTER(WorldHipMorph), C.POINTER(WorldHipMorphCurves),
                                               C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(lib, "world_hip_resample_batch"):                     # (likewise)
+        op = C.POINTER(WorldHipResampleOption)
+        lib.world_hip_resample_option.argtypes = [C.c_int, op]
+        lib.world_hip_resample_option.restype = None
+        lib.world_hip_resample_length.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.world_hip_resample_shape.argtypes = [C.c_int, C.c_int, op, _ip, _ip, _ip]
+        lib.world_hip_resample_taps.argtypes = [C.c_int, C.c_int, op, vp]
+        lib.world_hip_resample_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, op, vp, C.c_int, _ip, vp, C.c_int]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -388,6 +403,39 @@ def load_library(path=LIB_PATH):
 def frame_count(fs, x_length, frame_period):
     """GetSamplesForHarvest / GetSamplesForDIO."""
     return int(1000.0 * x_length / fs / frame_period) + 1
+
+
+def resample_length(n_in, fs_in, fs_out):
+    """samples of n_in samples at fs_in after conversion to fs_out: ceil(n_in * L / M) with L / M = fs_out / fs_in in lowest
+    terms (include/world_hip.h: world_hip_resample_length; host arithmetic)"""
+    import math
+    n_in, fs_in, fs_out = int(n_in), int(fs_in), int(fs_out)
+    if n_in < 1 or fs_in < 1 or fs_out < 1:
+        raise ValueError(f"resample_length: {n_in} samples, {fs_in} -> {fs_out} Hz")
+    g = math.gcd(fs_in, fs_out)
+    n = -((-n_in * (fs_out // g)) // (fs_in // g))
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"resample_length: {n_in} samples at {fs_in} Hz are more than INT_MAX at {fs_out} Hz")
+    return n
+
+
+def resample_option(quality="best"):
+    """"best", "fast" or a (zeros, rolloff, kaiser_beta) triple -> WorldHipResampleOption (the presets' values are the
+    header's, written once here as well so that no library is needed to name them)"""
+    if isinstance(quality, WorldHipResampleOption):
+        return quality
+    if isinstance(quality, str):
+        if quality not in RESAMPLE_QUALITIES:
+            raise ValueError(f"resample: quality {quality!r} is neither 'best' nor 'fast' nor a (zeros, rolloff, beta) triple")
+        return WorldHipResampleOption(*{"best": (64, 0.9475937167399596, 14.769656459379492),
+                                        "fast": (16, 0.85, 8.555504641634386)}[quality])
+    try:
+        zeros, rolloff, beta = quality
+        if int(zeros) != zeros:
+            raise ValueError
+        return WorldHipResampleOption(int(zeros), float(rolloff), float(beta))
+    except (TypeError, ValueError):
+        raise ValueError(f"resample: quality {quality!r} is neither 'best' nor 'fast' nor a (zeros, rolloff, beta) triple") from None
 
 
 def cheaptrick_fft_size(fs, f0_floor=71.0):
@@ -1428,6 +1476,27 @@ class WorldHip:
     def set_synthesis_pulse_capacity(self, pulses_per_utterance):
         self._check(self.lib.world_hip_set_synthesis_pulse_capacity(self._context(), int(pulses_per_utterance)),
                     "set_synthesis_pulse_capacity")
+
+    # ---- sampling-rate conversion (include/world_hip.h: world_hip_resample_batch) ----
+    def resample(self, x, fs_in, fs_out, x_len=None, quality="best", out=None):
+        """x [B, L] float64 on the device at fs_in -> (y [B, max(y_len)], y_len) at fs_out, y_len[u] =
+        resample_length(x_len[u], fs_in, fs_out); zero beyond y_len.  quality: "best", "fast" or a (zeros, rolloff,
+        kaiser_beta) triple.  Equal rates copy.  out: a [B, >= max(y_len)] tensor of the caller's to write into (samples
+        beyond y_len are left as they are)."""
+        t = self.torch
+        if not hasattr(self.lib, "world_hip_resample_batch"):
+            raise RuntimeError("this libworld_hip.so has no resampler (world_hip_resample_batch)")
+        opt = resample_option(quality)
+        B, L, xl = self._prep(x, x_len)
+        if int(fs_in) < 1 or int(fs_out) < 1 or (B and int(xl.min()) < 1):
+            raise ValueError(f"resample: {fs_in} -> {fs_out} Hz, lengths {xl.tolist()}")
+        y_len = np.array([resample_length(n, fs_in, fs_out) for n in xl], dtype=np.int32)
+        if out is None:
+            out = t.zeros((B, int(y_len.max())), dtype=t.float64, device=x.device)
+        assert out.dtype == t.float64 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == B and out.device == x.device
+        self._check(self.lib.world_hip_resample_batch(self._context(), B, int(fs_in), int(fs_out), C.byref(opt), x.data_ptr(), L,
+                                                      xl.ctypes.data_as(_ip), out.data_ptr(), out.shape[1]), "resample")
+        return out, y_len
 
     def pcm16_to_double(self, pcm):
         """int16 samples (any shape) -> float64 / 32768, wavread()'s convention, on the device"""

@@ -29,6 +29,7 @@
 #include "exchange.h"
 #include "fft_probe.h"
 #include "machine_probe.h"
+#include "resample.h"
 #include "harvest.h"
 #include "stage_params.h"
 #include "synthesis.h"
@@ -102,6 +103,14 @@ struct CodecTables {             // the coders' tables of one (fs, fft_size) (re
   double *d_wc_re = nullptr, *d_wc_im = nullptr, *d_wd_re = nullptr, *d_wd_im = nullptr;
 };
 
+struct ResampleTable {           // the resampler's device tables of one (L, M, design); a few are kept, least recently used out
+  long long L = 0, M = 0, W = 0;
+  ResampleDesign design{0, 0.0, 0.0};
+  double *d_coef = nullptr;      // [2 W][L], column r = m mod L (resample.h)
+  int *d_kdiv = nullptr;         // [L]
+  unsigned long long used = 0;   // the call that last used it
+};
+
 }  // namespace world_hip
 
 // The small per-call host arrays (lengths, frame counts, row offsets: a few ints per utterance) depend only on the
@@ -153,6 +162,8 @@ struct WorldHipContext {
   int *d_synth_need = nullptr;   // largest pulse count a synthesis call could not hold (0 = nothing was dropped)
   int synth_pulse_cap = 0;       // caller's capacity per utterance (0 = automatic)
   std::vector<world_hip::CodecTables> codec_tables;
+  std::vector<world_hip::ResampleTable> resample_tables;
+  unsigned long long resample_calls = 0;
   // the device arrays of tab and of the cached tables (bands, d_nuttall .. codec_tables, d_pk): allocated and freed by
   // put_table / drop_table only, released together when the context goes
   std::vector<void *> tables;
@@ -1950,6 +1961,97 @@ static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, con
   if (with_f0) launch_morph_frames_f0(p, max_out, c->stream);
 }
 
+// Sampling-rate conversion (include/world_hip.h: world_hip_resample_batch; resample.inc).  The host arithmetic -- lengths,
+// shape, refusals, coefficients -- is tables.cpp's; here the table is put on the device once per (L, M, design) and found again.
+static ResampleDesign resample_design(const WorldHipResampleOption *opt) {
+  WorldHipResampleOption best;
+  if (!opt) { world_hip_resample_option(WORLD_HIP_RESAMPLE_BEST, &best); opt = &best; }   // (the presets are named there alone)
+  return ResampleDesign{opt->zeros, opt->rolloff, opt->kaiser_beta};
+}
+constexpr size_t kResampleTablesKept = 4;        // a mixed-rate tool run alternates between a few ratios
+static const ResampleTable &resample_table(WorldHipContext *c, const ResampleShape &sh, const ResampleDesign &d) {
+  ++c->resample_calls;
+  for (ResampleTable &t : c->resample_tables)
+    if (t.L == sh.L && t.M == sh.M && t.W == sh.W && t.design.zeros == d.zeros && t.design.rolloff == d.rolloff &&
+        t.design.beta == d.beta) {
+      t.used = c->resample_calls;
+      return t;
+    }
+  // a miss allocates and uploads: neither is possible while the stream is being captured into a graph
+  if (devrt::is_capturing(c->stream)) fail("resample: a ratio that was never run before cannot be captured: run it once first");
+  const size_t taps = 2 * (size_t)sh.W, L = (size_t)sh.L;
+  std::vector<double> host(L * taps), dev(L * taps);
+  std::vector<int> kdiv(L);
+  build_resample_taps(sh, d, host.data());
+  for (size_t r = 0; r < L; ++r) {
+    const size_t p = (size_t)(((long long)r * sh.M) % sh.L);
+    kdiv[r] = (int)(((long long)r * sh.M) / sh.L);
+    for (size_t i = 0; i < taps; ++i) dev[i * L + r] = host[p * taps + i];
+  }
+  devrt::sync(c->stream);                        // (a kernel may still read the table that goes)
+  if (c->resample_tables.size() >= kResampleTablesKept) {
+    auto oldest = std::min_element(c->resample_tables.begin(), c->resample_tables.end(),
+                                   [](const ResampleTable &a, const ResampleTable &b) { return a.used < b.used; });
+    drop_table(c, oldest->d_coef);
+    drop_table(c, oldest->d_kdiv);
+    c->resample_tables.erase(oldest);
+  }
+  ResampleTable t;
+  t.L = sh.L; t.M = sh.M; t.W = sh.W; t.design = d; t.used = c->resample_calls;
+  put_table(c, t.d_coef, dev);
+  put_table(c, t.d_kdiv, kdiv);
+  devrt::sync(c->stream);                        // (the host copies go out of scope)
+  c->resample_tables.push_back(t);
+  return c->resample_tables.back();
+}
+
+static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, const WorldHipResampleOption *opt,
+                         const double *d_x, int x_stride, const int *x_length, double *d_y, int y_stride) {
+  if (n_utt < 1) fail("resample: n_utt must be positive");
+  if (!d_x || !d_y || !x_length) fail("resample: null d_x / d_y / x_length");
+  const ResampleDesign design = resample_design(opt);
+  ResampleShape sh;
+  if (const char *why = resample_shape(fs_in, fs_out, design, &sh)) fail("resample: %s", why);
+  std::vector<int> n_out(n_utt);
+  int max_out = 0, max_in = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (x_length[u] < 1 || x_length[u] > x_stride)
+      fail("resample: x_length[%d]=%d outside [1, x_stride=%d]", u, x_length[u], x_stride);
+    n_out[u] = resample_length(x_length[u], fs_in, fs_out);
+    if (n_out[u] < 1) fail("resample: utterance %d: %d samples at %d Hz are more than INT_MAX at %d Hz", u, x_length[u], fs_in, fs_out);
+    if (n_out[u] > y_stride) fail("resample: y_stride %d below utterance %d's %d output samples", y_stride, u, n_out[u]);
+    max_out = std::max(max_out, n_out[u]);
+    max_in = std::max(max_in, x_length[u]);
+  }
+  {
+    const char *x_lo = reinterpret_cast<const char *>(d_x), *x_hi = x_lo + sizeof(double) * (size_t)n_utt * x_stride;
+    const char *y_lo = reinterpret_cast<const char *>(d_y), *y_hi = y_lo + sizeof(double) * (size_t)n_utt * y_stride;
+    if (y_lo < x_hi && x_lo < y_hi) fail("resample: d_y overlaps d_x; the output may not alias the input");
+  }
+  open_uploads(c);                                          // (no workspace: prepared offsets stay valid)
+  ResampleParams p;
+  p.L = (int)sh.L; p.M = (int)sh.M; p.W = (int)sh.W;
+  p.tile = p.span = 0;
+  p.x_stride = x_stride; p.y_stride = y_stride;
+  p.coef = nullptr; p.kdiv = nullptr;
+  const bool copy = fs_in == fs_out;
+  ResamplePlan plan{};
+  if (!copy) {
+    const ResampleTable &t = resample_table(c, sh, design);
+    p.coef = t.d_coef; p.kdiv = t.d_kdiv;
+    plan = resample_plan(sh.L, sh.M, sh.W);
+    p.tile = plan.tile; p.span = plan.span;
+  }
+  const int *d_len = upload(c, std::vector<int>(x_length, x_length + n_utt)), *d_out = upload(c, n_out);
+  for (int u0 = 0; u0 < n_utt; u0 += 65535) {               // (a grid's y extent)
+    const int n = std::min(65535, n_utt - u0);
+    p.x = d_x + (size_t)u0 * x_stride; p.y = d_y + (size_t)u0 * y_stride;
+    p.x_len = d_len + u0; p.n_out = d_out + u0;
+    if (copy) launch_resample_copy(p, max_in, n, c->stream);
+    else launch_resample(p, plan, max_out, n, c->stream);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2081,7 +2183,10 @@ int world_hip_synthesis_pulses_dropped(WorldHipContext *c, int *needed) {
 }
 
 unsigned long long world_hip_workspace_bytes(WorldHipContext *c) {
-  return c ? c->arena.cap : 0;
+  if (!c) return 0;
+  unsigned long long bytes = c->arena.cap;
+  for (const ResampleTable &t : c->resample_tables) bytes += (2ull * t.W * sizeof(double) + sizeof(int)) * t.L;
+  return bytes;
 }
 
 // the device's shared randn table (live + superseded generations), see rng.h
@@ -2630,6 +2735,38 @@ int world_hip_morph_batch(WorldHipContext *c, int n_pairs, int fs, int fft_size,
     run_morph(c, n_pairs, fs, fft_size, n_a, a_stride, d_f0_a, d_sp_a, d_ap_a, n_b, b_stride, d_f0_b, d_sp_b, d_ap_b, p_stride,
               d_path, d_path_len, morphs, curves, o_stride, d_f0_out, d_sp_out, d_ap_out, d_pos_a, d_pos_b);
   });
+}
+void world_hip_resample_option(int quality, WorldHipResampleOption *opt) {
+  if (!opt) return;
+  if (quality == WORLD_HIP_RESAMPLE_FAST) *opt = WorldHipResampleOption{16, 0.85, 8.555504641634386};
+  else *opt = WorldHipResampleOption{64, 0.9475937167399596, 14.769656459379492};
+}
+int world_hip_resample_length(int n_in, int fs_in, int fs_out) { return resample_length(n_in, fs_in, fs_out); }
+int world_hip_resample_shape(int fs_in, int fs_out, const WorldHipResampleOption *opt, int *L, int *M, int *W) {
+  ResampleShape sh;
+  if (const char *why = resample_shape(fs_in, fs_out, resample_design(opt), &sh)) {
+    g_last_error = std::string("resample: ") + why;
+    return 1;
+  }
+  if (L) *L = (int)sh.L;
+  if (M) *M = (int)sh.M;
+  if (W) *W = (int)sh.W;
+  return 0;
+}
+int world_hip_resample_taps(int fs_in, int fs_out, const WorldHipResampleOption *opt, double *table) {
+  ResampleShape sh;
+  const ResampleDesign design = resample_design(opt);
+  if (const char *why = resample_shape(fs_in, fs_out, design, &sh)) {
+    g_last_error = std::string("resample: ") + why;
+    return 1;
+  }
+  if (!table) { g_last_error = "resample: null table"; return 1; }
+  build_resample_taps(sh, design, table);
+  return 0;
+}
+int world_hip_resample_batch(WorldHipContext *c, int n_utt, int fs_in, int fs_out, const WorldHipResampleOption *opt,
+                             const double *d_x, int x_stride, const int *x_length, double *d_y, int y_stride) {
+  return guarded(c, [&] { run_resample(c, n_utt, fs_in, fs_out, opt, d_x, x_stride, x_length, d_y, y_stride); });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||

@@ -2,8 +2,12 @@
 // samples of a WAV file <-> the doubles wavread()/wavwrite() exchange with the analysis
 // (tools/audioio.cpp:123-127 and :230-249).  Uploading the file's bytes and widening on
 // the GPU moves 8/qb x fewer bytes over PCIe than uploading FP64; every operation here is
-// exact in FP64, so the results are bit-identical to the reference's.
+// exact in FP64, so the results are bit-identical to the reference's.  The sampling-rate conversion in front of the analysis
+// (8f.4: files of any rate used together) is resample.inc, included at the end.
+#include <algorithm>
+
 #include "common.h"
+#include "resample.h"
 
 namespace world_hip {
 
@@ -51,5 +55,7 @@ void launch_pcm_bytes_to_double(const unsigned char *d_pcm, double *d_x, long n,
 void launch_double_to_pcm16(const double *d_x, short *d_pcm, long n, hipStream_t stream) {
   WH_THREADS(double_to_pcm16, n, 1, 1, stream, d_x, d_pcm, n);
 }
+
+#include "resample.inc"
 
 }  // namespace world_hip

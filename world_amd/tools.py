@@ -11,6 +11,8 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools transform a.wav --outdir out --align-to b.wav       # a's voice with b's timing
     python -m world_amd.tools mcd ref1.wav test1.wav ref2.wav test2.wav --dims 25 # mel-cepstral distortion along the DTW path
     python -m world_amd.tools morph a.wav b.wav -o out.wav --rate 0.3             # 70 % a, 30 % b; --fade: a cross-fades into b
+    python -m world_amd.tools resample a.wav b.wav ... --outdir out --fs 16000    # every file at 16 kHz (--quality fast|best)
+    python -m world_amd.tools morph a44k.wav b48k.wav -o out.wav --fs 48000       # --fs on analysis, transform, mcd, morph
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -24,6 +26,12 @@ With --align-to the time map is the alignment of each input to another recording
 mel-cepstra of both, c0 left out), one output frame per frame of that recording.  `mcd` analyses pairs of files into coded
 records, aligns each pair on the device and prints the mel-cepstral distortion along the path.  `morph` analyses two files, aligns them the same way and writes the frames
 between them (world_hip_morph_batch): timing, F0, envelope and aperiodicity each part-way from the first file to the second.
+`resample` converts files to one sampling rate (world_hip_resample_batch, a polyphase Kaiser-windowed sinc): PCM bytes go
+up, decode, conversion and the 16-bit quantiser run on the device, int16 comes down.  `analysis`, `transform`, `mcd` and
+`morph` take --fs F (and --quality): every input whose rate differs from F is converted on the device between the PCM decode
+and the analysis -- nothing is quantised in between -- so files of any rates can be used together (and an 8 kHz recording,
+below D4C's range, analysed at 16 kHz).  Files are still batched per SOURCE rate, one conversion per batch; outputs carry F.
+Without --fs every tool behaves as before, refusals of mixed rates included.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -35,17 +43,38 @@ import numpy as np
 from .api import FileAPI, WorldHip, cheaptrick_fft_size, frame_count, uniform_time_map
 
 
+def _at_rate(wh, x, x_len, fs, target, quality="best"):
+    """--fs: a decoded batch of rate fs -> (x, x_len, rate) at the target rate (None or the batch's own: as it is)"""
+    if target is None or target == fs:
+        return x, x_len, fs
+    try:
+        y, y_len = wh.resample(x, fs, target, x_len=x_len, quality=quality)
+    except RuntimeError as e:                                   # the library's refusal (44100 -> 48001 Hz: too many phases)
+        raise ValueError(str(e)) from None
+    return y, y_len, target
+
+
+def _check_rate(tool, a):
+    if a.fs is not None and a.fs < 1:
+        sys.exit(f"{tool}: --fs {a.fs} is not a sampling rate")
+
+
 def _analysis(a):
+    _check_rate("analysis", a)
     wh, files = WorldHip(), FileAPI()
     os.makedirs(a.outdir, exist_ok=True)
     by_rate = {}
     for path in a.wav:
         by_rate.setdefault(wh.wav_layout(path)[0], []).append(path)
     frames = 0
-    for fs, group in sorted(by_rate.items()):
+    for src_fs, group in sorted(by_rate.items()):
         for at in range(0, len(group), a.batch):
             chunk = group[at:at + a.batch]
             x, x_len = _load_batch(wh, chunk)
+            try:
+                x, x_len, fs = _at_rate(wh, x, x_len, src_fs, a.fs, a.quality)
+            except ValueError as e:
+                sys.exit(f"analysis: {e}")
             tpos, f0, sp, ap, nf = wh.analyze(x, fs, x_len=x_len, f0_method=a.f0, frame_period=a.s, f0_floor=a.f,
                                               f0_ceil=a.c, q1=a.q, threshold=a.t)
             fft_size = cheaptrick_fft_size(fs, 71.0)
@@ -134,6 +163,7 @@ def transform_outputs(wavs, outdir):
 
 
 def _transform(a):
+    _check_rate("transform", a)
     try:
         outs = transform_outputs(a.wav, a.outdir)
     except ValueError as e:
@@ -164,10 +194,14 @@ def _transform(a):
     for path in a.wav:
         by_rate.setdefault(wh.wav_layout(path)[0], []).append(path)
     samples = 0
-    for fs, group in sorted(by_rate.items()):
+    for src_fs, group in sorted(by_rate.items()):
         for at in range(0, len(group), a.batch):
             chunk = group[at:at + a.batch]
             x, x_len = _load_batch(wh, chunk)
+            try:
+                x, x_len, fs = _at_rate(wh, x, x_len, src_fs, a.fs, a.quality)
+            except ValueError as e:
+                sys.exit(f"transform: {e}")
             if frames:
                 y, y_len = _resynthesize_frames(wh, a, x, fs, x_len, track)
             else:
@@ -235,10 +269,14 @@ def _cepstra(block, dims, keep_c0):
 def _align_to(wh, a, x, fs, x_len):
     """--align-to: the time map [B, n_other] that gives every input the timing of the other recording -- the mid-points
     of the DTW path between the input's and the other's mel-cepstra, per frame of the other"""
-    if a.other["fs"] != fs:
+    if a.other["fs"] != fs and a.fs is None:
         sys.exit(f"transform: {a.align_to} has another sampling rate ({a.other['fs']} Hz) than the {fs} Hz inputs")
-    if "block" not in a.other:                                  # (one rate only gets here: once for all batches)
-        other, other_len = _load_batch(wh, [a.align_to])
+    if "block" not in a.other:                                  # (once for all batches: they all arrive at one rate -- their
+        other, other_len = _load_batch(wh, [a.align_to])        #  own, the other's, or with --fs any source rates at F)
+        try:
+            other, other_len, _ = _at_rate(wh, other, other_len, a.other["fs"], a.fs, a.quality)
+        except ValueError as e:
+            sys.exit(f"transform: --align-to {a.align_to}: {e}")
         a.other["block"], a.other["row"], a.other["nf"] = _coded_block(wh, other, fs, other_len, a.s, ALIGN_DIMS, a.f, a.c)
     blk_b, row_b, nf_b = a.other["block"], a.other["row"], a.other["nf"]
     blk_a, row_a, nf_a = _coded_block(wh, x, fs, x_len, a.s, ALIGN_DIMS, a.f, a.c)
@@ -248,28 +286,36 @@ def _align_to(wh, a, x, fs, x_len):
     return map_b
 
 
-def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch=64):
+def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch=64, fs=None, quality="best"):
     """[(ref.wav, test.wav)] -> [(frames of ref, frames of test, path length, MCD in dB)]: every file analysed once into
-    coded records (batches per sampling rate), every pair aligned on the device, one align call per rate"""
-    by_rate, rate_of = {}, {}
+    coded records (batches per sampling rate), every pair aligned on the device, one align call per rate.  fs: every file
+    is converted to that rate on the device first (batches per source rate), and pairs of any two rates can be scored"""
+    target = fs
+    by_source, rate_of = {}, {}
     for path in dict.fromkeys(p for pair in pairs for p in pair):
-        rate_of[path] = wh.wav_layout(path)[0]
-        by_rate.setdefault(rate_of[path], []).append(path)
+        source = wh.wav_layout(path)[0]
+        rate_of[path] = source if target is None else target
+        by_source.setdefault(source, []).append(path)
     for ref, test in pairs:
         if rate_of[ref] != rate_of[test]:
             raise ValueError(f"{ref} and {test} have different sampling rates")
+    by_rate = {}                                                # analysis rate -> [(source rate, its files)]
+    for source, group in sorted(by_source.items()):
+        by_rate.setdefault(source if target is None else target, []).append((source, group))
     out = {}
-    for fs, group in sorted(by_rate.items()):
+    for fs, sources in sorted(by_rate.items()):
         import torch
         blocks, where, at = [], {}, 0
-        for lo in range(0, len(group), batch):
-            chunk = group[lo:lo + batch]
-            x, x_len = _load_batch(wh, chunk)
-            block, first, nf = _coded_block(wh, x, fs, x_len, frame_period, dims)
-            blocks.append(block)
-            for path, r, n in zip(chunk, first, nf):
-                where[path] = (at + int(r), int(n))
-            at += block.shape[0]
+        for source, group in sources:
+            for lo in range(0, len(group), batch):
+                chunk = group[lo:lo + batch]
+                x, x_len = _load_batch(wh, chunk)
+                x, x_len, _ = _at_rate(wh, x, x_len, source, target, quality)
+                block, first, nf = _coded_block(wh, x, fs, x_len, frame_period, dims)
+                blocks.append(block)
+                for path, r, n in zip(chunk, first, nf):
+                    where[path] = (at + int(r), int(n))
+                at += block.shape[0]
         block = torch.cat(blocks) if len(blocks) > 1 else blocks[0]
         mine = [pr for pr in pairs if rate_of[pr[0]] == fs]
         feats = _cepstra(block, dims, keep_c0)
@@ -283,13 +329,14 @@ def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch
 
 
 def _mcd(a):
+    _check_rate("mcd", a)
     if len(a.wav) % 2:
         sys.exit("mcd: the files come in pairs: REF.wav TEST.wav [REF2.wav TEST2.wav ...]")
     if a.dims < (1 if a.keep_c0 else 2):
         sys.exit(f"mcd: --dims {a.dims} leaves no coefficient to compare")
     pairs = list(zip(a.wav[0::2], a.wav[1::2]))
     try:
-        results = mcd_pairs(WorldHip(), pairs, a.dims, a.keep_c0, a.s, a.batch)
+        results = mcd_pairs(WorldHip(), pairs, a.dims, a.keep_c0, a.s, a.batch, a.fs, a.quality)
     except ValueError as e:
         sys.exit(f"mcd: {e}")
     for (ref, test), (na, nb, K, mcd) in zip(pairs, results):
@@ -334,15 +381,54 @@ def _morph(a):
         (fs_a, fs_b) = (wh.wav_layout(path)[0] for path in (a.a, a.b))
     except Exception as e:
         sys.exit(f"morph: not a readable WAV file ({e})")
-    if fs_a != fs_b:
+    if fs_a != fs_b and a.fs is None:
         sys.exit(f"morph: {a.b} has another sampling rate ({fs_b} Hz) than {a.a} ({fs_a} Hz)")
     xa, xb = wh.wavread(a.a)[0], wh.wavread(a.b)[0]
+    fs = fs_a if a.fs is None else a.fs
     try:
-        y, y_len = morph_waves(wh, xa, xb, fs_a, a.rate, a.time_rate, a.f0_rate, a.sp_rate, a.ap_rate, a.fade, a.s, a.f, a.c)
+        (xa, xb) = (_at_rate(wh, x[None].contiguous(), None, src, a.fs, a.quality)[0][0] for x, src in ((xa, fs_a), (xb, fs_b)))
     except ValueError as e:
         sys.exit(f"morph: {e}")
-    wh.wavwrite(a.o, y[0, :y_len], fs_a)
-    print(f"{a.a} {a.b} -> {a.o} ({y_len} samples at {fs_a} Hz)")
+    try:
+        y, y_len = morph_waves(wh, xa, xb, fs, a.rate, a.time_rate, a.f0_rate, a.sp_rate, a.ap_rate, a.fade, a.s, a.f, a.c)
+    except ValueError as e:
+        sys.exit(f"morph: {e}")
+    wh.wavwrite(a.o, y[0, :y_len], fs)
+    print(f"{a.a} {a.b} -> {a.o} ({y_len} samples at {fs} Hz)")
+
+
+def _resample(a):
+    _check_rate("resample", a)
+    try:
+        outs = transform_outputs(a.wav, a.outdir)
+    except ValueError as e:
+        sys.exit(f"resample: {e}")
+    wh = WorldHip()
+    by_rate = {}
+    try:
+        for path in a.wav:
+            by_rate.setdefault(wh.wav_layout(path)[0], []).append(path)
+    except OSError as e:
+        sys.exit(f"resample: not a readable WAV file ({e})")
+    os.makedirs(a.outdir, exist_ok=True)
+    out_of = dict(zip(a.wav, outs))
+    samples = 0
+    for src_fs, group in sorted(by_rate.items()):
+        for at in range(0, len(group), a.batch):
+            chunk = group[at:at + a.batch]
+            x, x_len = _load_batch(wh, chunk)
+            try:
+                y, y_len, _ = _at_rate(wh, x, x_len, src_fs, a.fs, a.quality)
+            except ValueError as e:
+                sys.exit(f"resample: {e}")
+            q = wh.double_to_pcm16(y).cpu().numpy()              # quantised on the device: int16 crosses PCIe
+            for row, path in enumerate(chunk):
+                n, name = int(y_len[row]), out_of[path]
+                pcm = np.ascontiguousarray(q[row, :n])
+                if wh.lib.world_hip_wav_write_pcm16(os.fsencode(name), a.fs, n, pcm.ctypes.data) != 1:
+                    sys.exit(f"resample: {name} cannot be written")
+                samples += n
+    print(f"{len(a.wav)} file(s), {samples} samples at {a.fs} Hz -> {a.outdir}")
 
 
 def main(argv=None):
@@ -407,6 +493,17 @@ def main(argv=None):
     mo.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
     mo.add_argument("-s", type=float, default=5.0, help="frame shift of the analysis (ms)")
     mo.set_defaults(run=_morph)
+    rs = sub.add_parser("resample", help="WAV files -> WAV files of one sampling rate")
+    rs.add_argument("wav", nargs="+")
+    rs.add_argument("--outdir", required=True, help="written under the input files' names; must hold none of the inputs")
+    rs.add_argument("--fs", type=int, required=True, metavar="F", help="the sampling rate of every output (Hz)")
+    rs.add_argument("--quality", choices=("best", "fast"), default="best", help="the filter: 64 or 16 zero crossings a side")
+    rs.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
+    rs.set_defaults(run=_resample)
+    for tool in (an, tr, mc, mo):
+        tool.add_argument("--fs", type=int, default=None, metavar="F",
+                          help="convert every input whose sampling rate differs from F to F on the device first")
+        tool.add_argument("--quality", choices=("best", "fast"), default="best", help="the filter of that conversion")
     a = p.parse_args(argv)
     a.run(a)
 
