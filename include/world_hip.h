@@ -317,7 +317,7 @@ WORLD_HIP_API const char *world_hip_last_error(void);
 WORLD_HIP_API int world_hip_set_hint(WorldHipContext *ctx, int hint);
 WORLD_HIP_API int world_hip_abi_version(void);
 WORLD_HIP_API int world_hip_sync(WorldHipContext *ctx);
-/* bytes of device workspace currently held by the context (its arena, and the resampler's coefficient tables) */
+/* bytes of device workspace currently held by the context (its arena, the resampler's coefficient tables and the mel-cepstrum's tables) */
 WORLD_HIP_API unsigned long long world_hip_workspace_bytes(WorldHipContext *ctx);
 /* The reference's randn() stream (src/matlabfunctions.cpp:237-264) is a constant of the algorithm: one
  * table per device, shared by every context of the process, checked in full against a sequential host
@@ -601,6 +601,46 @@ WORLD_HIP_API int world_hip_resample_taps(int fs_in, int fs_out, const WorldHipR
 WORLD_HIP_API int world_hip_resample_batch(WorldHipContext *ctx, int n_utt, int fs_in, int fs_out,
                                            const WorldHipResampleOption *opt, const double *d_x, int x_stride,
                                            const int *x_length /* host */, double *d_y, int y_stride);
+
+/* Mel-cepstra by all-pass frequency warping on the device: SPTK's freqt with a constant alpha, what users of a WORLD
+ * binding call sp2mc / mc2sp.  (The coders below are the reference's own: a DCT of the log envelope on a mel axis, a
+ * different transform with different numbers.)  The reference has no such function; THIS COMMENT IS THE RULE.
+ * N = fft_size, H = N / 2, K = H + 1 bins, P = order + 1 coefficients; w_0 = w_H = 1/2 and w = 1 otherwise.
+ *   encode (sp2mc).  mc_m = sum over k of M[m][k] ln sp_k, M = A F.
+ *            F[n][k] = (2 / N) w_n w_k cos(pi n k / H): c = F ln sp is the one-sided cepstrum, ln sp_k = 2 sum_n c_n
+ *            cos(pi n k / H) exactly.  A[m][n] is freqt applied to unit vectors:
+ *              A[0][0] = 1, A[m][0] = 0 for m > 0;  A[0][n] = alpha A[0][n-1];
+ *              A[1][n] = (1 - alpha^2) A[0][n-1] + alpha A[1][n-1];
+ *              A[m][n] = A[m-1][n-1] + alpha (A[m][n-1] - A[m-1][n]) for m >= 2.
+ *   decode (mc2sp).  sp_k = exp(sum over m of D[k][m] mc_m), D[k][m] = 2 cos(m w~_k),
+ *            w~_k = w_k + 2 atan2(alpha sin w_k, 1 - alpha cos w_k), w_k = pi k / H: H(z) = exp sum mc_m z~^-m, sp = |H|^2
+ *            (SPTK's convention).  With alpha = 0 encode is plain cepstral truncation.
+ *   tables.  Both are made on the host in long double and rounded once to double; world_hip_mcep_tables returns them,
+ *            M as [P][K] and D as [K][P] (either may be NULL), the very doubles the device multiplies by.  (The rows of M
+ *            are cosine transforms of the rows of A and are made by a long-double FFT: milliseconds at any shape.)
+ *   alpha.   world_hip_mcep_alpha(fs) = i / 1000 for the first i in [0, 999] that minimises the RMS, over w_j = pi j / 1000,
+ *            j = 0 .. 999, of the difference between ln(1 + (fs / 2000) j / 1000) and w_j + 2 atan2(alpha sin w_j,
+ *            1 - alpha cos w_j), each divided by its value at j = 999: 0.41 at 16 kHz, 0.554 at 48 kHz.  NaN for fs < 1.
+ *   sums.    Each output is a sum over ascending k (m) on the FP64 matrix unit; a row's result depends on nothing but the
+ *            row: not on the batch, the row's position, the launch shape or a graph replay.
+ * Strides are counted in doubles: d_block + 2 with world_hip_record_columns(fft_size, 0) reads the envelopes of packed f64
+ * records where they lie, and a stride above P writes the coefficients into records of the caller's.  Doubles of an output
+ * row beyond P (K for mc2sp) and rows beyond `rows` are never written.  Refused, before any GPU work and with nothing written:
+ * rows < 1, a NULL pointer, fft_size not a power of two in [128, 8192], order outside [0, min(H, 255)], alpha not finite or
+ * |alpha| > 0.9, a stride shorter than the row, an output range that overlaps the input range.  A row with a non-finite or
+ * non-positive envelope bin yields an unspecified row (it may be NaN); no other row changes.
+ * world_hip_mcep_alpha / _tables are host arithmetic and need no GPU; _tables returns 0, or 1 with the reason in
+ * world_hip_last_error.  world_hip_sp2mc / _mc2sp: stream order and errors as the other batched calls; a direction's table
+ * stays with the context's device tables (a few (fft_size, order, alpha) keys are kept; world_hip_workspace_bytes counts
+ * them), so after one eager call of a shape the call neither allocates nor copies from the host nor waits, and can be
+ * captured. */
+WORLD_HIP_API double world_hip_mcep_alpha(int fs);
+WORLD_HIP_API int world_hip_mcep_tables(int fft_size, int order, double alpha, double *M /* host, [P][K] */,
+                                        double *D /* host, [K][P] */);
+WORLD_HIP_API int world_hip_sp2mc(WorldHipContext *ctx, int rows, int fft_size, int order, double alpha, const double *d_sp,
+                                  long long sp_row_stride, double *d_mc, long long mc_row_stride);
+WORLD_HIP_API int world_hip_mc2sp(WorldHipContext *ctx, int rows, int fft_size, int order, double alpha, const double *d_mc,
+                                  long long mc_row_stride, double *d_sp, long long sp_row_stride);
 
 /* Coders on dense device rows (reference src/codec.cpp:217-324).  Rows are independent:
  *   spectrogram / aperiodicity  [rows][fft_size/2+1]

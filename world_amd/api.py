@@ -395,6 +395,12 @@ def load_library(path=LIB_PATH):
         lib.world_hip_resample_shape.argtypes = [C.c_int, C.c_int, op, _ip, _ip, _ip]
         lib.world_hip_resample_taps.argtypes = [C.c_int, C.c_int, op, vp]
         lib.world_hip_resample_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, op, vp, C.c_int, _ip, vp, C.c_int]
+    if hasattr(lib, "world_hip_sp2mc"):                              # (likewise)
+        lib.world_hip_mcep_alpha.argtypes = [C.c_int]
+        lib.world_hip_mcep_alpha.restype = C.c_double
+        lib.world_hip_mcep_tables.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp]
+        for fn in (lib.world_hip_sp2mc, lib.world_hip_mc2sp):
+            fn.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_longlong, vp, C.c_longlong]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -1577,6 +1583,68 @@ class WorldHip:
     def decode_aperiodicity(self, coded, fs, fft_size):
         return self._codec(self.lib.world_hip_decode_aperiodicity, "decode_aperiodicity", coded, fs, fft_size,
                            fft_size // 2 + 1)
+
+    # ---- all-pass mel-cepstra (include/world_hip.h: world_hip_sp2mc / world_hip_mc2sp) ----
+    def mcep_alpha(self, fs):
+        """the all-pass constant whose warp lies closest to the mel scale at fs (0.41 at 16 kHz, 0.554 at 48 kHz)"""
+        if not hasattr(self.lib, "world_hip_sp2mc"):
+            raise RuntimeError("this libworld_hip.so has no mel-cepstrum (world_hip_sp2mc)")
+        if int(fs) < 1:
+            raise ValueError(f"mcep_alpha: fs {fs}")
+        return float(self.lib.world_hip_mcep_alpha(int(fs)))
+
+    def _mcep_rows(self, x, cols, row_stride, rows, what):
+        """(rows, stride in doubles, leading shape) of the rows of `cols` doubles in x: a dense [..., cols] tensor, a 2-D
+        view whose rows lie further apart (x.stride(0)), or -- row_stride given -- any tensor that starts at the first
+        row's first double and reaches the last row's last"""
+        t = self.torch
+        assert x.dtype == t.float64 and x.is_cuda and x.device == self.device, f"{what}: float64 on {self.device}"
+        if row_stride is not None:
+            if rows is None:
+                raise ValueError(f"{what}: row_stride needs rows")
+            assert x.is_contiguous() and x.numel() >= (int(rows) - 1) * int(row_stride) + cols, f"{what}: the tensor ends before the last row"
+            return int(rows), int(row_stride), (int(rows),)
+        assert x.shape[-1] == cols and x.stride(-1) == 1, f"{what}: [..., {cols}] with adjacent columns"
+        if x.dim() == 2 and not x.is_contiguous():
+            return int(x.shape[0]), int(x.stride(0)), (int(x.shape[0]),)
+        assert x.is_contiguous(), f"{what}: dense, or a 2-D view with a row stride"
+        return int(x.numel() // cols), cols, tuple(x.shape[:-1])
+
+    def _mcep(self, decode, src, in_cols, out_cols, fft_size, order, alpha, out, row_stride, rows):
+        t = self.torch
+        what = "mc2sp" if decode else "sp2mc"
+        if not hasattr(self.lib, "world_hip_sp2mc"):
+            raise RuntimeError("this libworld_hip.so has no mel-cepstrum (world_hip_sp2mc)")
+        n, in_stride, lead = self._mcep_rows(src, in_cols, row_stride, rows, what)
+        ret = out
+        if out is None:
+            out = ret = t.empty(lead + (out_cols,), dtype=t.float64, device=src.device)
+            out_stride = out_cols
+        else:
+            assert out.dtype == t.float64 and out.device == src.device and out.dim() == 2 and out.shape[0] == n and \
+                out.shape[1] >= out_cols and out.stride(1) == 1, f"{what}: out must be [{n}, >= {out_cols}] float64 with adjacent columns"
+            out_stride = int(out.stride(0)) if n > 1 else max(int(out.stride(0)), out_cols)
+        fn = self.lib.world_hip_mc2sp if decode else self.lib.world_hip_sp2mc
+        self._check(fn(self._context(), n, int(fft_size), int(order), float(alpha), src.data_ptr(), in_stride, out.data_ptr(),
+                       out_stride), what)
+        return ret
+
+    def sp2mc(self, sp, order, alpha, out=None, row_stride=None, rows=None, fft_size=None):
+        """envelope rows -> mel-cepstra c_0 .. c_order by all-pass warping (SPTK's freqt of the cepstrum of ln sp).
+        sp: [..., fft_size / 2 + 1] float64 on the device; a 2-D view with a larger row stride (block[:, 2:2 + K] of packed
+        records) is read where it lies.  row_stride (with rows and fft_size): sp is any tensor starting at the first
+        envelope.  out: a [rows, >= order + 1] tensor or view of the caller's (columns beyond order + 1 are left alone).
+        Returns [..., order + 1], or out."""
+        if fft_size is None:
+            fft_size = 2 * (int(sp.shape[-1]) - 1)
+        return self._mcep(False, sp, int(fft_size) // 2 + 1, int(order) + 1, fft_size, order, alpha, out, row_stride, rows)
+
+    def mc2sp(self, mc, alpha, fft_size, out=None, row_stride=None, rows=None, order=None):
+        """mel-cepstra -> envelope rows [..., fft_size / 2 + 1]: sp = |exp sum mc_m z~^-m|^2.  mc: [..., order + 1], a 2-D
+        view with a larger row stride, or -- row_stride with rows and order -- any tensor starting at the first c_0."""
+        if order is None:
+            order = int(mc.shape[-1]) - 1
+        return self._mcep(True, mc, int(order) + 1, int(fft_size) // 2 + 1, fft_size, order, alpha, out, row_stride, rows)
 
     def probe_machine(self):
         """world_hip_probe_machine (include/world_hip.h): ~50 ms of microbenchmarks that characterise the box"""

@@ -29,6 +29,7 @@
 #include "exchange.h"
 #include "fft_probe.h"
 #include "machine_probe.h"
+#include "mcep_host.h"
 #include "resample.h"
 #include "harvest.h"
 #include "stage_params.h"
@@ -111,6 +112,15 @@ struct ResampleTable {           // the resampler's device tables of one (L, M, 
   unsigned long long used = 0;   // the call that last used it
 };
 
+struct McepTable {               // one direction's device table of one (fft_size, order, alpha); a few are kept, least recently used out
+  int fft_size = 0, order = 0;
+  unsigned long long alpha_bits = 0;
+  bool decode = false;
+  int k_pad = 0, n_pad = 0;
+  double *d_table = nullptr;     // [k_pad][n_pad], zero beyond the table (codec.h: McepParams)
+  unsigned long long used = 0;
+};
+
 }  // namespace world_hip
 
 // The small per-call host arrays (lengths, frame counts, row offsets: a few ints per utterance) depend only on the
@@ -164,6 +174,8 @@ struct WorldHipContext {
   std::vector<world_hip::CodecTables> codec_tables;
   std::vector<world_hip::ResampleTable> resample_tables;
   unsigned long long resample_calls = 0;
+  std::vector<world_hip::McepTable> mcep_tables;
+  unsigned long long mcep_calls = 0;
   // the device arrays of tab and of the cached tables (bands, d_nuttall .. codec_tables, d_pk): allocated and freed by
   // put_table / drop_table only, released together when the context goes
   std::vector<void *> tables;
@@ -2052,6 +2064,72 @@ static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, c
   }
 }
 
+// All-pass mel-cepstra (include/world_hip.h: world_hip_sp2mc / world_hip_mc2sp; mcep.inc).  The host arithmetic -- the
+// refusals of a shape, the tables -- is tables.cpp's; here a direction's table is put on the device once per
+// (fft_size, order, alpha) and found again.
+constexpr size_t kMcepTablesKept = 4;            // both directions of two shapes
+static const McepTable &mcep_table(WorldHipContext *c, bool decode, int fft_size, int order, double alpha) {
+  unsigned long long bits;
+  memcpy(&bits, &alpha, sizeof bits);
+  ++c->mcep_calls;
+  for (McepTable &t : c->mcep_tables)
+    if (t.decode == decode && t.fft_size == fft_size && t.order == order && t.alpha_bits == bits) {
+      t.used = c->mcep_calls;
+      return t;
+    }
+  // a miss allocates and uploads: neither is possible while the stream is being captured into a graph
+  if (devrt::is_capturing(c->stream)) fail("mcep: a (fft_size, order, alpha) that was never run before cannot be captured: run it once first");
+  const size_t K = (size_t)fft_size / 2 + 1, P = (size_t)order + 1;
+  McepTable t;
+  t.fft_size = fft_size; t.order = order; t.alpha_bits = bits; t.decode = decode; t.used = c->mcep_calls;
+  mcep_table_shape(decode, fft_size, order, &t.k_pad, &t.n_pad);
+  std::vector<double> host(K * P), dev((size_t)t.k_pad * t.n_pad, 0.0);
+  if (decode) {                                  // D [K][P] -> [m][k]
+    build_mcep_decode(fft_size, order, alpha, host.data());
+    for (size_t k = 0; k < K; ++k)
+      for (size_t m = 0; m < P; ++m) dev[m * t.n_pad + k] = host[k * P + m];
+  } else {                                       // M [P][K] -> [k][m]
+    build_mcep_encode(fft_size, order, alpha, host.data());
+    for (size_t m = 0; m < P; ++m)
+      for (size_t k = 0; k < K; ++k) dev[k * t.n_pad + m] = host[m * K + k];
+  }
+  devrt::sync(c->stream);                        // (a kernel may still read the table that goes)
+  if (c->mcep_tables.size() >= kMcepTablesKept) {
+    auto oldest = std::min_element(c->mcep_tables.begin(), c->mcep_tables.end(),
+                                   [](const McepTable &a, const McepTable &b) { return a.used < b.used; });
+    drop_table(c, oldest->d_table);
+    c->mcep_tables.erase(oldest);
+  }
+  put_table(c, t.d_table, dev);
+  devrt::sync(c->stream);                        // (the host copy goes out of scope)
+  c->mcep_tables.push_back(t);
+  return c->mcep_tables.back();
+}
+
+static void run_mcep(WorldHipContext *c, bool decode, int rows, int fft_size, int order, double alpha, const double *d_in,
+                     long long in_stride, double *d_out, long long out_stride) {
+  const char *name = decode ? "mc2sp" : "sp2mc";
+  if (rows < 1) fail("%s: rows must be positive", name);
+  if (!d_in || !d_out) fail("%s: null %s", name, decode ? "d_mc / d_sp" : "d_sp / d_mc");
+  if (const char *why = mcep_shape(fft_size, order, alpha)) fail("%s: %s", name, why);
+  const long long K = fft_size / 2 + 1, P = order + 1, in_cols = decode ? P : K, out_cols = decode ? K : P;
+  if (in_stride < in_cols)
+    fail("%s: %s %lld below the row's %lld doubles", name, decode ? "mc_row_stride" : "sp_row_stride", in_stride, in_cols);
+  if (out_stride < out_cols)
+    fail("%s: %s %lld below the row's %lld doubles", name, decode ? "sp_row_stride" : "mc_row_stride", out_stride, out_cols);
+  {
+    const char *i_lo = reinterpret_cast<const char *>(d_in), *i_hi = i_lo + sizeof(double) * (size_t)((rows - 1) * in_stride + in_cols);
+    const char *o_lo = reinterpret_cast<const char *>(d_out), *o_hi = o_lo + sizeof(double) * (size_t)((rows - 1) * out_stride + out_cols);
+    if (o_lo < i_hi && i_lo < o_hi) fail("%s: the output range overlaps the input range; the output may not alias the input", name);
+  }
+  const McepTable &t = mcep_table(c, decode, fft_size, order, alpha);
+  McepParams p;
+  p.in = d_in; p.out = d_out; p.table = t.d_table;
+  p.in_stride = in_stride; p.out_stride = out_stride;
+  p.rows = rows; p.k_in = (int)in_cols; p.k_out = (int)out_cols; p.k_pad = t.k_pad; p.n_pad = t.n_pad;
+  launch_mcep(p, decode, c->stream);
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2186,6 +2264,7 @@ unsigned long long world_hip_workspace_bytes(WorldHipContext *c) {
   if (!c) return 0;
   unsigned long long bytes = c->arena.cap;
   for (const ResampleTable &t : c->resample_tables) bytes += (2ull * t.W * sizeof(double) + sizeof(int)) * t.L;
+  for (const McepTable &t : c->mcep_tables) bytes += sizeof(double) * (unsigned long long)t.k_pad * t.n_pad;
   return bytes;
 }
 
@@ -2767,6 +2846,24 @@ int world_hip_resample_taps(int fs_in, int fs_out, const WorldHipResampleOption 
 int world_hip_resample_batch(WorldHipContext *c, int n_utt, int fs_in, int fs_out, const WorldHipResampleOption *opt,
                              const double *d_x, int x_stride, const int *x_length, double *d_y, int y_stride) {
   return guarded(c, [&] { run_resample(c, n_utt, fs_in, fs_out, opt, d_x, x_stride, x_length, d_y, y_stride); });
+}
+double world_hip_mcep_alpha(int fs) { return mcep_alpha(fs); }
+int world_hip_mcep_tables(int fft_size, int order, double alpha, double *M, double *D) {
+  if (const char *why = mcep_shape(fft_size, order, alpha)) {
+    g_last_error = std::string("mcep: ") + why;
+    return 1;
+  }
+  if (M) build_mcep_encode(fft_size, order, alpha, M);
+  if (D) build_mcep_decode(fft_size, order, alpha, D);
+  return 0;
+}
+int world_hip_sp2mc(WorldHipContext *c, int rows, int fft_size, int order, double alpha, const double *d_sp,
+                    long long sp_row_stride, double *d_mc, long long mc_row_stride) {
+  return guarded(c, [&] { run_mcep(c, false, rows, fft_size, order, alpha, d_sp, sp_row_stride, d_mc, mc_row_stride); });
+}
+int world_hip_mc2sp(WorldHipContext *c, int rows, int fft_size, int order, double alpha, const double *d_mc,
+                    long long mc_row_stride, double *d_sp, long long sp_row_stride) {
+  return guarded(c, [&] { run_mcep(c, true, rows, fft_size, order, alpha, d_mc, mc_row_stride, d_sp, sp_row_stride); });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||

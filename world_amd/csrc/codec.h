@@ -168,4 +168,17 @@ void launch_morph_frames_sp(const MorphParams &p, int max_out, hipStream_t strea
 void launch_morph_frames_ap(const MorphParams &p, int max_out, hipStream_t stream);
 void launch_morph_frames_f0(const MorphParams &p, int max_out, hipStream_t stream);
 
+// All-pass mel-cepstra (world_hip_sp2mc / world_hip_mc2sp; mcep.inc): out [rows][k_out] = f(in [rows][k_in]) x table, with
+// ln applied to the input (encode: k_in bins -> k_out coefficients) or exp to the output (decode).  `table` is the
+// direction's host table transposed to [k_in][k_out] and padded with zeros to [k_pad][n_pad] (mcep_table_shape).
+struct McepParams {
+  const double *in;
+  double *out;
+  const double *table;
+  long long in_stride, out_stride;  // doubles between rows
+  int rows, k_in, k_out, k_pad, n_pad;
+};
+void mcep_table_shape(bool decode, int fft_size, int order, int *k_pad, int *n_pad);
+void launch_mcep(const McepParams &p, bool decode, hipStream_t stream);
+
 }  // namespace world_hip

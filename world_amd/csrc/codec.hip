@@ -24,7 +24,8 @@
 //                    then the warp / gain / target and scale of that frame
 // The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
 // And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end;
-// behind it morph.inc, the frames between two utterances aligned that way (world_hip_morph_batch).
+// behind it morph.inc, the frames between two utterances aligned that way (world_hip_morph_batch); and mcep.inc, the
+// all-pass mel-cepstrum of an envelope and back (world_hip_sp2mc / world_hip_mc2sp) on the FP64 matrix unit.
 #include "codec.h"
 #include "fft.h"
 
@@ -450,5 +451,6 @@ void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) 
 
 #include "align.inc"
 #include "morph.inc"
+#include "mcep.inc"
 
 }  // namespace world_hip

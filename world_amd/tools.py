@@ -13,6 +13,9 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools morph a.wav b.wav -o out.wav --rate 0.3             # 70 % a, 30 % b; --fade: a cross-fades into b
     python -m world_amd.tools resample a.wav b.wav ... --outdir out --fs 16000    # every file at 16 kHz (--quality fast|best)
     python -m world_amd.tools morph a44k.wav b48k.wav -o out.wav --fs 48000       # --fs on analysis, transform, mcd, morph
+    python -m world_amd.tools features a.wav b.wav ... --outdir feats --order 59  # -> feats/a.lf0 a.mgc a.bap (float32)
+    python -m world_amd.tools features-synthesis a.lf0 a.mgc a.bap --fs 48000 --order 59 -o a.wav
+    python -m world_amd.tools mcd ref.wav test.wav --mcep 24                      # MCD on all-pass mel-cepstra c1 .. c24
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -32,6 +35,12 @@ up, decode, conversion and the 16-bit quantiser run on the device, int16 comes d
 and the analysis -- nothing is quantised in between -- so files of any rates can be used together (and an 8 kHz recording,
 below D4C's range, analysed at 16 kHz).  Files are still batched per SOURCE rate, one conversion per batch; outputs carry F.
 Without --fs every tool behaves as before, refusals of mixed rates included.
+`features` writes what TTS and voice-conversion corpora are stored in, headerless little-endian float32 (the HTS / Merlin
+convention): .lf0 = ln F0 per frame, -1e10 where unvoiced; .mgc = [frames][order + 1] mel-cepstra by all-pass warping
+(world_hip_sp2mc: SPTK's freqt, what other WORLD bindings call sp2mc; alpha defaults to world_hip_mcep_alpha of the rate);
+.bap = CodeAperiodicity's band values.  `features-synthesis` is the way back (world_hip_mc2sp, DecodeAperiodicity, synthesis).
+`mcd --mcep M` scores c1 .. cM of those cepstra instead of the reference coder's, the figure published MCDs are computed on;
+the alignment itself is unchanged.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -286,10 +295,32 @@ def _align_to(wh, a, x, fs, x_len):
     return map_b
 
 
-def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch=64, fs=None, quality="best"):
+def _mcep_block(wh, x, fs, x_len, frame_period, order, alpha):
+    """_coded_block with all-pass mel-cepstra: analyze, then sp2mc of every utterance's frames straight into columns
+    2 .. 2 + order of coded-style records [0, 0, c0 .. c_order] -> (block, first row, frames)"""
+    import torch
+    _, _, sp, _, nf = wh.analyze(x, fs, x_len=x_len, frame_period=frame_period)
+    nf = np.asarray(nf, dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(nf)[:-1]])
+    block = torch.zeros((int(nf.sum()), 2 + order + 1), dtype=torch.float64, device=wh.device)
+    alpha = wh.mcep_alpha(fs) if alpha is None else alpha
+    try:
+        for u, (r, n) in enumerate(zip(first, nf)):
+            wh.sp2mc(sp[u, :int(n)], order, alpha, out=block[int(r):int(r) + int(n), 2:])
+    except RuntimeError as e:                                   # the library's refusal of an order or an alpha
+        raise ValueError(str(e)) from None
+    return block, first, nf
+
+
+def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch=64, fs=None, quality="best", mcep=None,
+              alpha=None):
     """[(ref.wav, test.wav)] -> [(frames of ref, frames of test, path length, MCD in dB)]: every file analysed once into
     coded records (batches per sampling rate), every pair aligned on the device, one align call per rate.  fs: every file
-    is converted to that rate on the device first (batches per source rate), and pairs of any two rates can be scored"""
+    is converted to that rate on the device first (batches per source rate), and pairs of any two rates can be scored.
+    mcep: the features are the all-pass mel-cepstra c0 .. c_mcep (alpha: world_hip_mcep_alpha of the rate unless given)
+    instead of `dims` coefficients of the reference's coder"""
+    if mcep is not None:
+        dims = mcep + 1
     target = fs
     by_source, rate_of = {}, {}
     for path in dict.fromkeys(p for pair in pairs for p in pair):
@@ -311,7 +342,10 @@ def mcd_pairs(wh, pairs, dims=ALIGN_DIMS, keep_c0=False, frame_period=5.0, batch
                 chunk = group[lo:lo + batch]
                 x, x_len = _load_batch(wh, chunk)
                 x, x_len, _ = _at_rate(wh, x, x_len, source, target, quality)
-                block, first, nf = _coded_block(wh, x, fs, x_len, frame_period, dims)
+                if mcep is None:
+                    block, first, nf = _coded_block(wh, x, fs, x_len, frame_period, dims)
+                else:
+                    block, first, nf = _mcep_block(wh, x, fs, x_len, frame_period, mcep, alpha)
                 blocks.append(block)
                 for path, r, n in zip(chunk, first, nf):
                     where[path] = (at + int(r), int(n))
@@ -334,9 +368,11 @@ def _mcd(a):
         sys.exit("mcd: the files come in pairs: REF.wav TEST.wav [REF2.wav TEST2.wav ...]")
     if a.dims < (1 if a.keep_c0 else 2):
         sys.exit(f"mcd: --dims {a.dims} leaves no coefficient to compare")
+    if a.mcep is not None and a.mcep < (0 if a.keep_c0 else 1):
+        sys.exit(f"mcd: --mcep {a.mcep} leaves no coefficient to compare")
     pairs = list(zip(a.wav[0::2], a.wav[1::2]))
     try:
-        results = mcd_pairs(WorldHip(), pairs, a.dims, a.keep_c0, a.s, a.batch, a.fs, a.quality)
+        results = mcd_pairs(WorldHip(), pairs, a.dims, a.keep_c0, a.s, a.batch, a.fs, a.quality, a.mcep, a.alpha)
     except ValueError as e:
         sys.exit(f"mcd: {e}")
     for (ref, test), (na, nb, K, mcd) in zip(pairs, results):
@@ -430,6 +466,73 @@ def _resample(a):
                 samples += n
     print(f"{len(a.wav)} file(s), {samples} samples at {a.fs} Hz -> {a.outdir}")
 
+UNVOICED_LF0 = -1e10  # .lf0 of an unvoiced frame (the HTS / Merlin convention)
+
+
+def _features(a):
+    _check_rate("features", a)
+    if a.order < 0:
+        sys.exit(f"features: --order {a.order}")
+    wh = WorldHip()
+    by_rate = {}
+    try:
+        for path in a.wav:
+            by_rate.setdefault(wh.wav_layout(path)[0], []).append(path)
+    except OSError as e:
+        sys.exit(f"features: not a readable WAV file ({e})")
+    os.makedirs(a.outdir, exist_ok=True)
+    frames = 0
+    for src_fs, group in sorted(by_rate.items()):
+        for at in range(0, len(group), a.batch):
+            chunk = group[at:at + a.batch]
+            x, x_len = _load_batch(wh, chunk)
+            try:
+                x, x_len, fs = _at_rate(wh, x, x_len, src_fs, a.fs, a.quality)
+                _, f0, sp, ap, nf = wh.analyze(x, fs, x_len=x_len, f0_method=a.f0, frame_period=a.s, f0_floor=a.f, f0_ceil=a.c)
+                fft_size = cheaptrick_fft_size(fs, 71.0)
+                alpha = wh.mcep_alpha(fs) if a.alpha is None else a.alpha
+                mgc = wh.sp2mc(sp, a.order, alpha).cpu().numpy()
+                bap = wh.code_aperiodicity(ap, fs, fft_size).cpu().numpy()
+            except (ValueError, RuntimeError) as e:
+                sys.exit(f"features: {e}")
+            f0 = f0.cpu().numpy()
+            for row, path in enumerate(chunk):
+                n, stem = int(nf[row]), os.path.join(a.outdir, os.path.splitext(os.path.basename(path))[0])
+                voiced = f0[row, :n] > 0
+                lf0 = np.where(voiced, np.log(np.where(voiced, f0[row, :n], 1.0)), UNVOICED_LF0)
+                for ext, v in ((".lf0", lf0), (".mgc", mgc[row, :n]), (".bap", bap[row, :n])):
+                    np.ascontiguousarray(v).astype("<f4").tofile(stem + ext)
+                frames += n
+    print(f"{len(a.wav)} file(s), {frames} frames -> {a.outdir}")
+
+
+def _features_synthesis(a):
+    import torch
+    wh = WorldHip()
+    if a.fs < 1 or a.order < 0:
+        sys.exit(f"features-synthesis: --fs {a.fs} --order {a.order}")
+    try:
+        lf0, mgc, bap = (np.fromfile(path, dtype="<f4").astype(np.float64) for path in (a.lf0, a.mgc, a.bap))
+    except OSError as e:
+        sys.exit(f"features-synthesis: {e}")
+    n, nap = lf0.size, wh.lib.GetNumberOfAperiodicities(a.fs)
+    if n < 1 or mgc.size != n * (a.order + 1) or nap < 1 or bap.size != n * nap:
+        sys.exit(f"features-synthesis: {n} frames of ln F0, but {mgc.size} values of {a.order + 1} mel-cepstra and {bap.size} "
+                 f"of {nap} band aperiodicities")
+    fft_size = cheaptrick_fft_size(a.fs, 71.0)
+    f0 = np.where(lf0 > 0.5 * UNVOICED_LF0, np.exp(np.where(lf0 > 0.5 * UNVOICED_LF0, lf0, 0.0)), 0.0)
+    try:
+        alpha = wh.mcep_alpha(a.fs) if a.alpha is None else a.alpha
+        sp = wh.mc2sp(torch.from_numpy(mgc.reshape(n, a.order + 1)).to(wh.device), alpha, fft_size)
+        ap = wh.decode_aperiodicity(torch.from_numpy(bap.reshape(n, nap)).to(wh.device), a.fs, fft_size)
+        y_length = int(n * a.s / 1000.0 * a.fs)
+        y = wh.synthesis(torch.from_numpy(f0).to(wh.device)[None], sp[None], ap[None], np.array([n], dtype=np.int32), fft_size,
+                         a.s, a.fs, np.array([y_length], dtype=np.int32))
+    except (ValueError, RuntimeError) as e:
+        sys.exit(f"features-synthesis: {e}")
+    wh.wavwrite(a.o, y[0, :y_length], a.fs)
+    print(f"{n} frames -> {a.o} ({y_length} samples at {a.fs} Hz)")
+
 
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m world_amd.tools", description=__doc__.split("\n\n")[0])
@@ -500,7 +603,31 @@ def main(argv=None):
     rs.add_argument("--quality", choices=("best", "fast"), default="best", help="the filter: 64 or 16 zero crossings a side")
     rs.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
     rs.set_defaults(run=_resample)
-    for tool in (an, tr, mc, mo):
+    mc.add_argument("--mcep", type=int, default=None, metavar="M",
+                    help="score the all-pass mel-cepstra c1 .. cM (sp2mc) instead of --dims coefficients of the reference's coder")
+    mc.add_argument("--alpha", type=float, default=None, help="the all-pass constant of --mcep (default: the rate's)")
+    fe = sub.add_parser("features", help="WAV files -> .lf0 / .mgc / .bap files (float32)")
+    fe.add_argument("wav", nargs="+")
+    fe.add_argument("--outdir", default=".")
+    fe.add_argument("--order", type=int, required=True, metavar="M", help="mel-cepstra c0 .. cM per frame")
+    fe.add_argument("--alpha", type=float, default=None, help="the all-pass constant (default: the rate's, 0.41 at 16 kHz)")
+    fe.add_argument("--f0", choices=("harvest", "dio"), default="harvest", help="dio = Dio + StoneMask")
+    fe.add_argument("-f", type=float, default=71.0, help="floor of the F0 range (Hz)")
+    fe.add_argument("-c", type=float, default=800.0, help="ceiling of the F0 range (Hz)")
+    fe.add_argument("-s", type=float, default=5.0, help="frame shift (ms)")
+    fe.add_argument("--batch", type=int, default=64, help="utterances per GPU call")
+    fe.set_defaults(run=_features)
+    fs_ = sub.add_parser("features-synthesis", help=".lf0 + .mgc + .bap -> WAV")
+    fs_.add_argument("lf0")
+    fs_.add_argument("mgc")
+    fs_.add_argument("bap")
+    fs_.add_argument("--fs", type=int, required=True, metavar="F", help="the sampling rate the features were made at (Hz)")
+    fs_.add_argument("--order", type=int, required=True, metavar="M")
+    fs_.add_argument("--alpha", type=float, default=None, help="the all-pass constant (default: the rate's)")
+    fs_.add_argument("-s", type=float, default=5.0, help="frame shift (ms)")
+    fs_.add_argument("-o", default="output.wav")
+    fs_.set_defaults(run=_features_synthesis)
+    for tool in (an, tr, mc, mo, fe):
         tool.add_argument("--fs", type=int, default=None, metavar="F",
                           help="convert every input whose sampling rate differs from F to F on the device first")
         tool.add_argument("--quality", choices=("best", "fast"), default="best", help="the filter of that conversion")
