@@ -642,6 +642,59 @@ WORLD_HIP_API int world_hip_sp2mc(WorldHipContext *ctx, int rows, int fft_size, 
 WORLD_HIP_API int world_hip_mc2sp(WorldHipContext *ctx, int rows, int fft_size, int order, double alpha, const double *d_mc,
                                   long long mc_row_stride, double *d_sp, long long sp_row_stride);
 
+/* Dynamic features (delta, delta-delta) and maximum-likelihood parameter generation (MLPG) on the device: what a TTS or
+ * voice-conversion stack puts between the statics and an acoustic model, and between the model and the synthesiser.  The
+ * reference has no such function; THIS COMMENT IS THE RULE.
+ * An utterance u has T = n_frames[u] frames (host array), a stream `dim` = D static dimensions.  There are n_win windows,
+ * 1 <= n_win <= 4, all of half-width L = half_width in {0, 1, 2}, given as host doubles win[n_win][2 L + 1] (zeros at the
+ * ends are allowed).  Window 0 must be the identity, 1 at tau = 0 and 0 elsewhere: the system below is then positive
+ * definite whenever every static variance is positive.  The usual set is [0 1 0], [-0.5 0 0.5], [1 -2 1].  d_mask[u][t]
+ * (bytes, mask_utt_stride bytes between utterances; non-zero = present; NULL: every frame is present) marks the frames
+ * that exist: the unvoiced frames of an .lf0 stream are the masked ones.
+ *   coupling.  A term (t, tau) COUNTS when every frame from t to t + tau inclusive lies inside the utterance and is
+ *            present.  Every maximal run of present frames is therefore handled exactly as an utterance of its own, its
+ *            windows truncated at its ends (the band-matrix convention of Merlin / nnmnkwii).
+ *   deltas (world_hip_delta_batch).  For a present frame t,
+ *              o[t][w D + d] = sum over tau = -L .. L, (t, tau) counts, of win[w][tau] c[t + tau][d],
+ *            in ascending tau from +0.0, every product and every sum rounded (no FMA).  For a masked frame all n_win D
+ *            outputs are `fill`.  Masked rows of d_c are never read.
+ *   generation (world_hip_mlpg_batch).  For each (u, d) independently, c[.][d] over the present frames minimises
+ *              sum over present t, over w, of p[t][w D + d] (mu[t][w D + d] - sum over tau, (t, tau) counts, of
+ *                                                            win[w][tau] c[t + tau][d])^2,
+ *            p = 1 / variance, or the given value itself where `precision` is non-zero: the system R c = r, R = W' P W,
+ *            r = W' P mu, R symmetric positive definite with half-bandwidth 2 L.  It is solved by a banded L D L' without
+ *            pivoting or square roots in double precision.  Masked frames of the output get `fill`; masked rows of d_mean
+ *            and d_var are never read.
+ *   layouts.  Strides are counted in doubles.  d_mean[u][t][n_win D]: utterance stride and row stride >= n_win D; d_var
+ *            the same, where a row stride of 0 means one row per utterance and an utterance stride of 0 as well one global
+ *            row (the common case).  d_c[u][t][D], d_out[u][t][D] (generation) or [u][t][n_win D] (deltas) have strides of
+ *            their own.  Doubles beyond a row's extent and rows at or beyond n_frames[u] are never written.
+ *   data.     A variance (precision) in a present frame that is not finite and positive makes that (u, d) column
+ *            unspecified (it may be NaN); no other column changes, the call returns and the next call is unaffected.
+ *   determinism.  A column's result depends on nothing but that column's data, T, the mask and the windows: not on the
+ *            batch, the column's position, the strides, the launch shape or a graph replay.
+ * Refused, before any GPU work and with nothing written (1 is returned, the reason is in world_hip_last_error): n_utt < 1,
+ * dim < 1, any n_frames[u] < 1, a NULL win / n_frames / d_c / d_mean / d_var / d_out, n_win outside [1, 4], half_width
+ * outside [0, 2], a window coefficient that is not finite, window 0 not the identity, a row stride shorter than the row (a 0
+ * stride of d_var excepted), a negative utterance stride, utterances of the output (or of the mask) that run into each
+ * other, an output range that overlaps an input range, n_win dim above INT_MAX or more than 2^38 elements (frames x dim)
+ * in one utterance.
+ * Stream order and errors as the other batched calls.  The generation keeps the factor and the scaled right-hand side,
+ * [max T][2 L + 1][n_utt D] doubles, in the context's workspace (world_hip_workspace_bytes counts it; none for L = 0 or
+ * for the deltas); once the workspace has the size a call neither allocates nor waits and can be captured, and a capture
+ * goes stale when the workspace grows, as for the other batched calls. */
+WORLD_HIP_API int world_hip_delta_batch(WorldHipContext *ctx, int n_utt, int dim, int n_win, int half_width,
+                                        const double *win /* host, [n_win][2 half_width + 1] */, const int *n_frames /* host */,
+                                        const unsigned char *d_mask, long long mask_utt_stride, const double *d_c,
+                                        long long c_utt_stride, long long c_row_stride, double fill, double *d_out,
+                                        long long out_utt_stride, long long out_row_stride);
+WORLD_HIP_API int world_hip_mlpg_batch(WorldHipContext *ctx, int n_utt, int dim, int n_win, int half_width,
+                                       const double *win /* host, [n_win][2 half_width + 1] */, const int *n_frames /* host */,
+                                       const unsigned char *d_mask, long long mask_utt_stride, const double *d_mean,
+                                       long long mean_utt_stride, long long mean_row_stride, const double *d_var,
+                                       long long var_utt_stride, long long var_row_stride, int precision, double fill,
+                                       double *d_out, long long out_utt_stride, long long out_row_stride);
+
 /* Coders on dense device rows (reference src/codec.cpp:217-324).  Rows are independent:
  *   spectrogram / aperiodicity  [rows][fft_size/2+1]
  *   coded spectral envelope     [rows][number_of_dimensions]

@@ -401,6 +401,12 @@ def load_library(path=LIB_PATH):
         lib.world_hip_mcep_tables.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp]
         for fn in (lib.world_hip_sp2mc, lib.world_hip_mc2sp):
             fn.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_longlong, vp, C.c_longlong]
+    if hasattr(lib, "world_hip_mlpg_batch"):                         # (likewise)
+        ll = C.c_longlong
+        lib.world_hip_delta_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, _ip, vp, ll, vp, ll, ll, C.c_double,
+                                              vp, ll, ll]
+        lib.world_hip_mlpg_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, _ip, vp, ll, vp, ll, ll, vp, ll, ll,
+                                             C.c_int, C.c_double, vp, ll, ll]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -1645,6 +1651,98 @@ class WorldHip:
         if order is None:
             order = int(mc.shape[-1]) - 1
         return self._mcep(True, mc, int(order) + 1, int(fft_size) // 2 + 1, fft_size, order, alpha, out, row_stride, rows)
+
+    # ---- dynamic features and parameter generation (include/world_hip.h: world_hip_delta_batch / world_hip_mlpg_batch) ----
+    DEFAULT_WINDOWS = ((0.0, 1.0, 0.0), (-0.5, 0.0, 0.5), (1.0, -2.0, 1.0))
+
+    @staticmethod
+    def _windows(windows):
+        """windows -> (float64 [n_win][2 L + 1], L): sequences of odd length, the shorter ones padded with zeros"""
+        rows = [np.asarray(w, dtype=np.float64).reshape(-1) for w in (WorldHip.DEFAULT_WINDOWS if windows is None else windows)]
+        if not rows or any(len(r) % 2 == 0 for r in rows):
+            raise ValueError("windows: at least one, each of odd length")
+        half = max(len(r) // 2 for r in rows)
+        win = np.zeros((len(rows), 2 * half + 1), dtype=np.float64)
+        for w, r in enumerate(rows):
+            win[w, half - len(r) // 2:half + len(r) // 2 + 1] = r
+        return win, half
+
+    def _frames3(self, x, what):
+        """[T][cols] or [U][T][cols] float64 on the device with adjacent columns -> the [U][T][cols] view"""
+        t = self.torch
+        assert x.dtype == t.float64 and x.is_cuda and x.device == self.device and x.dim() in (2, 3), f"{what}: [U][T][cols] float64 on {self.device}"
+        x3 = x[None] if x.dim() == 2 else x
+        assert x3.shape[2] == 1 or x3.stride(2) == 1, f"{what}: adjacent columns"
+        return x3
+
+    def _mlpg_call(self, generate, x, var, windows, mask, n_frames, precision, fill, out):
+        t = self.torch
+        what = "mlpg" if generate else "deltas"
+        if not hasattr(self.lib, "world_hip_mlpg_batch"):
+            raise RuntimeError("this libworld_hip.so has no parameter generation (world_hip_mlpg_batch)")
+        win, half = self._windows(windows)
+        n_win = win.shape[0]
+        x3 = self._frames3(x, what)
+        U, T, cols = (int(v) for v in x3.shape)
+        if generate:
+            if cols % n_win:
+                raise ValueError(f"mlpg: {cols} columns are no multiple of the {n_win} windows")
+            dim, out_cols = cols // n_win, cols // n_win
+        else:
+            dim, out_cols = cols, cols * n_win
+        nf = np.full(U, T, dtype=np.int32) if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32).reshape(-1)
+        if nf.shape != (U,) or (nf.size and int(nf.max()) > T):
+            raise ValueError(f"{what}: n_frames must be {U} counts of at most {T}")
+        m_ptr, m_us = None, 0
+        if mask is not None:
+            assert mask.device == x.device and mask.dtype in (t.bool, t.uint8), f"{what}: mask must be bool or uint8 on the device"
+            m3 = mask[None] if mask.dim() == 1 else mask
+            assert tuple(m3.shape) == (U, T) and (T == 1 or m3.stride(1) == 1), f"{what}: mask must be [{U}][{T}] with adjacent frames"
+            m_ptr, m_us = m3.data_ptr(), int(m3.stride(0))
+        v_ptr, v_us, v_rs = None, 0, 0
+        if generate:
+            assert var.dtype == t.float64 and var.device == x.device and var.shape[-1] == cols and \
+                (cols == 1 or var.stride(-1) == 1), f"mlpg: var must be [..., {cols}] float64 with adjacent columns"
+            if var.dim() == 1:                                       # one global row
+                var = var[None, None]
+            elif var.dim() == 2:                                     # one utterance's rows, or one row per utterance
+                var = var[None] if x.dim() == 2 else var[:, None]
+            assert var.dim() == 3 and var.shape[0] in (1, U) and var.shape[1] in (1, T), \
+                f"mlpg: var must be [{U} or 1][{T} or 1][{cols}], [{U}][{cols}] or [{cols}]"
+            v_ptr = var.data_ptr()
+            v_us = int(var.stride(0)) if var.shape[0] > 1 else 0
+            v_rs = int(var.stride(1)) if var.shape[1] > 1 else 0
+        ret = out
+        if out is None:
+            out = t.empty((U, T, out_cols), dtype=t.float64, device=x.device)
+            ret = out[0] if x.dim() == 2 else out
+        o3 = self._frames3(out, what)
+        assert tuple(o3.shape) == (U, T, out_cols), f"{what}: out must be [{U}][{T}][{out_cols}]"
+        rs = lambda a, c: int(a.stride(1)) if a.shape[1] > 1 else max(int(a.stride(1)), c)
+        us = lambda a: int(a.stride(0)) if a.shape[0] > 1 else 0
+        if generate:
+            rc = self.lib.world_hip_mlpg_batch(self._context(), U, dim, n_win, half, win.ctypes.data, nf.ctypes.data_as(_ip), m_ptr, m_us, x3.data_ptr(),
+                                               us(x3), rs(x3, cols), v_ptr, v_us, v_rs, int(bool(precision)), float(fill),
+                                               o3.data_ptr(), us(o3), rs(o3, out_cols))
+        else:
+            rc = self.lib.world_hip_delta_batch(self._context(), U, dim, n_win, half, win.ctypes.data, nf.ctypes.data_as(_ip), m_ptr, m_us,
+                                                x3.data_ptr(), us(x3), rs(x3, cols), float(fill), o3.data_ptr(), us(o3),
+                                                rs(o3, out_cols))
+        self._check(rc, what)
+        return ret
+
+    def deltas(self, x, windows=None, mask=None, fill=0.0, n_frames=None, out=None):
+        """statics -> [static, delta, delta-delta, ...]: x [U][T][D] (or [T][D]) float64 on the device, strides honoured;
+        windows: sequences of odd length, the first the identity (default: [1], [-0.5 0 0.5], [1 -2 1]); mask [U][T] bool or
+        uint8 marks the frames that exist (windows are truncated at the ends of every run), masked frames get `fill`;
+        n_frames: per-utterance lengths (host).  Returns [U][T][n_win D] (or [T][n_win D]), or out."""
+        return self._mlpg_call(False, x, None, windows, mask, n_frames, False, fill, out)
+
+    def mlpg(self, mean, var, windows=None, mask=None, precision=False, fill=0.0, n_frames=None, out=None):
+        """the maximum-likelihood static trajectory under predicted static / delta / delta-delta means and variances:
+        mean [U][T][n_win D] (or [T][n_win D]); var of the same shape, [U][1][n_win D] or [U][n_win D] (one row per
+        utterance) or [n_win D] (one global row); precision=True: var holds 1 / variance.  Returns [U][T][D] (or [T][D])."""
+        return self._mlpg_call(True, mean, var, windows, mask, n_frames, precision, fill, out)
 
     def probe_machine(self):
         """world_hip_probe_machine (include/world_hip.h): ~50 ms of microbenchmarks that characterise the box"""

@@ -9,6 +9,7 @@
 #include "../../include/world_hip.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -2130,6 +2131,99 @@ static void run_mcep(WorldHipContext *c, bool decode, int rows, int fft_size, in
   launch_mcep(p, decode, c->stream);
 }
 
+// Dynamic features and parameter generation (include/world_hip.h: world_hip_delta_batch / world_hip_mlpg_batch; mlpg.inc).
+// Everything the host can know is refused before any GPU work.  The stencil (generate == false) reads the statics
+// [u][t][dim] as `d_in` and needs no workspace; the generation reads means and variances [u][t][n_win dim] and keeps the
+// factor and the scaled right-hand side of every system, [max T][2 L + 1][n_utt dim] doubles, in the arena.
+static void run_mlpg_or_delta(WorldHipContext *c, bool generate, int n_utt, int dim, int n_win, int half_width,
+                              const double *win, const int *n_frames, const unsigned char *d_mask, long long mask_us,
+                              const double *d_in, long long in_us, long long in_rs, const double *d_var, long long var_us,
+                              long long var_rs, int precision, double fill, double *d_out, long long out_us, long long out_rs) {
+  const char *name = generate ? "mlpg" : "delta";
+  if (n_utt < 1) fail("%s: n_utt must be positive", name);
+  if (dim < 1) fail("%s: dim must be positive", name);
+  if (!win || !n_frames || !d_in || !d_out || (generate && !d_var))
+    fail("%s: null %s", name, generate ? "win / n_frames / d_mean / d_var / d_out" : "win / n_frames / d_c / d_out");
+  if (n_win < 1 || n_win > 4) fail("%s: n_win %d outside [1, 4]", name, n_win);
+  if (half_width < 0 || half_width > 2) fail("%s: half_width %d outside [0, 2]", name, half_width);
+  const int taps = 2 * half_width + 1;
+  for (int k = 0; k < n_win * taps; ++k)
+    if (!std::isfinite(win[k])) fail("%s: window %d has a coefficient that is not finite", name, k / taps);
+  for (int k = 0; k < taps; ++k)
+    if (win[k] != (k == half_width ? 1.0 : 0.0)) fail("%s: window 0 must be the identity (1 at tau = 0, 0 elsewhere)", name);
+  if ((long long)n_win * dim > INT_MAX) fail("%s: n_win * dim above INT_MAX", name);
+  int max_frames = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (n_frames[u] < 1) fail("%s: n_frames[%d]=%d; an utterance needs a frame", name, u, n_frames[u]);
+    max_frames = std::max(max_frames, n_frames[u]);
+  }
+  if ((long long)max_frames * dim > (1LL << 38)) fail("%s: %d frames of %d dimensions are more than 2^38 elements", name, max_frames, dim);
+  const long long in_cols = generate ? (long long)n_win * dim : dim, out_cols = generate ? dim : (long long)n_win * dim;
+  const char *in_name = generate ? "mean" : "c";
+  if (in_rs < in_cols) fail("%s: %s_row_stride %lld below the row's %lld doubles", name, in_name, in_rs, in_cols);
+  if (out_rs < out_cols) fail("%s: out_row_stride %lld below the row's %lld doubles", name, out_rs, out_cols);
+  if (generate && var_rs != 0 && var_rs < in_cols) fail("%s: var_row_stride %lld is neither 0 nor the row's %lld doubles or more", name, var_rs, in_cols);
+  if (in_us < 0 || out_us < 0 || (generate && var_us < 0) || (d_mask && mask_us < 0)) fail("%s: a negative utterance stride", name);
+  // the doubles (bytes for the mask) each array spans; utterances of the output may not run into each other
+  long long in_span = 0, var_span = 0, out_span = 0, mask_span = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const long long rows = n_frames[u] - 1;
+    if (u + 1 < n_utt && rows * out_rs + out_cols > out_us)
+      fail("%s: out_utt_stride %lld below utterance %d's %lld doubles", name, out_us, u, rows * out_rs + out_cols);
+    if (d_mask && u + 1 < n_utt && n_frames[u] > mask_us) fail("%s: mask_utt_stride %lld below n_frames[%d]=%d", name, mask_us, u, n_frames[u]);
+    in_span = std::max(in_span, u * in_us + rows * in_rs + in_cols);
+    var_span = std::max(var_span, u * var_us + rows * var_rs + in_cols);
+    out_span = std::max(out_span, u * out_us + rows * out_rs + out_cols);
+    mask_span = std::max(mask_span, u * mask_us + rows + 1);
+  }
+  {
+    const char *o_lo = reinterpret_cast<const char *>(d_out), *o_hi = o_lo + sizeof(double) * (size_t)out_span;
+    auto overlaps = [&](const void *q, size_t bytes) {
+      const char *lo = static_cast<const char *>(q);
+      return q && o_lo < lo + bytes && lo < o_hi;
+    };
+    if (overlaps(d_in, sizeof(double) * (size_t)in_span) || (generate && overlaps(d_var, sizeof(double) * (size_t)var_span)) ||
+        overlaps(d_mask, (size_t)mask_span))
+      fail("%s: the output range overlaps an input range; the output may not alias an input", name);
+  }
+  MlpgParams p;
+  p.ws = nullptr;
+  if (generate && half_width > 0)
+    begin_stage(c, [&](Arena &a) { p.ws = a.take<double>(mlpg_workspace_doubles(n_utt, dim, max_frames, half_width)); });
+  else
+    open_uploads(c);                                        // (no workspace: prepared offsets stay valid)
+  p.mean = d_in; p.var = d_var; p.out = d_out; p.mask = d_mask;
+  p.mean_us = in_us; p.mean_rs = in_rs; p.var_us = var_us; p.var_rs = var_rs; p.out_us = out_us; p.out_rs = out_rs;
+  p.mask_us = mask_us;
+  p.n_sys = (long long)n_utt * dim;
+  p.dim = dim; p.n_win = n_win; p.precision = precision != 0; p.fill = fill;
+  for (int w = 0; w < 4; ++w)
+    for (int k = 0; k < 5; ++k) {
+      const int tau = k - 2;
+      p.win[w][k] = w < n_win && tau >= -half_width && tau <= half_width ? win[w * taps + tau + half_width] : 0.0;
+    }
+  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  for (int u0 = 0; u0 < n_utt; u0 += 65535) {               // (a grid's y extent)
+    const int n = std::min(65535, n_utt - u0);
+    p.u0 = u0;
+    if (generate) launch_mlpg(p, half_width, n, max_frames, c->stream);
+    else launch_delta(p, half_width, n, max_frames, c->stream);
+  }
+}
+static void run_delta(WorldHipContext *c, int n_utt, int dim, int n_win, int half_width, const double *win, const int *n_frames,
+                      const unsigned char *d_mask, long long mask_us, const double *d_c, long long c_us, long long c_rs,
+                      double fill, double *d_out, long long out_us, long long out_rs) {
+  run_mlpg_or_delta(c, false, n_utt, dim, n_win, half_width, win, n_frames, d_mask, mask_us, d_c, c_us, c_rs, nullptr, 0, 0, 0,
+                    fill, d_out, out_us, out_rs);
+}
+static void run_mlpg(WorldHipContext *c, int n_utt, int dim, int n_win, int half_width, const double *win, const int *n_frames,
+                     const unsigned char *d_mask, long long mask_us, const double *d_mean, long long mean_us, long long mean_rs,
+                     const double *d_var, long long var_us, long long var_rs, int precision, double fill, double *d_out,
+                     long long out_us, long long out_rs) {
+  run_mlpg_or_delta(c, true, n_utt, dim, n_win, half_width, win, n_frames, d_mask, mask_us, d_mean, mean_us, mean_rs, d_var,
+                    var_us, var_rs, precision, fill, d_out, out_us, out_rs);
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2864,6 +2958,25 @@ int world_hip_sp2mc(WorldHipContext *c, int rows, int fft_size, int order, doubl
 int world_hip_mc2sp(WorldHipContext *c, int rows, int fft_size, int order, double alpha, const double *d_mc,
                     long long mc_row_stride, double *d_sp, long long sp_row_stride) {
   return guarded(c, [&] { run_mcep(c, true, rows, fft_size, order, alpha, d_mc, mc_row_stride, d_sp, sp_row_stride); });
+}
+int world_hip_delta_batch(WorldHipContext *c, int n_utt, int dim, int n_win, int half_width, const double *win,
+                          const int *n_frames, const unsigned char *d_mask, long long mask_utt_stride, const double *d_c,
+                          long long c_utt_stride, long long c_row_stride, double fill, double *d_out,
+                          long long out_utt_stride, long long out_row_stride) {
+  return guarded(c, [&] {
+    run_delta(c, n_utt, dim, n_win, half_width, win, n_frames, d_mask, mask_utt_stride, d_c, c_utt_stride, c_row_stride, fill,
+              d_out, out_utt_stride, out_row_stride);
+  });
+}
+int world_hip_mlpg_batch(WorldHipContext *c, int n_utt, int dim, int n_win, int half_width, const double *win,
+                         const int *n_frames, const unsigned char *d_mask, long long mask_utt_stride, const double *d_mean,
+                         long long mean_utt_stride, long long mean_row_stride, const double *d_var, long long var_utt_stride,
+                         long long var_row_stride, int precision, double fill, double *d_out, long long out_utt_stride,
+                         long long out_row_stride) {
+  return guarded(c, [&] {
+    run_mlpg(c, n_utt, dim, n_win, half_width, win, n_frames, d_mask, mask_utt_stride, d_mean, mean_utt_stride,
+             mean_row_stride, d_var, var_utt_stride, var_row_stride, precision, fill, d_out, out_utt_stride, out_row_stride);
+  });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||

@@ -181,4 +181,25 @@ struct McepParams {
 void mcep_table_shape(bool decode, int fft_size, int order, int *k_pad, int *n_pad);
 void launch_mcep(const McepParams &p, bool decode, hipStream_t stream);
 
+// Dynamic features and parameter generation (world_hip_delta_batch / world_hip_mlpg_batch; mlpg.inc).  One block for both:
+// the stencil reads `mean` as the statics [u][t][dim] and writes out [u][t][n_win dim]; the generation reads mean and var
+// [u][t][n_win dim] and writes out [u][t][dim].  Strides are counted in doubles (mask_us in bytes); var_rs and var_us may
+// be 0.  `win` holds the windows centred: win[w][2 + tau], zeros beyond the half-width.
+struct MlpgParams {
+  const double *mean, *var;
+  double *out;
+  const unsigned char *mask;      // [u][t], non-zero = present; nullptr: every frame is
+  double *ws;                     // the sweeps' workspace [t][B + 1][n_sys] (mlpg_workspace_doubles)
+  const int *n_frames;            // device, [n_utt]
+  long long mean_us, mean_rs, var_us, var_rs, out_us, out_rs, mask_us;
+  long long n_sys;                // systems of the whole call: n_utt * dim
+  int u0;                         // first utterance of this launch
+  int dim, n_win, precision;
+  double fill;
+  double win[4][5];
+};
+size_t mlpg_workspace_doubles(int n_utt, int dim, int max_frames, int half_width);
+void launch_delta(const MlpgParams &p, int half_width, int n_utt, int max_frames, hipStream_t stream);
+void launch_mlpg(const MlpgParams &p, int half_width, int n_utt, int max_frames, hipStream_t stream);
+
 }  // namespace world_hip

@@ -16,6 +16,8 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools features a.wav b.wav ... --outdir feats --order 59  # -> feats/a.lf0 a.mgc a.bap (float32)
     python -m world_amd.tools features-synthesis a.lf0 a.mgc a.bap --fs 48000 --order 59 -o a.wav
     python -m world_amd.tools mcd ref.wav test.wav --mcep 24                      # MCD on all-pass mel-cepstra c1 .. c24
+    python -m world_amd.tools deltas a.mgc --dim 60 -o a.mgc.dyn                  # [frames][60] -> [frames][180]: static, delta, delta-delta
+    python -m world_amd.tools mlpg mean.mgc.dyn var.mgc.dyn --dim 60 -o a.mgc     # the smooth trajectory under means and variances
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -41,6 +43,11 @@ convention): .lf0 = ln F0 per frame, -1e10 where unvoiced; .mgc = [frames][order
 .bap = CodeAperiodicity's band values.  `features-synthesis` is the way back (world_hip_mc2sp, DecodeAperiodicity, synthesis).
 `mcd --mcep M` scores c1 .. cM of those cepstra instead of the reference coder's, the figure published MCDs are computed on;
 the alignment itself is unchanged.
+`deltas` appends the dynamic features acoustic models are trained on (world_hip_delta_batch, windows [1], [-0.5 0 0.5],
+[1 -2 1]) to a float32 file of [frames][dim] statics; `mlpg` is the way back from a model's output (world_hip_mlpg_batch,
+maximum-likelihood parameter generation): a file of [frames][3 dim] means and one of as many rows, or of one row, of
+variances give the [frames][dim] trajectory, which goes into `features-synthesis` as it is.  With --lf0 (dim 1) the -1e10
+frames are masked: windows stop at the ends of every voiced run and unvoiced frames stay -1e10.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -534,6 +541,54 @@ def _features_synthesis(a):
     print(f"{n} frames -> {a.o} ({y_length} samples at {a.fs} Hz)")
 
 
+def _float_rows(tool, path, cols):
+    """a headerless float32 file of rows of `cols` values -> float64 [rows][cols]"""
+    try:
+        v = np.fromfile(path, dtype="<f4").astype(np.float64)
+    except OSError as e:
+        sys.exit(f"{tool}: {e}")
+    if v.size < cols or v.size % cols:
+        sys.exit(f"{tool}: {path} holds {v.size} values, no positive multiple of {cols}")
+    return v.reshape(-1, cols)
+
+
+def _deltas(a):
+    import torch
+    dim = 1 if a.lf0 and a.dim is None else a.dim
+    if dim is None or dim < 1:
+        sys.exit(f"deltas: --dim {dim}")
+    x = _float_rows("deltas", a.x, dim)
+    wh = WorldHip()
+    try:
+        d_x = torch.from_numpy(x).to(wh.device)
+        mask = (d_x[:, 0] > 0.5 * UNVOICED_LF0) if a.lf0 else None
+        out = wh.deltas(d_x, mask=mask, fill=UNVOICED_LF0 if a.lf0 else 0.0)
+    except (ValueError, RuntimeError) as e:
+        sys.exit(f"deltas: {e}")
+    out.cpu().numpy().astype("<f4").tofile(a.o)
+    print(f"{len(x)} frames of {dim} -> {a.o} ([{len(x)}][{out.shape[1]}])")
+
+
+def _mlpg(a):
+    import torch
+    dim = 1 if a.lf0 and a.dim is None else a.dim
+    if dim is None or dim < 1:
+        sys.exit(f"mlpg: --dim {dim}")
+    n_win = len(WorldHip.DEFAULT_WINDOWS)
+    mean, var = _float_rows("mlpg", a.mean, n_win * dim), _float_rows("mlpg", a.var, n_win * dim)
+    if len(var) not in (1, len(mean)):
+        sys.exit(f"mlpg: {len(mean)} rows of means but {len(var)} of variances (as many, or one)")
+    wh = WorldHip()
+    try:
+        d_mean, d_var = torch.from_numpy(mean).to(wh.device), torch.from_numpy(var).to(wh.device)
+        mask = (d_mean[:, 0] > 0.5 * UNVOICED_LF0) if a.lf0 else None
+        out = wh.mlpg(d_mean, d_var, mask=mask, precision=a.precision, fill=UNVOICED_LF0 if a.lf0 else 0.0)
+    except (ValueError, RuntimeError) as e:
+        sys.exit(f"mlpg: {e}")
+    out.cpu().numpy().astype("<f4").tofile(a.o)
+    print(f"{len(mean)} frames of {n_win} x {dim} -> {a.o} ([{len(mean)}][{dim}])")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m world_amd.tools", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="tool", required=True)
@@ -627,6 +682,20 @@ def main(argv=None):
     fs_.add_argument("-s", type=float, default=5.0, help="frame shift (ms)")
     fs_.add_argument("-o", default="output.wav")
     fs_.set_defaults(run=_features_synthesis)
+    de = sub.add_parser("deltas", help="[frames][dim] float32 statics -> [frames][3 dim]: static, delta, delta-delta")
+    de.add_argument("x", metavar="X")
+    de.add_argument("--dim", type=int, default=None, metavar="D", help="values per frame (with --lf0: 1)")
+    de.add_argument("--lf0", action="store_true", help="-1e10 marks unvoiced frames: masked, and -1e10 in the output")
+    de.add_argument("-o", required=True)
+    de.set_defaults(run=_deltas)
+    ml = sub.add_parser("mlpg", help="[frames][3 dim] means + variances ([frames] or 1 row) -> the [frames][dim] trajectory")
+    ml.add_argument("mean", metavar="MEAN")
+    ml.add_argument("var", metavar="VAR")
+    ml.add_argument("--dim", type=int, default=None, metavar="D", help="static values per frame (with --lf0: 1)")
+    ml.add_argument("--lf0", action="store_true", help="frames whose static mean is -1e10 are masked and stay -1e10")
+    ml.add_argument("--precision", action="store_true", help="VAR holds 1 / variance")
+    ml.add_argument("-o", required=True)
+    ml.set_defaults(run=_mlpg)
     for tool in (an, tr, mc, mo, fe):
         tool.add_argument("--fs", type=int, default=None, metavar="F",
                           help="convert every input whose sampling rate differs from F to F on the device first")
