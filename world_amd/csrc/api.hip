@@ -105,21 +105,31 @@ struct CodecTables {             // the coders' tables of one (fs, fft_size) (re
   double *d_wc_re = nullptr, *d_wc_im = nullptr, *d_wd_re = nullptr, *d_wd_im = nullptr;
 };
 
-struct ResampleTable {           // the resampler's device tables of one (L, M, design); a few are kept, least recently used out
+// The two kinds of entry of cached_table (below): a few of each are kept, least recently used out.  `used` is the
+// context's table_clock at the call that last used the entry, Host the host arrays put() uploads.
+struct ResampleTable {           // the resampler's device tables of one (L, M, design)
   long long L = 0, M = 0, W = 0;
   ResampleDesign design{0, 0.0, 0.0};
   double *d_coef = nullptr;      // [2 W][L], column r = m mod L (resample.h)
   int *d_kdiv = nullptr;         // [L]
-  unsigned long long used = 0;   // the call that last used it
+  unsigned long long used = 0;
+  struct Host { std::vector<double> coef; std::vector<int> kdiv; };
+  void put(WorldHipContext *c, const Host &h);
+  void drop(WorldHipContext *c);
+  unsigned long long bytes() const { return (2ull * W * sizeof(double) + sizeof(int)) * L; }
 };
 
-struct McepTable {               // one direction's device table of one (fft_size, order, alpha); a few are kept, least recently used out
+struct McepTable {               // one direction's device table of one (fft_size, order, alpha)
   int fft_size = 0, order = 0;
   unsigned long long alpha_bits = 0;
   bool decode = false;
   int k_pad = 0, n_pad = 0;
   double *d_table = nullptr;     // [k_pad][n_pad], zero beyond the table (codec.h: McepParams)
   unsigned long long used = 0;
+  using Host = std::vector<double>;
+  void put(WorldHipContext *c, const Host &h);
+  void drop(WorldHipContext *c);
+  unsigned long long bytes() const { return sizeof(double) * (unsigned long long)k_pad * n_pad; }
 };
 
 }  // namespace world_hip
@@ -174,9 +184,8 @@ struct WorldHipContext {
   int synth_pulse_cap = 0;       // caller's capacity per utterance (0 = automatic)
   std::vector<world_hip::CodecTables> codec_tables;
   std::vector<world_hip::ResampleTable> resample_tables;
-  unsigned long long resample_calls = 0;
   std::vector<world_hip::McepTable> mcep_tables;
-  unsigned long long mcep_calls = 0;
+  unsigned long long table_clock = 0;   // look-ups of the two caches above (cached_table)
   // the device arrays of tab and of the cached tables (bands, d_nuttall .. codec_tables, d_pk): allocated and freed by
   // put_table / drop_table only, released together when the context goes
   std::vector<void *> tables;
@@ -217,7 +226,7 @@ namespace world_hip {
 
 // Thrown by ensure_arena while a floor is held: the arena cannot move under the arrays kept there, so the call that holds
 // the floor grows it to `bytes` (floor included) with the floor released and starts over.  Invariant: a floor is set only
-// inside an attempt loop that catches this (run_resynthesis, run_synthesis_records).  It is not a std::exception, so that
+// by hold_at_floor, whose attempt loop catches this.  It is not a std::exception, so that
 // no stage's own error handling can swallow it; should it ever escape a call, guarded() turns it into an internal error
 // instead of letting it cross the C boundary.
 struct ArenaRegrow { size_t bytes; };
@@ -250,6 +259,35 @@ template <class T> static void put_table(WorldHipContext *c, T *&slot, size_t n,
 }
 template <class T> static void put_table(WorldHipContext *c, T *&slot, const std::vector<T> &host) {
   put_table(c, slot, host.size(), host.data());
+}
+
+// A small keyed cache of device tables, at most `keep` of them, least recently used out (resample_table, mcep_table).
+// `same` is the kind's key comparison and `refusal` its words for a miss under capture; on a miss `build` fills the new
+// entry's key and shape and returns the host arrays that the entry's put() uploads.
+template <class Table, class Same, class Build>
+static const Table &cached_table(WorldHipContext *c, std::vector<Table> &kept, size_t keep, const char *refusal, Same same,
+                                 Build build) {
+  ++c->table_clock;
+  for (Table &t : kept)
+    if (same(t)) {
+      t.used = c->table_clock;
+      return t;
+    }
+  // a miss allocates and uploads: neither is possible while the stream is being captured into a graph
+  if (devrt::is_capturing(c->stream)) fail("%s", refusal);
+  Table t;
+  const typename Table::Host host = build(t);
+  devrt::sync(c->stream);                        // (a kernel may still read the table that goes)
+  if (kept.size() >= keep) {
+    auto oldest = std::min_element(kept.begin(), kept.end(), [](const Table &a, const Table &b) { return a.used < b.used; });
+    oldest->drop(c);
+    kept.erase(oldest);
+  }
+  t.used = c->table_clock;
+  t.put(c, host);
+  devrt::sync(c->stream);                        // (the host copies go out of scope)
+  kept.push_back(t);
+  return kept.back();
 }
 
 // The randn() stream is a constant of the algorithm: its first `draws` values live in the device's
@@ -304,9 +342,25 @@ static char *small_array(WorldHipContext *c, const void *data, size_t bytes) {
   return kept->second.dev;
 }
 
-template <class T> static T *upload(WorldHipContext *c, const std::vector<T> &v) {
-  if (v.empty()) return reinterpret_cast<T *>(small_array(c, "", 1));
-  return reinterpret_cast<T *>(small_array(c, v.data(), sizeof(T) * v.size()));
+template <class T> static T *upload(WorldHipContext *c, const T *host, size_t n) {
+  if (n == 0) return reinterpret_cast<T *>(small_array(c, "", 1));
+  return reinterpret_cast<T *>(small_array(c, host, sizeof(T) * n));
+}
+template <class T> static T *upload(WorldHipContext *c, const std::vector<T> &v) { return upload(c, v.data(), v.size()); }
+
+// An output may not overlap an input or another output: the byte ranges of what a call touches.  Null pointers are skipped.
+struct Span { const void *p; size_t bytes; const char *name; };
+static void refuse_overlap(const char *call, std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+  auto meet = [](const Span &a, const Span &b) {
+    const char *a_lo = static_cast<const char *>(a.p), *b_lo = static_cast<const char *>(b.p);
+    return a.p && b.p && a_lo < b_lo + b.bytes && b_lo < a_lo + a.bytes;
+  };
+  for (const Span *o = outs.begin(); o != outs.end(); ++o) {
+    for (const Span &i : ins)
+      if (meet(*o, i)) fail("%s: %s overlaps %s; no output may alias an input", call, o->name, i.name);
+    for (const Span *o2 = o + 1; o2 != outs.end(); ++o2)
+      if (meet(*o, *o2)) fail("%s: %s overlaps %s", call, o->name, o2->name);
+  }
 }
 
 static int ilog2_exact(int n) {
@@ -315,6 +369,7 @@ static int ilog2_exact(int n) {
   if ((1 << l) != n) fail("fft size %d is not a power of two", n);
   return l;
 }
+constexpr int kGridY = 65535;                                         // a grid's y extent: a launch takes that many utterances or pairs
 
 static int frame_count(int fs, int x_length, double frame_period) {   // harvest.cpp:1219, dio.cpp:639
   return static_cast<int>(1000.0 * x_length / fs / frame_period) + 1;
@@ -335,6 +390,17 @@ static int max_frame_count(const int *n_frames, int n_utt, int f_stride) {
     max_frames = std::max(max_frames, n_frames[u]);
   }
   return max_frames;
+}
+// the first record of every utterance: utterance u's n_frames[u] records follow those of u - 1, from first_row on
+static std::vector<int> record_rows(const int *n_frames, int n_utt, long long first_row) {
+  std::vector<int> rows(n_utt);
+  long long row = first_row;
+  for (int u = 0; u < n_utt; ++u) {
+    if (row + n_frames[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
+    rows[u] = static_cast<int>(row);
+    row += n_frames[u];
+  }
+  return rows;
 }
 static BatchView batch_view(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
                             const int *n_frames, int f_stride) {
@@ -390,6 +456,33 @@ template <class Carve> static void begin_stage(WorldHipContext *c, Carve carve) 
   arena_reset(c);
   carve(c->arena);
   open_uploads(c);
+}
+// Arrays that outlive the stages of one call: `carve` takes them at the bottom of the arena, where they are held
+// (Arena::floor) while `body` runs stages that carve above them.  A stage that needs a larger arena than the one held
+// cannot grow it under those arrays (ArenaRegrow): the arena is grown with the floor released and carve and body start over
+// (the first call of a shape only; the stages then fit).  `what` names the call in the message.
+template <class Carve, class Body> static void hold_at_floor(WorldHipContext *c, const char *what, Carve carve, Body body) {
+  struct Release {                                          // the floor never outlives the call, whatever happens in it
+    WorldHipContext *c;
+    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
+  } release{c};
+  size_t want = 0;
+  for (int attempt = 0;; ++attempt) {
+    c->arena.floor = 0;
+    ensure_arena(c, std::max(measure(carve), want));
+    arena_reset(c);
+    carve(c->arena);
+    c->arena.floor = c->arena.used;
+    try {
+      body();
+      return;
+    } catch (const ArenaRegrow &r) {
+      // growing frees the arena: not possible while the stream is being captured into a graph
+      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
+      if (attempt >= 4) fail("%s: the workspace did not settle", what);
+      want = std::max(want, r.bytes);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -465,6 +558,10 @@ static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c,
 // CheapTrick
 // ---------------------------------------------------------------------------
 static std::string shape_limit(int what, int fs, int fft_size);       // below: "Shape limits of the GPU path"
+static void refuse_shape_limit(int what, int fs, int fft_size) {      // a call's first check: before any upload or launch
+  const std::string lim = shape_limit(what, fs, fft_size);
+  if (!lim.empty()) fail("%s", lim.c_str());
+}
 static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride,
                                  const int *x_length, const int *n_frames, int f_stride, const double *d_tpos,
                                  const double *d_f0, const CheapTrickOption *opt, double *d_sp, const RowLayout &lay,
@@ -975,6 +1072,7 @@ static void interp1_tables(const std::vector<double> &x, const std::vector<doubl
   }
 }
 
+// (not a cached_table: this cache is unbounded and does not refuse a miss under capture, and stays so)
 static const CodecTables &codec_tables(WorldHipContext *c, int fs, int fft_size) {
   for (const CodecTables &t : c->codec_tables)
     if (t.fs == fs && t.fft_size == fft_size) return t;
@@ -1139,8 +1237,8 @@ static void synthesize_rows(WorldHipContext *c, int n_utt, int fs, double frame_
     p.np = a.take<int>(B);
     p.resp = a.take<double>(B * p.pulse_cap * p.resp_stride);
   });
-  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
-  p.y_len = upload(c, std::vector<int>(y_length, y_length + n_utt));
+  p.n_frames = upload(c, n_frames, n_utt);
+  p.y_len = upload(c, y_length, n_utt);
   p.first_row = upload(c, rows.first_row);
   p.dc_remover = c->d_dc_remover;
   p.noise = ensure_noise(c, (size_t)max_y + 8);
@@ -1155,8 +1253,7 @@ static void run_synthesis(WorldHipContext *c, int n_utt, int fs, double frame_pe
   if (fs <= 0 || frame_period <= 0) fail("fs and frame_period must be positive");
   if (!d_f0 || !d_sp || !d_ap || !d_y || !n_frames || !y_length) fail("null buffer");
   ilog2_exact(fft_size);
-  const std::string lim = shape_limit(8, fs, fft_size);                 // before any upload or launch
-  if (!lim.empty()) fail("%s", lim.c_str());
+  refuse_shape_limit(8, fs, fft_size);
   int max_y = 0;
   for (int u = 0; u < n_utt; ++u) {
     if (n_frames[u] < 2 || n_frames[u] > f_stride) fail("n_frames[%d]=%d outside [2, f_stride]", u, n_frames[u]);
@@ -1181,18 +1278,12 @@ static void run_pack(WorldHipContext *c, bool unpack, int n_utt, const int *n_fr
   if (!n_frames || !d_tpos || !d_f0 || !d_sp || !d_ap || !d_block) fail("null buffer");
   if (nb < 1 || first_row < 0) fail("bad record shape");
   const int max_frames = max_frame_count(n_frames, n_utt, f_stride);
-  std::vector<int> off(n_utt);
-  long long row = first_row;
-  for (int u = 0; u < n_utt; ++u) {
-    if (row + n_frames[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
-    off[u] = static_cast<int>(row);
-    row += n_frames[u];
-  }
+  const std::vector<int> off = record_rows(n_frames, n_utt, first_row);
   if (max_frames == 0) return;
   begin_stage(c, [](Arena &) {});
   PackArgs a;
   a.n_utt = n_utt; a.f_stride = f_stride; a.nb = nb;
-  a.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  a.n_frames = upload(c, n_frames, n_utt);
   a.row_offset = upload(c, off);
   a.tpos = d_tpos; a.f0 = d_f0; a.sp = d_sp; a.ap = d_ap; a.block = d_block;
   launch_pack_rows(a, max_frames, unpack, c->stream);
@@ -1250,16 +1341,13 @@ static void analyze_into_records(WorldHipContext *c, int n_utt, int fs, const do
   const int nb = copt->fft_size / 2 + 1;
   // the record width names the wire format: 2 + 2 nb doubles = f64 spectra, 2 + nb doubles = f32 spectra
   const int wire = code_ndim == 0 && cols == record_cols(copt->fft_size, 1) ? 1 : 0;
-  std::vector<int> nf(n_utt), rows(n_utt);
-  long long row = first_row;
+  std::vector<int> nf(n_utt);
   int f_stride = 1;
   for (int u = 0; u < n_utt; ++u) {
     nf[u] = frame_count(fs, x_length[u], hopt->frame_period);
-    if (row + nf[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
-    rows[u] = static_cast<int>(row);
-    row += nf[u];
     f_stride = std::max(f_stride, nf[u]);
   }
+  const std::vector<int> rows = record_rows(nf.data(), n_utt, first_row);
   // the time axis and F0 stay dense ([n_utt][f_stride]: what CheapTrick and D4C read); they outlive the stages' arenas
   const size_t fr = (size_t)n_utt * f_stride;
   if (c->pk_cap < 2 * fr) {
@@ -1326,9 +1414,8 @@ static void run_analyze_coded(WorldHipContext *c, int n_utt, int fs, const doubl
 // Synthesis straight from records (include/world_hip.h: world_hip_synthesis_records): the mirror image of analyze_packed /
 // analyze_coded.  wire 0: the f64 records are read in place through SynthParams' row addressing, nothing is staged.
 // wire 1 / 2: sy_stage_records (codec.hip) turns every record into dense f64 rows once -- F0 [rows], sp and ap [rows][nb],
-// the utterances back to back -- carved at the bottom of the arena and held there (Arena::floor) while the synthesis
-// stage carves above them; a stage that needs more arena than is held makes the call grow it and start over, as in
-// run_resynthesis.
+// the utterances back to back -- carved at the bottom of the arena and held there while the synthesis stage carves above
+// them (hold_at_floor).
 // ---------------------------------------------------------------------------
 static void run_synthesis_records(WorldHipContext *c, int n_utt, int fs, double frame_period, int fft_size,
                                   const int *n_frames, long long first_row, const double *d_block, int cols, int wire,
@@ -1339,8 +1426,7 @@ static void run_synthesis_records(WorldHipContext *c, int n_utt, int fs, double 
   if (!d_y || !n_frames || !y_length) fail("null buffer");
   if (first_row < 0) fail("synthesis_records: negative first_row");
   if (wire < 0 || wire > 2) fail("synthesis_records: wire %d (0: f64 records, 1: f32 records, 2: coded records)", wire);
-  const std::string lim = shape_limit(15, fs, fft_size);                // world_hip_check_shape's rule, before any GPU work
-  if (!lim.empty()) fail("%s", lim.c_str());
+  refuse_shape_limit(15, fs, fft_size);                                 // world_hip_check_shape's rule
   const int lg = ilog2_exact(fft_size), nb = fft_size / 2 + 1;
   int nap = 0;
   if (wire == 2) {                                                      // what the decoders refuse (run_codec)
@@ -1354,18 +1440,16 @@ static void run_synthesis_records(WorldHipContext *c, int n_utt, int fs, double 
   } else if (cols != record_cols(fft_size, wire)) {
     fail("synthesis_records: %d columns, wire %d at fft_size %d needs %d", cols, wire, fft_size, record_cols(fft_size, wire));
   }
-  std::vector<int> src(n_utt), dst(n_utt);
-  long long row = first_row, total = 0;
+  long long total = 0;
   int max_y = 0, max_frames = 0;
   for (int u = 0; u < n_utt; ++u) {
     if (n_frames[u] < 2) fail("n_frames[%d]=%d: synthesis needs 2 frames", u, n_frames[u]);
     if (y_length[u] < 1 || y_length[u] > y_stride) fail("y_length[%d]=%d outside [1, y_stride]", u, y_length[u]);
-    if (row + n_frames[u] > 0x7FFFFFFFll) fail("block exceeds 2^31 records");
-    src[u] = static_cast<int>(row); dst[u] = static_cast<int>(total);
-    row += n_frames[u]; total += n_frames[u];
+    total += n_frames[u];
     max_y = std::max(max_y, y_length[u]);
     max_frames = std::max(max_frames, n_frames[u]);
   }
+  const std::vector<int> src = record_rows(n_frames, n_utt, first_row), dst = record_rows(n_frames, n_utt, 0);
   SynthRows rows;
   if (wire == 0) {                                                      // [tpos, f0, sp[nb], ap[nb]] in place
     rows.f0 = d_block + 1; rows.sp = d_block + 2; rows.ap = d_block + 2 + nb;
@@ -1381,38 +1465,21 @@ static void run_synthesis_records(WorldHipContext *c, int n_utt, int fs, double 
     sp.f0 = a.take<double>((size_t)total);
     sp.sp = a.take<double>((size_t)total * nb); sp.ap = a.take<double>((size_t)total * nb);
   };
-  struct Release {                                          // the floor never outlives the call, whatever happens in it
-    WorldHipContext *c;
-    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
-  } release{c};
-  size_t want = 0;
-  for (int attempt = 0;; ++attempt) {
-    c->arena.floor = 0;
-    ensure_arena(c, std::max(measure(carve), want));
-    arena_reset(c);
-    carve(c->arena);
-    c->arena.floor = c->arena.used;
-    try {
-      open_uploads(c);
-      if (wire == 2) {
-        const CodecTables &t = codec_tables(c, fs, fft_size);
-        sp.knot_sp = t.d_knot_dec; sp.frac_sp = t.d_frac_dec; sp.w_re = t.d_wd_re; sp.w_im = t.d_wd_im;
-        sp.knot_ap = t.d_knot_ap; sp.frac_ap = t.d_frac_ap;
-      }
-      sp.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
-      sp.src_row = upload(c, src); sp.dst_row = upload(c, dst);
-      sp.tab = c->tab;
-      launch_stage_records(sp, max_frames, c->stream);
-      rows.f0 = sp.f0; rows.sp = sp.sp; rows.ap = sp.ap;
-      rows.first_row.assign(dst.begin(), dst.end()); rows.row_stride = (size_t)nb; rows.f0_stride = 1;
-      synthesize_rows(c, n_utt, fs, frame_period, fft_size, n_frames, rows, y_length, y_stride, max_y, d_y);
-      return;
-    } catch (const ArenaRegrow &r) {
-      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
-      if (attempt >= 4) fail("synthesis_records: the workspace did not settle");
-      want = std::max(want, r.bytes);
+  hold_at_floor(c, "synthesis_records", carve, [&] {
+    open_uploads(c);
+    if (wire == 2) {
+      const CodecTables &t = codec_tables(c, fs, fft_size);
+      sp.knot_sp = t.d_knot_dec; sp.frac_sp = t.d_frac_dec; sp.w_re = t.d_wd_re; sp.w_im = t.d_wd_im;
+      sp.knot_ap = t.d_knot_ap; sp.frac_ap = t.d_frac_ap;
     }
-  }
+    sp.n_frames = upload(c, n_frames, n_utt);
+    sp.src_row = upload(c, src); sp.dst_row = upload(c, dst);
+    sp.tab = c->tab;
+    launch_stage_records(sp, max_frames, c->stream);
+    rows.f0 = sp.f0; rows.sp = sp.sp; rows.ap = sp.ap;
+    rows.first_row.assign(dst.begin(), dst.end()); rows.row_stride = (size_t)nb; rows.f0_stride = 1;
+    synthesize_rows(c, n_utt, fs, frame_period, fft_size, n_frames, rows, y_length, y_stride, max_y, d_y);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1584,7 +1651,7 @@ static void run_modify(WorldHipContext *c, int n_utt, int fs, int fft_size, cons
   open_uploads(c);                                          // (the stage uses no workspace: prepared offsets stay valid)
   ModifyParams p;
   p.n_utt = n_utt; p.f_stride = f_stride; p.fs = fs; p.fft_size = fft_size;
-  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.n_frames = upload(c, n_frames, n_utt);
   p.ratio = upload(c, ratio); p.sp_in = d_sp_in; p.sp_out = d_sp_out;
   p.f0_scale = upload(c, scale); p.convert = upload(c, convert); p.target = upload(c, target);
   p.f0_in = d_f0_in; p.f0_out = d_f0_out; p.stats = nullptr;
@@ -1600,7 +1667,7 @@ static void run_f0_statistics(WorldHipContext *c, int n_utt, const int *n_frames
   open_uploads(c);
   ModifyParams p;
   p.n_utt = n_utt; p.f_stride = f_stride; p.fs = 0; p.fft_size = 0;
-  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.n_frames = upload(c, n_frames, n_utt);
   p.ratio = nullptr; p.sp_in = nullptr; p.sp_out = nullptr;
   p.convert = upload(c, std::vector<int>(n_utt, 0));
   p.f0_scale = nullptr; p.target = nullptr;
@@ -1612,24 +1679,27 @@ static int resynthesis_length(int fs, int n_frames, double frame_period, double 
   return static_cast<int>((n_frames - 1) * frame_period * time_scale / 1000.0 * fs) + 1;
 }
 
-// Harvest -> CheapTrick + D4C -> modification -> Synthesis at frame_period * time_scale.  tpos, f0, sp and ap are carved at
-// the bottom of the arena and held there (Arena::floor) while the stages carve above them.  A stage that needs a larger
-// arena than the one held cannot grow it under those arrays: the call grows it with the floor released and starts over
-// (the first call of a shape only; the stages then fit).
-static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
-                            const HarvestOption *hopt, const CheapTrickOption *copt, const D4COption *dopt,
-                            const WorldHipModification *mods, double time_scale, const int *y_length, int y_stride,
-                            double *d_y) {
+// what the resynthesis calls refuse first: the batch, a null option, a HarvestOption no analysis could run with
+static void check_analysis_input(int n_utt, int fs, const void *d_x, int x_stride, const int *x_length, const HarvestOption *hopt,
+                                 const CheapTrickOption *copt, const D4COption *dopt) {
   check_batch(n_utt, fs, d_x, x_stride, x_length);
   if (!hopt || !copt || !dopt) fail("null option");
   if (!(hopt->f0_floor > 0) || !(hopt->f0_ceil > hopt->f0_floor) || !(hopt->frame_period > 0) ||
       !std::isfinite(hopt->frame_period) || !std::isfinite(hopt->f0_ceil))
     fail("bad HarvestOption");
+}
+
+// Harvest -> CheapTrick + D4C -> modification -> Synthesis at frame_period * time_scale.  tpos, f0, sp and ap are carved at
+// the bottom of the arena and held there while the stages carve above them (hold_at_floor).
+static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride, const int *x_length,
+                            const HarvestOption *hopt, const CheapTrickOption *copt, const D4COption *dopt,
+                            const WorldHipModification *mods, double time_scale, const int *y_length, int y_stride,
+                            double *d_y) {
+  check_analysis_input(n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt);
   if (!std::isfinite(time_scale) || !(time_scale > 0.0)) fail("resynthesize: time_scale %g must be finite and > 0", time_scale);
   if (!y_length || !d_y) fail("null buffer");
   const int fft_size = copt->fft_size;
-  const std::string lim = shape_limit(14, fs, fft_size);
-  if (!lim.empty()) fail("%s", lim.c_str());
+  refuse_shape_limit(14, fs, fft_size);
   check_modifications(mods, n_utt, fft_size);
   std::vector<int> nf(n_utt);
   int f_stride = 1;
@@ -1645,29 +1715,12 @@ static void run_resynthesis(WorldHipContext *c, int n_utt, int fs, const double 
     tpos = a.take<double>(fr); f0 = a.take<double>(fr);
     sp = a.take<double>(fr * nb); ap = a.take<double>(fr * nb);
   };
-  struct Release {                                          // the floor never outlives the call, whatever happens in it
-    WorldHipContext *c;
-    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
-  } release{c};
-  size_t want = 0;
-  for (int attempt = 0;; ++attempt) {
-    c->arena.floor = 0;
-    ensure_arena(c, std::max(measure(carve), want));
-    arena_reset(c);
-    carve(c->arena);
-    c->arena.floor = c->arena.used;
-    try {
-      run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
-      run_modify(c, n_utt, fs, fft_size, nf.data(), f_stride, mods, f0, f0, sp, sp);
-      run_synthesis(c, n_utt, fs, hopt->frame_period * time_scale, fft_size, nf.data(), f_stride, f0, sp, ap, y_length,
-                    y_stride, d_y);
-      return;
-    } catch (const ArenaRegrow &r) {
-      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
-      if (attempt >= 4) fail("resynthesize: the workspace did not settle");
-      want = std::max(want, r.bytes);
-    }
-  }
+  hold_at_floor(c, "resynthesize", carve, [&] {
+    run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
+    run_modify(c, n_utt, fs, fft_size, nf.data(), f_stride, mods, f0, f0, sp, sp);
+    run_synthesis(c, n_utt, fs, hopt->frame_period * time_scale, fft_size, nf.data(), f_stride, f0, sp, ap, y_length, y_stride,
+                  d_y);
+  });
 }
 
 // Frame-wise modification behind a time map (include/world_hip.h: world_hip_modify_frames_batch; codec.hip's
@@ -1721,12 +1774,12 @@ static void run_modify_frames(WorldHipContext *c, int n_utt, int fs, int fft_siz
     open_uploads(c);                                        // (no workspace: prepared offsets stay valid)
   ModifyFramesParams p;
   p.m.n_utt = n_utt; p.m.f_stride = f_stride; p.m.fs = fs; p.m.fft_size = fft_size;
-  p.m.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
+  p.m.n_frames = upload(c, n_frames, n_utt);
   p.m.ratio = upload(c, ratio); p.m.sp_in = d_sp_in; p.m.sp_out = d_sp_out;
   p.m.f0_scale = upload(c, scale); p.m.convert = upload(c, convert); p.m.target = upload(c, target);
   p.m.f0_in = d_f0_in; p.m.f0_out = d_f0_out; p.m.stats = nullptr;
   p.o_stride = o_stride;
-  p.n_out = upload(c, std::vector<int>(n_out, n_out + n_utt));
+  p.n_out = upload(c, n_out, n_utt);
   p.time_map = cv.d_time_map; p.f0_target = cv.d_f0_target; p.f0_scale = cv.d_f0_scale;
   p.formant_shift = cv.d_formant_shift; p.ap_gain = cv.d_ap_gain;
   p.ap_in = d_ap_in; p.ap_out = d_ap_out;
@@ -1748,15 +1801,10 @@ static void run_resynthesis_frames(WorldHipContext *c, int n_utt, int fs, const 
                                    const HarvestOption *hopt, const CheapTrickOption *copt, const D4COption *dopt,
                                    const WorldHipModification *mods, const WorldHipFrameCurves *curves, const int *n_out,
                                    int o_stride, const int *y_length, int y_stride, double *d_y) {
-  check_batch(n_utt, fs, d_x, x_stride, x_length);
-  if (!hopt || !copt || !dopt) fail("null option");
-  if (!(hopt->f0_floor > 0) || !(hopt->f0_ceil > hopt->f0_floor) || !(hopt->frame_period > 0) ||
-      !std::isfinite(hopt->frame_period) || !std::isfinite(hopt->f0_ceil))
-    fail("bad HarvestOption");
+  check_analysis_input(n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt);
   if (!n_out || !y_length || !d_y) fail("null buffer");
   const int fft_size = copt->fft_size;
-  const std::string lim = shape_limit(14, fs, fft_size);
-  if (!lim.empty()) fail("%s", lim.c_str());
+  refuse_shape_limit(14, fs, fft_size);
   check_modifications(mods, n_utt, fft_size);
   const bool mapped = curves && curves->d_time_map;
   std::vector<int> nf(n_utt);
@@ -1778,28 +1826,11 @@ static void run_resynthesis_frames(WorldHipContext *c, int n_utt, int fs, const 
     sp = a.take<double>(fr * nb); ap = a.take<double>(fr * nb);
     f0m = a.take<double>(fo); spm = a.take<double>(fo * nb); apm = a.take<double>(fo * nb);
   };
-  struct Release {                                          // the floor never outlives the call, whatever happens in it
-    WorldHipContext *c;
-    ~Release() { c->arena.floor = 0; c->prep_ct.valid = c->prep_d4c.valid = false; }
-  } release{c};
-  size_t want = 0;
-  for (int attempt = 0;; ++attempt) {
-    c->arena.floor = 0;
-    ensure_arena(c, std::max(measure(carve), want));
-    arena_reset(c);
-    carve(c->arena);
-    c->arena.floor = c->arena.used;
-    try {
-      run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
-      run_modify_frames(c, n_utt, fs, fft_size, nf.data(), f_stride, n_out, o_stride, mods, curves, f0, f0m, sp, spm, ap, apm);
-      run_synthesis(c, n_utt, fs, hopt->frame_period, fft_size, n_out, o_stride, f0m, spm, apm, y_length, y_stride, d_y);
-      return;
-    } catch (const ArenaRegrow &r) {
-      if (devrt::is_capturing(c->stream)) fail("a call shape that was never run before cannot be captured: run it once first");
-      if (attempt >= 4) fail("resynthesize_frames: the workspace did not settle");
-      want = std::max(want, r.bytes);
-    }
-  }
+  hold_at_floor(c, "resynthesize_frames", carve, [&] {
+    run_analyze_dense(c, n_utt, fs, d_x, x_stride, x_length, hopt, copt, dopt, f_stride, tpos, f0, sp, ap);
+    run_modify_frames(c, n_utt, fs, fft_size, nf.data(), f_stride, n_out, o_stride, mods, curves, f0, f0m, sp, spm, ap, apm);
+    run_synthesis(c, n_utt, fs, hopt->frame_period, fft_size, n_out, o_stride, f0m, spm, apm, y_length, y_stride, d_y);
+  });
 }
 
 // Alignment of pairs of frame rows by dynamic time warping (include/world_hip.h: world_hip_align_batch; align.inc).
@@ -1851,10 +1882,10 @@ static void run_align(WorldHipContext *c, int n_pairs, int n_dims, const double 
   });
   p.n_dims = n_dims;
   p.a = d_a; p.b = d_b; p.a_stride = a_row_stride; p.b_stride = b_row_stride;
-  p.a_row = upload(c, std::vector<long long>(a_row, a_row + n_pairs));
-  p.b_row = upload(c, std::vector<long long>(b_row, b_row + n_pairs));
-  p.n_a = upload(c, std::vector<int>(n_a, n_a + n_pairs));
-  p.n_b = upload(c, std::vector<int>(n_b, n_b + n_pairs));
+  p.a_row = upload(c, a_row, n_pairs);
+  p.b_row = upload(c, b_row, n_pairs);
+  p.n_a = upload(c, n_a, n_pairs);
+  p.n_b = upload(c, n_b, n_pairs);
   p.cell0 = upload(c, cell0);
   p.mcd_scale = 10.0 / log(10.0) * sqrt(2.0);
   p.path = d_path; p.p_stride = p_stride; p.path_len = d_path_len; p.summary = d_summary;
@@ -1887,7 +1918,7 @@ static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, con
                       const double *d_sp_b, const double *d_ap_b, int p_stride, const int *d_path, const int *d_path_len,
                       const WorldHipMorph *morphs, const WorldHipMorphCurves *curves, int o_stride, double *d_f0_out,
                       double *d_sp_out, double *d_ap_out, double *d_pos_a, double *d_pos_b) {
-  if (n_pairs < 1 || n_pairs > 65535) fail("morph: n_pairs %d outside [1, 65535]", n_pairs);
+  if (n_pairs < 1 || n_pairs > kGridY) fail("morph: n_pairs %d outside [1, %d]", n_pairs, kGridY);
   if (!n_a || !n_b || !morphs) fail("morph: null n_a / n_b / morphs");
   if ((!d_f0_a != !d_f0_b) || (!d_f0_a != !d_f0_out)) fail("morph: give d_f0_a, d_f0_b and d_f0_out, or none of them");
   if ((!d_sp_a != !d_sp_b) || (!d_sp_a != !d_sp_out)) fail("morph: give d_sp_a, d_sp_b and d_sp_out, or none of them");
@@ -1895,9 +1926,7 @@ static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, con
   const bool with_f0 = d_f0_a != nullptr, with_sp = d_sp_a != nullptr, with_ap = d_ap_a != nullptr;
   if (with_sp || with_ap) {
     if (fs <= 0) fail("morph: fs must be positive");
-    int lg = 0;
-    while ((1 << lg) < fft_size) ++lg;
-    if (fft_size < 128 || fft_size > 8192 || (1 << lg) != fft_size)
+    if (fft_size < 128 || fft_size > 8192 || (fft_size & (fft_size - 1)) != 0)
       fail("morph: fft_size %d is not a power of two in [128, 8192]", fft_size);
   }
   if (d_path && !d_path_len) fail("morph: a path needs d_path_len (null)");
@@ -1921,32 +1950,18 @@ static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, con
     if (n_out[u] > o_stride) fail("morph: o_stride %d below pair %d's %d output frames", o_stride, u, n_out[u]);
     max_out = std::max(max_out, n_out[u]);
   }
-  // no output may overlap an input or another output: byte ranges of everything the call touches
   const WorldHipMorphCurves none = {nullptr, nullptr, nullptr};
   const WorldHipMorphCurves &cv = curves ? *curves : none;
   {
-    struct Range { const char *lo, *hi; const char *name; };
-    const size_t nbins = (size_t)(fft_size / 2 + 1) * sizeof(double), P = (size_t)n_pairs;
-    auto range = [](const void *p, size_t bytes, const char *name) {
-      return Range{static_cast<const char *>(p), static_cast<const char *>(p) + bytes, name};
-    };
-    std::vector<Range> in, out;
-    auto add = [&](std::vector<Range> &v, const void *p, size_t bytes, const char *name) { if (p) v.push_back(range(p, bytes, name)); };
-    add(in, d_f0_a, P * a_stride * sizeof(double), "d_f0_a"); add(in, d_f0_b, P * b_stride * sizeof(double), "d_f0_b");
-    add(in, d_sp_a, P * a_stride * nbins, "d_sp_a"); add(in, d_sp_b, P * b_stride * nbins, "d_sp_b");
-    add(in, d_ap_a, P * a_stride * nbins, "d_ap_a"); add(in, d_ap_b, P * b_stride * nbins, "d_ap_b");
-    add(in, d_path, P * p_stride * 2 * sizeof(int), "d_path"); add(in, d_path_len, P * sizeof(int), "d_path_len");
-    add(in, cv.d_f0_rate, P * o_stride * sizeof(double), "d_f0_rate"); add(in, cv.d_sp_rate, P * o_stride * sizeof(double), "d_sp_rate");
-    add(in, cv.d_ap_rate, P * o_stride * sizeof(double), "d_ap_rate");
-    add(out, d_f0_out, P * o_stride * sizeof(double), "d_f0_out"); add(out, d_sp_out, P * o_stride * nbins, "d_sp_out");
-    add(out, d_ap_out, P * o_stride * nbins, "d_ap_out");
-    add(out, d_pos_a, P * o_stride * sizeof(double), "d_pos_a"); add(out, d_pos_b, P * o_stride * sizeof(double), "d_pos_b");
-    for (size_t x = 0; x < out.size(); ++x) {
-      for (const Range &r : in)
-        if (out[x].lo < r.hi && r.lo < out[x].hi) fail("morph: %s overlaps %s; no output may alias an input", out[x].name, r.name);
-      for (size_t y = x + 1; y < out.size(); ++y)
-        if (out[x].lo < out[y].hi && out[y].lo < out[x].hi) fail("morph: %s overlaps %s", out[x].name, out[y].name);
-    }
+    const size_t f0 = (size_t)n_pairs * sizeof(double), bins = f0 * (fft_size / 2 + 1);   // bytes per frame of all pairs
+    refuse_overlap("morph",
+                   {{d_f0_out, f0 * o_stride, "d_f0_out"}, {d_sp_out, bins * o_stride, "d_sp_out"}, {d_ap_out, bins * o_stride, "d_ap_out"},
+                    {d_pos_a, f0 * o_stride, "d_pos_a"}, {d_pos_b, f0 * o_stride, "d_pos_b"}},
+                   {{d_f0_a, f0 * a_stride, "d_f0_a"}, {d_f0_b, f0 * b_stride, "d_f0_b"}, {d_sp_a, bins * a_stride, "d_sp_a"},
+                    {d_sp_b, bins * b_stride, "d_sp_b"}, {d_ap_a, bins * a_stride, "d_ap_a"}, {d_ap_b, bins * b_stride, "d_ap_b"},
+                    {d_path, (size_t)n_pairs * p_stride * 2 * sizeof(int), "d_path"}, {d_path_len, (size_t)n_pairs * sizeof(int), "d_path_len"},
+                    {cv.d_f0_rate, f0 * o_stride, "d_f0_rate"}, {cv.d_sp_rate, f0 * o_stride, "d_sp_rate"},
+                    {cv.d_ap_rate, f0 * o_stride, "d_ap_rate"}});
   }
   if (!with_f0 && !with_sp && !with_ap && !d_pos_a && !d_pos_b) return;
   MorphParams p;
@@ -1960,8 +1975,8 @@ static void run_morph(WorldHipContext *c, int n_pairs, int fs, int fft_size, con
     open_uploads(c);                                        // (no workspace: prepared offsets stay valid)
   p.n_pairs = n_pairs; p.fft_size = fft_size;
   p.a_stride = a_stride; p.b_stride = b_stride; p.o_stride = o_stride; p.p_stride = p_stride;
-  p.n_a = upload(c, std::vector<int>(n_a, n_a + n_pairs));
-  p.n_b = upload(c, std::vector<int>(n_b, n_b + n_pairs));
+  p.n_a = upload(c, n_a, n_pairs);
+  p.n_b = upload(c, n_b, n_pairs);
   p.n_out = upload(c, n_out);
   p.rate = upload(c, rate);
   p.path = d_path; p.path_len = d_path_len;
@@ -1982,40 +1997,28 @@ static ResampleDesign resample_design(const WorldHipResampleOption *opt) {
   return ResampleDesign{opt->zeros, opt->rolloff, opt->kaiser_beta};
 }
 constexpr size_t kResampleTablesKept = 4;        // a mixed-rate tool run alternates between a few ratios
+void ResampleTable::put(WorldHipContext *c, const Host &h) { put_table(c, d_coef, h.coef); put_table(c, d_kdiv, h.kdiv); }
+void ResampleTable::drop(WorldHipContext *c) { drop_table(c, d_coef); drop_table(c, d_kdiv); }
 static const ResampleTable &resample_table(WorldHipContext *c, const ResampleShape &sh, const ResampleDesign &d) {
-  ++c->resample_calls;
-  for (ResampleTable &t : c->resample_tables)
-    if (t.L == sh.L && t.M == sh.M && t.W == sh.W && t.design.zeros == d.zeros && t.design.rolloff == d.rolloff &&
-        t.design.beta == d.beta) {
-      t.used = c->resample_calls;
-      return t;
-    }
-  // a miss allocates and uploads: neither is possible while the stream is being captured into a graph
-  if (devrt::is_capturing(c->stream)) fail("resample: a ratio that was never run before cannot be captured: run it once first");
-  const size_t taps = 2 * (size_t)sh.W, L = (size_t)sh.L;
-  std::vector<double> host(L * taps), dev(L * taps);
-  std::vector<int> kdiv(L);
-  build_resample_taps(sh, d, host.data());
-  for (size_t r = 0; r < L; ++r) {
-    const size_t p = (size_t)(((long long)r * sh.M) % sh.L);
-    kdiv[r] = (int)(((long long)r * sh.M) / sh.L);
-    for (size_t i = 0; i < taps; ++i) dev[i * L + r] = host[p * taps + i];
-  }
-  devrt::sync(c->stream);                        // (a kernel may still read the table that goes)
-  if (c->resample_tables.size() >= kResampleTablesKept) {
-    auto oldest = std::min_element(c->resample_tables.begin(), c->resample_tables.end(),
-                                   [](const ResampleTable &a, const ResampleTable &b) { return a.used < b.used; });
-    drop_table(c, oldest->d_coef);
-    drop_table(c, oldest->d_kdiv);
-    c->resample_tables.erase(oldest);
-  }
-  ResampleTable t;
-  t.L = sh.L; t.M = sh.M; t.W = sh.W; t.design = d; t.used = c->resample_calls;
-  put_table(c, t.d_coef, dev);
-  put_table(c, t.d_kdiv, kdiv);
-  devrt::sync(c->stream);                        // (the host copies go out of scope)
-  c->resample_tables.push_back(t);
-  return c->resample_tables.back();
+  return cached_table(
+      c, c->resample_tables, kResampleTablesKept, "resample: a ratio that was never run before cannot be captured: run it once first",
+      [&](const ResampleTable &t) {
+        return t.L == sh.L && t.M == sh.M && t.W == sh.W && t.design.zeros == d.zeros && t.design.rolloff == d.rolloff &&
+               t.design.beta == d.beta;
+      },
+      [&](ResampleTable &t) {
+        t.L = sh.L; t.M = sh.M; t.W = sh.W; t.design = d;
+        const size_t taps = 2 * (size_t)sh.W, L = (size_t)sh.L;
+        std::vector<double> host(L * taps);
+        ResampleTable::Host dev{std::vector<double>(L * taps), std::vector<int>(L)};
+        build_resample_taps(sh, d, host.data());
+        for (size_t r = 0; r < L; ++r) {
+          const size_t p = (size_t)(((long long)r * sh.M) % sh.L);
+          dev.kdiv[r] = (int)(((long long)r * sh.M) / sh.L);
+          for (size_t i = 0; i < taps; ++i) dev.coef[i * L + r] = host[p * taps + i];
+        }
+        return dev;
+      });
 }
 
 static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, const WorldHipResampleOption *opt,
@@ -2036,11 +2039,8 @@ static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, c
     max_out = std::max(max_out, n_out[u]);
     max_in = std::max(max_in, x_length[u]);
   }
-  {
-    const char *x_lo = reinterpret_cast<const char *>(d_x), *x_hi = x_lo + sizeof(double) * (size_t)n_utt * x_stride;
-    const char *y_lo = reinterpret_cast<const char *>(d_y), *y_hi = y_lo + sizeof(double) * (size_t)n_utt * y_stride;
-    if (y_lo < x_hi && x_lo < y_hi) fail("resample: d_y overlaps d_x; the output may not alias the input");
-  }
+  refuse_overlap("resample", {{d_y, sizeof(double) * (size_t)n_utt * y_stride, "d_y"}},
+                 {{d_x, sizeof(double) * (size_t)n_utt * x_stride, "d_x"}});
   open_uploads(c);                                          // (no workspace: prepared offsets stay valid)
   ResampleParams p;
   p.L = (int)sh.L; p.M = (int)sh.M; p.W = (int)sh.W;
@@ -2055,9 +2055,9 @@ static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, c
     plan = resample_plan(sh.L, sh.M, sh.W);
     p.tile = plan.tile; p.span = plan.span;
   }
-  const int *d_len = upload(c, std::vector<int>(x_length, x_length + n_utt)), *d_out = upload(c, n_out);
-  for (int u0 = 0; u0 < n_utt; u0 += 65535) {               // (a grid's y extent)
-    const int n = std::min(65535, n_utt - u0);
+  const int *d_len = upload(c, x_length, n_utt), *d_out = upload(c, n_out);
+  for (int u0 = 0; u0 < n_utt; u0 += kGridY) {
+    const int n = std::min(kGridY, n_utt - u0);
     p.x = d_x + (size_t)u0 * x_stride; p.y = d_y + (size_t)u0 * y_stride;
     p.x_len = d_len + u0; p.n_out = d_out + u0;
     if (copy) launch_resample_copy(p, max_in, n, c->stream);
@@ -2069,42 +2069,30 @@ static void run_resample(WorldHipContext *c, int n_utt, int fs_in, int fs_out, c
 // refusals of a shape, the tables -- is tables.cpp's; here a direction's table is put on the device once per
 // (fft_size, order, alpha) and found again.
 constexpr size_t kMcepTablesKept = 4;            // both directions of two shapes
+void McepTable::put(WorldHipContext *c, const Host &h) { put_table(c, d_table, h); }
+void McepTable::drop(WorldHipContext *c) { drop_table(c, d_table); }
 static const McepTable &mcep_table(WorldHipContext *c, bool decode, int fft_size, int order, double alpha) {
   unsigned long long bits;
   memcpy(&bits, &alpha, sizeof bits);
-  ++c->mcep_calls;
-  for (McepTable &t : c->mcep_tables)
-    if (t.decode == decode && t.fft_size == fft_size && t.order == order && t.alpha_bits == bits) {
-      t.used = c->mcep_calls;
-      return t;
-    }
-  // a miss allocates and uploads: neither is possible while the stream is being captured into a graph
-  if (devrt::is_capturing(c->stream)) fail("mcep: a (fft_size, order, alpha) that was never run before cannot be captured: run it once first");
-  const size_t K = (size_t)fft_size / 2 + 1, P = (size_t)order + 1;
-  McepTable t;
-  t.fft_size = fft_size; t.order = order; t.alpha_bits = bits; t.decode = decode; t.used = c->mcep_calls;
-  mcep_table_shape(decode, fft_size, order, &t.k_pad, &t.n_pad);
-  std::vector<double> host(K * P), dev((size_t)t.k_pad * t.n_pad, 0.0);
-  if (decode) {                                  // D [K][P] -> [m][k]
-    build_mcep_decode(fft_size, order, alpha, host.data());
-    for (size_t k = 0; k < K; ++k)
-      for (size_t m = 0; m < P; ++m) dev[m * t.n_pad + k] = host[k * P + m];
-  } else {                                       // M [P][K] -> [k][m]
-    build_mcep_encode(fft_size, order, alpha, host.data());
-    for (size_t m = 0; m < P; ++m)
-      for (size_t k = 0; k < K; ++k) dev[k * t.n_pad + m] = host[m * K + k];
-  }
-  devrt::sync(c->stream);                        // (a kernel may still read the table that goes)
-  if (c->mcep_tables.size() >= kMcepTablesKept) {
-    auto oldest = std::min_element(c->mcep_tables.begin(), c->mcep_tables.end(),
-                                   [](const McepTable &a, const McepTable &b) { return a.used < b.used; });
-    drop_table(c, oldest->d_table);
-    c->mcep_tables.erase(oldest);
-  }
-  put_table(c, t.d_table, dev);
-  devrt::sync(c->stream);                        // (the host copy goes out of scope)
-  c->mcep_tables.push_back(t);
-  return c->mcep_tables.back();
+  return cached_table(
+      c, c->mcep_tables, kMcepTablesKept, "mcep: a (fft_size, order, alpha) that was never run before cannot be captured: run it once first",
+      [&](const McepTable &t) { return t.decode == decode && t.fft_size == fft_size && t.order == order && t.alpha_bits == bits; },
+      [&](McepTable &t) {
+        t.fft_size = fft_size; t.order = order; t.alpha_bits = bits; t.decode = decode;
+        mcep_table_shape(decode, fft_size, order, &t.k_pad, &t.n_pad);
+        const size_t K = (size_t)fft_size / 2 + 1, P = (size_t)order + 1;
+        std::vector<double> host(K * P), dev((size_t)t.k_pad * t.n_pad, 0.0);
+        if (decode) {                            // D [K][P] -> [m][k]
+          build_mcep_decode(fft_size, order, alpha, host.data());
+          for (size_t k = 0; k < K; ++k)
+            for (size_t m = 0; m < P; ++m) dev[m * t.n_pad + k] = host[k * P + m];
+        } else {                                 // M [P][K] -> [k][m]
+          build_mcep_encode(fft_size, order, alpha, host.data());
+          for (size_t m = 0; m < P; ++m)
+            for (size_t k = 0; k < K; ++k) dev[k * t.n_pad + m] = host[m * K + k];
+        }
+        return dev;
+      });
 }
 
 static void run_mcep(WorldHipContext *c, bool decode, int rows, int fft_size, int order, double alpha, const double *d_in,
@@ -2118,11 +2106,8 @@ static void run_mcep(WorldHipContext *c, bool decode, int rows, int fft_size, in
     fail("%s: %s %lld below the row's %lld doubles", name, decode ? "mc_row_stride" : "sp_row_stride", in_stride, in_cols);
   if (out_stride < out_cols)
     fail("%s: %s %lld below the row's %lld doubles", name, decode ? "sp_row_stride" : "mc_row_stride", out_stride, out_cols);
-  {
-    const char *i_lo = reinterpret_cast<const char *>(d_in), *i_hi = i_lo + sizeof(double) * (size_t)((rows - 1) * in_stride + in_cols);
-    const char *o_lo = reinterpret_cast<const char *>(d_out), *o_hi = o_lo + sizeof(double) * (size_t)((rows - 1) * out_stride + out_cols);
-    if (o_lo < i_hi && i_lo < o_hi) fail("%s: the output range overlaps the input range; the output may not alias the input", name);
-  }
+  refuse_overlap(name, {{d_out, sizeof(double) * (size_t)((rows - 1) * out_stride + out_cols), decode ? "d_sp" : "d_mc"}},
+                 {{d_in, sizeof(double) * (size_t)((rows - 1) * in_stride + in_cols), decode ? "d_mc" : "d_sp"}});
   const McepTable &t = mcep_table(c, decode, fft_size, order, alpha);
   McepParams p;
   p.in = d_in; p.out = d_out; p.table = t.d_table;
@@ -2176,16 +2161,9 @@ static void run_mlpg_or_delta(WorldHipContext *c, bool generate, int n_utt, int 
     out_span = std::max(out_span, u * out_us + rows * out_rs + out_cols);
     mask_span = std::max(mask_span, u * mask_us + rows + 1);
   }
-  {
-    const char *o_lo = reinterpret_cast<const char *>(d_out), *o_hi = o_lo + sizeof(double) * (size_t)out_span;
-    auto overlaps = [&](const void *q, size_t bytes) {
-      const char *lo = static_cast<const char *>(q);
-      return q && o_lo < lo + bytes && lo < o_hi;
-    };
-    if (overlaps(d_in, sizeof(double) * (size_t)in_span) || (generate && overlaps(d_var, sizeof(double) * (size_t)var_span)) ||
-        overlaps(d_mask, (size_t)mask_span))
-      fail("%s: the output range overlaps an input range; the output may not alias an input", name);
-  }
+  refuse_overlap(name, {{d_out, sizeof(double) * (size_t)out_span, "d_out"}},
+                 {{d_in, sizeof(double) * (size_t)in_span, generate ? "d_mean" : "d_c"},
+                  {d_var, sizeof(double) * (size_t)var_span, "d_var"}, {d_mask, (size_t)mask_span, "d_mask"}});   // (delta: no d_var)
   MlpgParams p;
   p.ws = nullptr;
   if (generate && half_width > 0)
@@ -2202,9 +2180,9 @@ static void run_mlpg_or_delta(WorldHipContext *c, bool generate, int n_utt, int 
       const int tau = k - 2;
       p.win[w][k] = w < n_win && tau >= -half_width && tau <= half_width ? win[w * taps + tau + half_width] : 0.0;
     }
-  p.n_frames = upload(c, std::vector<int>(n_frames, n_frames + n_utt));
-  for (int u0 = 0; u0 < n_utt; u0 += 65535) {               // (a grid's y extent)
-    const int n = std::min(65535, n_utt - u0);
+  p.n_frames = upload(c, n_frames, n_utt);
+  for (int u0 = 0; u0 < n_utt; u0 += kGridY) {
+    const int n = std::min(kGridY, n_utt - u0);
     p.u0 = u0;
     if (generate) launch_mlpg(p, half_width, n, max_frames, c->stream);
     else launch_delta(p, half_width, n, max_frames, c->stream);
@@ -2357,8 +2335,8 @@ int world_hip_synthesis_pulses_dropped(WorldHipContext *c, int *needed) {
 unsigned long long world_hip_workspace_bytes(WorldHipContext *c) {
   if (!c) return 0;
   unsigned long long bytes = c->arena.cap;
-  for (const ResampleTable &t : c->resample_tables) bytes += (2ull * t.W * sizeof(double) + sizeof(int)) * t.L;
-  for (const McepTable &t : c->mcep_tables) bytes += sizeof(double) * (unsigned long long)t.k_pad * t.n_pad;
+  for (const ResampleTable &t : c->resample_tables) bytes += t.bytes();
+  for (const McepTable &t : c->mcep_tables) bytes += t.bytes();
   return bytes;
 }
 
