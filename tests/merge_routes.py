@@ -15,8 +15,8 @@ CASES = [(0, 16000, 1.0), (3, 16000, 2.5), (11, 16000, 3.0), (21, 44100, 1.5)]
 def main(kind, path):
     out = {}
     if kind == "emu":
-        from world_amd.api import HostAPI
-        H = HostAPI(os.path.join(ROOT, "tests", "emu", "libworld_emu.so"))
+        from backends import emu_host
+        H = emu_host()
         for seed, fs, dur in CASES[:3]:
             out[f"{seed}_{fs}"] = H.harvest(synth.utterance(seed, fs, dur).numpy(), fs)[1]
     else:

@@ -10,16 +10,14 @@
 3. The same criterion with fft_size off the rate's default (CheapTrick on the classic emulation).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from backends import emu  # noqa: F401 (a fixture)
 from util import ACC_A, ACC_C, ULP, assert_accurate, ct_floor, discrete_agreement, rel_errors
 from util import offdefault_f0 as _f0, synth_inputs as _synth_inputs, utterance as _signal
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
 mpmath = pytest.importorskip("mpmath")
 
 
@@ -195,13 +193,6 @@ def test_wide_interp1_against_mpmath(wide, port_oracle, mp40):
 
 
 # ---- the criterion on the emulated units ----
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
 def _track(kind, fs, nf, seed):
     """F0 from the reference's Harvest or a caller-made track in the style of tests/fuzz_given_f0.py"""
     rng = np.random.default_rng(seed)

@@ -6,14 +6,12 @@ Tolerances.  Every step is a specified IEEE operation (subtract, multiply, add i
 so the paths, K, both maps and D are compared bit for bit; mcd_db to 2 ulp (the constant (10 / ln 10) sqrt(2) may be
 spelled with another rounding)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import cpu_backend, lib  # noqa: F401 (lib: a fixture)
 
 _ip = C.POINTER(C.c_int)
 _lp = C.POINTER(C.c_longlong)
@@ -80,24 +78,8 @@ def mcd_db(D, K):
 
 
 # ---- a backend: the C call on arrays that live where the library wants them ---------------------------------------------
-class Backend:
-    """world_hip_align_batch on NumPy arrays.  Here device memory is host memory; the GPU suite overrides dev / host / addr
-    with torch tensors."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
-
-    def dev(self, a):
-        return np.ascontiguousarray(a)
-
-    def host(self, d):
-        return d
-
-    def addr(self, d):
-        return d.ctypes.data
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
+class Backend(backends.Backend):
+    """world_hip_align_batch on the arrays of backends.Backend"""
 
     def buffers(self, P, p_stride, map_stride, want=OUTPUTS):
         shapes = dict(path=((P, p_stride, 2), np.int32), path_len=((P,), np.int32), summary=((P, 3), np.float64),
@@ -129,19 +111,7 @@ class Backend:
         return rc, {k: self.host(v) for k, v in outs.items()}
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 # ---- helpers -------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,6 @@
 """Alignment by dynamic time warping on the MI355X (include/world_hip.h: world_hip_align_batch): the cases of
 test_align_cpu.py through the shipped library, graph replay, the Python layer, an utterance against its own time-stretched
 resynthesis, and the mcd tool."""
-import ctypes as C
-import os
 import re
 import subprocess
 import sys
@@ -12,41 +10,17 @@ import numpy as np
 import pytest
 
 import test_align_cpu as cpu
+from backends import ROOT, OnGpu, gpu_backend, wh, write_wav  # noqa: F401 (wh: a fixture)
 from util import load_golden
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 def test_degenerate_pairs(be):
@@ -162,12 +136,6 @@ def test_python_layer_on_dense_tensors_and_record_blocks(wh, be):
         assert np.array_equal(got[3][u, :len(B)].cpu().numpy(), want[2])
 
 
-def _write_wav(path, q, fs):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(fs)
-        w.writeframes(np.asarray(q).astype("<i2").tobytes())
-
-
 def test_an_utterance_against_its_stretched_resynthesis(wh):
     """golden utterance -> analyze_coded; resynthesize at time_scale 1.5 -> analyze_coded; aligned with c0 skipped: the path
     is the statement's on the same coded rows, and map_b drives modify_frames to n_b frames.  How close the map lies to
@@ -212,7 +180,7 @@ def test_mcd_tool_prints_what_the_python_call_gives(wh, tmp_path):
     names = []
     for name, seconds, seed in (("ref", 0.40, 31), ("test", 0.55, 32)):
         q = np.round(synth.vowel(fs, seconds, seed=seed).numpy() * 32768).clip(-32768, 32767).astype(np.int16)
-        _write_wav(tmp_path / (name + ".wav"), q, fs)
+        write_wav(tmp_path / (name + ".wav"), q, fs)
         names.append(str(tmp_path / (name + ".wav")))
     r = subprocess.run([sys.executable, "-m", "world_amd.tools", "mcd", *names, "--dims", "25"], cwd=ROOT, capture_output=True,
                        text=True, timeout=300)
@@ -237,7 +205,7 @@ def test_transform_align_to_gives_the_other_recordings_timing(wh, tmp_path):
     for name, seconds, seed in (("in", 0.40, 41), ("other", 0.55, 42)):
         q = np.round(synth.vowel(fs, seconds, seed=seed).numpy() * 32768).clip(-32768, 32767).astype(np.int16)
         paths[name] = str(tmp_path / (name + ".wav"))
-        _write_wav(paths[name], q, fs)
+        write_wav(paths[name], q, fs)
     out = tmp_path / "out"
     run = lambda *more: subprocess.run([sys.executable, "-m", "world_amd.tools", "transform", paths["in"], "--outdir", str(out),
                                         "--align-to", *more], cwd=ROOT, capture_output=True, text=True, timeout=300)

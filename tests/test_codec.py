@@ -2,11 +2,11 @@
 restatement, the host-emulated kernels and the HIP path against golden vectors generated
 from the unmodified reference (tests/golden/make_golden.py: codec.npz)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from backends import emu  # noqa: F401 (a fixture)
 from util import GOLDEN, RTOL, load_golden, max_rel
 
 NAMES = ["vaiueo2d_harvest", "vowel48k_harvest", "vowel16k_dio"]
@@ -45,14 +45,6 @@ def test_port_codec_matches_golden(port_oracle, codec_golden, name):
 @pytest.mark.parametrize("name", NAMES[:2])
 def test_reference_codec_reproduces_golden(ref_oracle, codec_golden, name):
     check_codec(ref_oracle, codec_golden, name, rtol=1e-10, atol=1e-12)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    emu_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.run(["make", "-s", "-f", os.path.join(emu_dir, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(os.path.join(emu_dir, "libworld_emu.so"))
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -8,6 +8,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from backends import emu_host, emu_library
 from world_amd import distributed as wd
 
 
@@ -129,11 +130,8 @@ def test_analyze_sharded_refuses_a_dense_analysis_with_another_bin_count():
 def _emu_analyze(x, fs, x_len=None, frame_period=5.0, **_):
     """WorldHip.analyze's contract on CPU tensors, computed by the emulated kernels (tests/emu/libworld_emu.so)
     through the drop-in C ABI, one utterance at a time"""
-    import subprocess
-    from world_amd.api import HostAPI, cheaptrick_fft_size, frame_count
-    emu_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.run(["make", "-s", "-f", os.path.join(emu_dir, "Makefile")], check=True)
-    H = HostAPI(os.path.join(emu_dir, "libworld_emu.so"))
+    from world_amd.api import cheaptrick_fft_size, frame_count
+    H = emu_host()
     fft = cheaptrick_fft_size(fs)
     nf = [frame_count(fs, int(n), frame_period) for n in x_len]
     B, F, nb = x.shape[0], max(nf), fft // 2 + 1
@@ -202,11 +200,8 @@ def test_chunk_sizes_taper_the_last_sub_batch():
 def _emu_packed(wire_cols):
     """WorldHip.analyze_packed's contract on CPU tensors: world_hip_analyze_packed of the host-compiled library"""
     import ctypes as C
-    import subprocess
-    from world_amd.api import (CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count, load_library)
-    emu_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.run(["make", "-s", "-f", os.path.join(emu_dir, "Makefile")], check=True)
-    L = load_library(os.path.join(emu_dir, "libworld_emu.so"))
+    from world_amd.api import CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count
+    L = emu_library()
     ctx = L.world_hip_create(0, None)
 
     def run(x, fs, block, first_row=0, x_len=None, frame_period=5.0, **_):
@@ -225,11 +220,8 @@ def _emu_coded(dims):
     """WorldHip.analyze_coded's contract on CPU tensors: world_hip_analyze_coded of the host-compiled library; also returns a
     coder of dense rows (world_hip_code_*) for the comparison"""
     import ctypes as C
-    import subprocess
-    from world_amd.api import (CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count, load_library)
-    emu_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.run(["make", "-s", "-f", os.path.join(emu_dir, "Makefile")], check=True)
-    L = load_library(os.path.join(emu_dir, "libworld_emu.so"))
+    from world_amd.api import CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count
+    L = emu_library()
     ctx = L.world_hip_create(0, None)
 
     def run(x, fs, block, first_row=0, x_len=None, frame_period=5.0, **_):
@@ -348,11 +340,8 @@ def test_own_buffers_survive_the_next_call():
 def _emu_range_backend(fs):
     """harvest / spectral_range of analyze_long_sharded on CPU tensors: the host-compiled library's batched entry points"""
     import ctypes as C
-    import subprocess
-    from world_amd.api import (CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count, load_library)
-    emu_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.run(["make", "-s", "-f", os.path.join(emu_dir, "Makefile")], check=True)
-    L = load_library(os.path.join(emu_dir, "libworld_emu.so"))
+    from world_amd.api import CheapTrickOption, D4COption, HarvestOption, cheaptrick_fft_size, frame_count
+    L = emu_library()
     ctx = L.world_hip_create(0, None)
     fft = cheaptrick_fft_size(fs)
     ip = C.POINTER(C.c_int)

@@ -13,16 +13,10 @@ import time
 import numpy as np
 import pytest
 
+from backends import EMU_DIR, ROOT, emu_host as _emu
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libworld_emu.so")
-
-
-def _emu():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(EMU_LIB)
 
 
 def _signal(fs, seconds, seed):

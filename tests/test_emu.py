@@ -9,16 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from backends import EMU_DIR, emu  # noqa: F401 (emu: a fixture)
 from util import check_against_golden, load_golden
-
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(os.path.join(EMU_DIR, "libworld_emu.so"))
 
 
 @pytest.mark.parametrize("name", ["vaiueo2d_harvest", "vowel48k_harvest", "vaiueo2d_dio", "vowel16k_dio", "vowel192k_harvest"])

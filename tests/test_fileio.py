@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from backends import emu_library_path
 from util import GOLDEN, RTOL, max_rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -144,9 +145,7 @@ def test_reference_tools_agree_with_their_own_fixtures(fx, tmp_path):
 
 def test_emulated_audio_files(fx, tmp_path):
     from world_amd.api import FileAPI
-    emu_dir = os.path.join(ROOT, "tests", "emu")
-    subprocess.run(["make", "-s", "-C", emu_dir], check=True)
-    E = FileAPI(os.path.join(emu_dir, "libworld_emu.so"), hip_runtime=False)
+    E = FileAPI(emu_library_path(), hip_runtime=False)
     check_audio_files(E, fx, tmp_path)
     check_parameter_files(E, fx, tmp_path)
 
@@ -288,9 +287,7 @@ def test_randomised_files_against_the_reference_tools(tmp_path):
     lib = os.path.join(REF_DIR, "libworld_tools_ref.so")
     if not os.path.exists(lib):
         pytest.skip("oracle/_ref not built")
-    emu_dir = os.path.join(ROOT, "tests", "emu")
-    subprocess.run(["make", "-s", "-C", emu_dir], check=True)
-    R, E, F = FileAPI(lib, hip_runtime=False), FileAPI(os.path.join(emu_dir, "libworld_emu.so"), hip_runtime=False), FileAPI()
+    R, E, F = FileAPI(lib, hip_runtime=False), FileAPI(emu_library_path(), hip_runtime=False), FileAPI()
     rng = np.random.default_rng(99)
     d = str(tmp_path)
     for case in range(120):

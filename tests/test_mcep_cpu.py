@@ -23,19 +23,15 @@ Bounds (the statement's; none comes from the code under test).
 Inputs: envelopes exp(-8 - 6 f + 3 cos 7 f + noise), f = k / H; the noise is 0.5 N(0, 1) per bin plus a level of 0, 4 or 9 per
 row, so that ln sp has both signs (the curve alone stays below -5) over about 40 dB within a row."""
 import ctypes as C
-import os
-import subprocess
-from contextlib import contextmanager
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import SENTINEL_F64 as SENTINEL, cached, cpu_backend, lib, same_bits  # noqa: F401 (lib: a fixture)
 
 LD = np.longdouble
-SENTINEL = -7.0
 SHAPES = [(128, 24, 0.42), (256, 39, 0.554), (512, 59, -0.3), (128, 0, 0.41), (128, 64, 0.0), (2048, 59, 0.554)]
 SHAPE_IDS = ["%d-%d-%g" % s for s in SHAPES]
 TABLE_SHAPES = SHAPES[:3] + [SHAPES[4]]
@@ -45,19 +41,6 @@ ALPHAS = {8000: 0.312, 16000: 0.41, 22050: 0.455, 24000: 0.466, 32000: 0.504, 44
           192000: 0.693}
 U = 2.0 ** -53
 BITS = 140
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        v = make()
-        for a in (v if isinstance(v, tuple) else (v,)):
-            if isinstance(a, np.ndarray):
-                a.setflags(write=False)
-        _cache[key] = v
-    return _cache[key]
-
 
 # ---- the statement, in mpmath ---------------------------------------------------------------------------------------------
 def _mp():
@@ -181,39 +164,9 @@ def encode_oracle(fft_size, order, alpha):
     return cached(("enc", fft_size, order, alpha), make)
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
-
-
 # ---- a backend: the C calls on arrays that live where the library wants them ---------------------------------------------
-class Backend:
-    """world_hip_sp2mc / _mc2sp on NumPy arrays.  Here device memory is host memory; the GPU suite overrides dev / host /
-    addr with torch tensors and `fresh` with a new WorldHip."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
-
-    def dev(self, a):
-        return np.ascontiguousarray(a).copy()
-
-    def host(self, d):
-        return d
-
-    def addr(self, d):
-        return d.ctypes.data
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
-
-    @contextmanager
-    def fresh(self):
-        c = self.lib.world_hip_create(0, None)
-        assert c
-        try:
-            yield type(self)(self.lib, c)
-        finally:
-            self.lib.world_hip_destroy(c)
+class Backend(backends.Backend):
+    """world_hip_sp2mc / _mc2sp on the arrays of backends.Backend"""
 
     def call(self, decode, rows, fft_size, order, alpha, in_ptr, in_stride, out_ptr, out_stride):
         """the C call itself on addresses (None: NULL)"""
@@ -243,19 +196,7 @@ class Backend:
         return np.array(out[:rows, :out_cols])
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 def library_tables(lib, fft_size, order, alpha):

@@ -4,55 +4,21 @@ exercises (the tables are asymmetric by nature: a row / column swap of the resul
 replay, the Python layer, the pipeline from a waveform and the tools."""
 import os
 import wave
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import test_mcep_cpu as cpu
+from backends import OnGpu, gpu_backend, wh, write_wav  # noqa: F401 (wh: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.array(a, order="C")).cuda()              # (a copy: the shared inputs are read-only)
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-    @contextmanager
-    def fresh(self):
-        from world_amd.api import WorldHip
-        w = WorldHip()
-        try:
-            yield GpuBackend(w)
-        finally:
-            w.close()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 # ---- the cases of the CPU file -------------------------------------------------------------------------------------------
@@ -158,7 +124,7 @@ def vowel(wh, tmp_path_factory):
     from world_amd.api import cheaptrick_fft_size, frame_count
     path = str(tmp_path_factory.mktemp("mcep") / "vowel.wav")
     q = np.round(synth.vowel(FS, SECONDS, seed=3).numpy() * 32768).clip(-32768, 32767).astype("<i2")
-    _write_wav(path, q)
+    write_wav(path, q, FS)
     x = wh.wavread(path)[0]
     fft_size, n = cheaptrick_fft_size(FS, 71.0), frame_count(FS, x.numel(), 5.0)
     block = torch.zeros((n, wh.lib.world_hip_record_columns(fft_size, 0)), dtype=torch.float64, device=wh.device)
@@ -200,13 +166,6 @@ def test_pipeline_from_packed_records_and_back_to_audio(wh, vowel):
         wh.sp2mc(block[:, 2:2 + K], ORDER, alpha, out=block[:, 2 + K:2 + K + ORDER + 1])
 
 
-def _write_wav(path, q):
-    with wave.open(path, "wb") as f:
-        f.setnchannels(1); f.setsampwidth(2); f.setframerate(FS)
-        f.writeframes(np.asarray(q, dtype="<i2").tobytes())
-    return path
-
-
 def test_features_tools_write_what_the_python_path_computes(wh, vowel, tmp_path, capsys):
     from world_amd import tools
     n, fft_size = vowel["n"], vowel["fft_size"]
@@ -214,7 +173,7 @@ def test_features_tools_write_what_the_python_path_computes(wh, vowel, tmp_path,
     with wave.open(vowel["path"]) as f:
         q = np.frombuffer(f.readframes(f.getnframes()), dtype="<i2").copy()
     q[-int(0.15 * FS):] = 0
-    path = _write_wav(str(tmp_path / "vowel.wav"), q)
+    path = write_wav(str(tmp_path / "vowel.wav"), q, FS)
     tools.main(["features", path, "--outdir", str(tmp_path), "--order", str(ORDER)])
     stem = str(tmp_path / "vowel")
     _, f0, sp, ap, nf = wh.analyze(wh.wavread(path)[0][None].contiguous(), FS)

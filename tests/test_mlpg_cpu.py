@@ -18,19 +18,15 @@ Bounds (the statement's; none comes from the code under test).
   against scipy's 1.8e-15 (16 * 2^-53).
 """
 import ctypes as C
-import os
-import subprocess
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import SENTINEL_F64 as SENTINEL, cpu_backend, lib, same_bits  # noqa: F401 (lib: a fixture)
 
 LD = np.longdouble
 U53 = 2.0 ** -53
-SENTINEL = -7.0
 FILL = -1e10
 OMEGA_MAX = 16 * U53
 
@@ -38,11 +34,6 @@ W1 = np.array([[1.0]])
 W3 = np.array([[0.0, 1.0, 0.0], [-0.5, 0.0, 0.5], [1.0, -2.0, 1.0]])
 W5 = np.array([[0.0, 0.0, 1.0, 0.0, 0.0], [-0.2, -0.1, 0.0, 0.1, 0.2], [0.285714, -0.142857, -0.285714, -0.142857, 0.285714]])
 WINDOWS = {"static": W1, "three": W3, "five": W5}
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
 
 
 # ---- the statement --------------------------------------------------------------------------------------------------------
@@ -117,36 +108,11 @@ def runs_of(present):
 
 
 # ---- a backend: the C calls on arrays that live where the library wants them ---------------------------------------------
-class Backend:
-    """world_hip_delta_batch / _mlpg_batch on NumPy arrays.  Here device memory is host memory; the GPU suite overrides dev /
-    host / addr with torch tensors and `fresh` with a new WorldHip."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
-
-    def dev(self, a):
-        return np.ascontiguousarray(a).copy()
-
-    def host(self, d):
-        return d
-
-    def addr(self, d):
-        return d.ctypes.data
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
+class Backend(backends.Backend):
+    """world_hip_delta_batch / _mlpg_batch on the arrays of backends.Backend"""
 
     def workspace(self):
         return int(self.lib.world_hip_workspace_bytes(self.ctx))
-
-    @contextmanager
-    def fresh(self):
-        c = self.lib.world_hip_create(0, None)
-        assert c
-        try:
-            yield type(self)(self.lib, c)
-        finally:
-            self.lib.world_hip_destroy(c)
 
     @staticmethod
     def _p(a):
@@ -239,19 +205,7 @@ class Backend:
         return self._finish(rc, d_out, out, lens, D, [(d_in, xin), (d_v, v)] + ([] if m is None else [(d_m, m)]))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------

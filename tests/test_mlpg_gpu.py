@@ -6,55 +6,21 @@ Measured on one MI355X: omega <= 2.63 * 2^-53 over the accuracy cases (the emula
 fused operation in both); round trip 8.9e-16 = 8 * 2^-53 against scipy.linalg.solveh_banded's 1.8e-15 = 16 * 2^-53."""
 import os
 import wave
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import test_mlpg_cpu as cpu
+from backends import OnGpu, gpu_backend, wh, write_wav  # noqa: F401 (wh: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.array(a, order="C")).cuda()              # (a copy: the shared inputs are read-only)
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-    @contextmanager
-    def fresh(self):
-        from world_amd.api import WorldHip
-        w = WorldHip()
-        try:
-            yield GpuBackend(w)
-        finally:
-            w.close()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 # ---- the cases of the CPU file -------------------------------------------------------------------------------------------
@@ -203,19 +169,12 @@ def test_worldhip_deltas_and_mlpg_honour_lengths_strides_and_layouts(wh, be):
 FS, ORDER = 16000, 24
 
 
-def _write_wav(path, q):
-    with wave.open(path, "wb") as f:
-        f.setnchannels(1); f.setsampwidth(2); f.setframerate(FS)
-        f.writeframes(np.asarray(q, dtype="<i2").tobytes())
-    return path
-
-
 def test_tools_features_deltas_mlpg_and_back_to_audio(wh, tmp_path):
     from world_amd import synth, tools
     q = np.round(synth.vowel(FS, 0.5, seed=3).numpy() * 32768).clip(-32768, 32767).astype("<i2")
     q[-int(0.15 * FS):] = 0                                                  # unvoiced frames as well
     q[:int(0.05 * FS)] = 0
-    path = _write_wav(str(tmp_path / "vowel.wav"), q)
+    path = write_wav(str(tmp_path / "vowel.wav"), q, FS)
     tools.main(["features", path, "--outdir", str(tmp_path), "--order", str(ORDER)])
     stem = str(tmp_path / "vowel")
     mgc, lf0 = np.fromfile(stem + ".mgc", dtype="<f4").reshape(-1, ORDER + 1), np.fromfile(stem + ".lf0", dtype="<f4")

@@ -3,13 +3,12 @@ host-compiled kernels (tests/emu/libworld_emu.so; device memory is host memory t
 world_hip_f0_statistics and world_hip_resynthesize_batch against a NumPy statement of the reference's arithmetic."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+from backends import ROOT, envelope, lib, rel  # noqa: F401 (lib: a fixture)
+
 REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libworld_ref.so")
 
 _dp = C.POINTER(C.c_double)
@@ -61,30 +60,7 @@ def map_f0(f0, scale, target=None):
     return out * scale
 
 
-def envelope(fs, fft_size, rows, seed):
-    """positive, formant-shaped rows with a tilt and some ripple"""
-    rng = np.random.default_rng(seed)
-    k = np.arange(fft_size // 2 + 1) * fs / fft_size
-    env = np.zeros((rows, k.size))
-    for c, bw, a in ((700.0, 130.0, 1.0), (1220.0, 170.0, 0.5), (2600.0, 240.0, 0.25), (3500.0, 300.0, 0.1)):
-        centre = c * (1.0 + 0.1 * rng.uniform(-1, 1, rows))[:, None]
-        env += a / (1.0 + ((k[None, :] - centre) / bw) ** 2)
-    return 1e-3 * env ** 2 * (1.0 + 0.3 * rng.uniform(0, 1, env.shape)) + 1e-9
-
-
-def rel(a, b):
-    return float(np.max(np.abs(a - b) / np.abs(b))) if a.size else 0.0
-
-
 # ---- the emulated library ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    L = load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-    return L
-
-
 @pytest.fixture(scope="module")
 def ctx(lib):
     c = lib.world_hip_create(0, None)

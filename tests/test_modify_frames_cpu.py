@@ -8,14 +8,12 @@ equality.  Rows that went through the warp: 1e-13 relative, what tests/test_modi
 device log / exp differ from libm in the last bits).  F0 frames that went through the log-F0 conversion: 1e-12 relative,
 what that file holds modify_f0 to.  Everything else (copies, one multiply, the clamp) is exact."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import cpu_backend, envelope, lib, rel  # noqa: F401 (lib: a fixture)
 
 _ip = C.POINTER(C.c_int)
 CURVES = ("time_map", "f0_target", "f0_scale", "formant_shift", "ap_gain")
@@ -130,45 +128,14 @@ def statement(f0, sp, ap, n_out, fs, fft_size, scale=1.0, ratio=1.0, target=None
     return f0_o, sp_o, ap_o, conv
 
 
-def envelope(fs, fft_size, rows, seed):
-    """positive, formant-shaped rows with a tilt and some ripple (as tests/test_modify_cpu.py)"""
-    rng = np.random.default_rng(seed)
-    k = np.arange(fft_size // 2 + 1) * fs / fft_size
-    env = np.zeros((rows, k.size))
-    for c, bw, a in ((700.0, 130.0, 1.0), (1220.0, 170.0, 0.5), (2600.0, 240.0, 0.25), (3500.0, 300.0, 0.1)):
-        centre = c * (1.0 + 0.1 * rng.uniform(-1, 1, rows))[:, None]
-        env += a / (1.0 + ((k[None, :] - centre) / bw) ** 2)
-    return 1e-3 * env ** 2 * (1.0 + 0.3 * rng.uniform(0, 1, env.shape)) + 1e-9
-
-
-def rel(a, b):
-    return float(np.max(np.abs(a - b) / np.abs(b))) if a.size else 0.0
-
-
 def fft_of(fs):
     from world_amd.api import cheaptrick_fft_size
     return cheaptrick_fft_size(fs, 71.0)
 
 
 # ---- a backend: the two C calls on arrays that live where the library wants them ----------------------------------------
-class Backend:
-    """world_hip_modify_batch / world_hip_modify_frames_batch on NumPy arrays.  Here device memory is host memory; the GPU
-    suite overrides dev / host / ptr with torch tensors."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
-
-    def dev(self, a):
-        return np.ascontiguousarray(a)
-
-    def host(self, d):
-        return d
-
-    def ptr(self, d):
-        return C.c_void_p(d.ctypes.data) if d is not None else None
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
+class Backend(backends.Backend):
+    """world_hip_modify_batch / world_hip_modify_frames_batch on the arrays of backends.Backend"""
 
     def modify(self, fs, fft, nf, mods, f0=None, sp=None):
         """out of place -> (f0', sp') with NaN beyond"""
@@ -202,19 +169,7 @@ class Backend:
         return (rc, *[self.host(o) if o is not None else None for o in outs])
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 def mods_of(n, scale=1.0, ratio=1.0, target=None):

@@ -5,49 +5,25 @@ import ctypes as C
 import os
 import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
 
 import test_modify_frames_cpu as cpu
+from backends import ROOT, OnGpu, gpu_backend, read_wav, wh, write_wav  # noqa: F401 (wh: a fixture)
 from util import load_golden
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
 _ip = C.POINTER(C.c_int)
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def ptr(self, d):
-        return C.c_void_p(d.data_ptr()) if d is not None else None
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 RATES = [48000, 192000]
@@ -191,17 +167,6 @@ def test_python_layer_validates_and_matches_the_c_call(wh, be):
 
 
 # ---- against the reference -----------------------------------------------------------------------------------------------
-def _write_wav(path, q, fs):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(fs)
-        w.writeframes(np.asarray(q).astype("<i2").tobytes())
-
-
-def _read_wav(path):
-    with wave.open(str(path)) as w:
-        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int32), w.getframerate()
-
-
 @pytest.mark.parametrize("args", [("1.5", "1.2"), ("0.7", "0.85"), ("2.0",)])
 def test_constant_curves_reproduce_the_reference_test_program(wh, tmp_path, args):
     """oracle/_ref/test_ref (the reference's test.cpp, unmodified) with its F0 / formant arguments against
@@ -214,10 +179,10 @@ def test_constant_curves_reproduce_the_reference_test_program(wh, tmp_path, args
         pytest.skip("oracle/_ref/test_ref was not prebuilt (needs the reference tree at build time)")
     g = load_golden("vaiueo2d_harvest")
     src = tmp_path / "in.wav"
-    _write_wav(src, g["q"], g["fs"])
+    write_wav(src, g["q"], g["fs"])
     r = subprocess.run([exe, str(src), "out.wav", *args], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "complete." in r.stdout, r.stdout + r.stderr
-    want, fs = _read_wav(tmp_path / "01out.wav")
+    want, fs = read_wav(tmp_path / "01out.wav")
     x = torch.from_numpy(g["x"]).to(wh.device)[None].contiguous()
     n = frame_count(fs, x.shape[1], 5.0)
     const = lambda v: torch.full((n,), float(v), dtype=torch.float64, device=wh.device)
@@ -266,7 +231,7 @@ def test_transform_tool_duration_and_f0_from(wh, tmp_path):
     fs = 16000
     q = np.round(synth.vowel(fs, 0.4, seed=31).numpy() * 32768).clip(-32768, 32767).astype(np.int16)
     src = tmp_path / "in.wav"
-    _write_wav(src, q, fs)
+    write_wav(src, q, fs)
     x, _ = wh.wavread(str(src))
     n = frame_count(fs, x.numel(), 5.0)
     track = np.where(np.arange(25) % 5 == 4, 0.0, np.linspace(120.0, 260.0, 25))
@@ -281,6 +246,6 @@ def test_transform_tool_duration_and_f0_from(wh, tmp_path):
     y, yl = wh.resynthesize_frames(x[None].contiguous(), fs, time_map=uniform_time_map(n, n_out, device=wh.device),
                                    f0_target=torch.from_numpy(target).cuda(), formant_shift=1.1)
     want = wh.double_to_pcm16(y[0, :int(yl[0])]).cpu().numpy().astype(np.int32)
-    got, fs2 = _read_wav(out / "in.wav")
+    got, fs2 = read_wav(out / "in.wav")
     assert fs2 == fs and np.array_equal(got, want)
     assert abs(len(got) / fs - 0.6) <= 0.005

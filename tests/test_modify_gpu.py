@@ -4,39 +4,17 @@ the separate library calls."""
 import os
 import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
 
+from backends import ROOT, read_wav, wh, write_wav  # noqa: F401 (wh: a fixture)
 from test_modify_cpu import envelope, log_f0_stats, map_f0, rel, warp_rows
 from util import load_golden
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-def _write_wav(path, q, fs):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(fs)
-        w.writeframes(np.asarray(q).astype("<i2").tobytes())
-
-
-def _read_wav(path):
-    with wave.open(str(path)) as w:
-        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int32), w.getframerate()
 
 
 @pytest.mark.parametrize("args", [("1.5", "1.2"), ("0.7", "0.85"), ("2.0",)])
@@ -49,10 +27,10 @@ def test_reference_test_program_end_to_end(wh, tmp_path, args):
         pytest.skip("oracle/_ref/test_ref was not prebuilt (needs the reference tree at build time)")
     g = load_golden("vaiueo2d_harvest")
     src = tmp_path / "in.wav"
-    _write_wav(src, g["q"], g["fs"])
+    write_wav(src, g["q"], g["fs"])
     r = subprocess.run([exe, str(src), "out.wav", *args], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "complete." in r.stdout, r.stdout + r.stderr
-    want, fs = _read_wav(tmp_path / "01out.wav")
+    want, fs = read_wav(tmp_path / "01out.wav")
     x = torch.from_numpy(g["x"]).to(wh.device)[None].contiguous()
     ratio = float(args[1]) if len(args) > 1 else 1.0
     y, yl = wh.resynthesize(x, fs, f0_scale=float(args[0]), formant_shift=ratio, f0_floor=40.0)
@@ -240,7 +218,7 @@ def test_transform_tool_writes_what_the_python_path_computes(wh, tmp_path):
     for k, sec in enumerate((0.4, 0.3)):
         q = np.round(synth.vowel(fs, sec, seed=30 + k).numpy() * 32768).clip(-32768, 32767).astype(np.int16)
         p = tmp_path / f"in{k}.wav"
-        _write_wav(p, q, fs)
+        write_wav(p, q, fs)
         paths.append(str(p))
     out = tmp_path / "out"
     r = subprocess.run([sys.executable, "-m", "world_amd.tools", "transform", *paths, "--outdir", str(out),
@@ -251,5 +229,5 @@ def test_transform_tool_writes_what_the_python_path_computes(wh, tmp_path):
         x, fs_ = wh.wavread(p)
         y, yl = wh.resynthesize(x[None].contiguous(), fs_, f0_scale=1.4, formant_shift=1.1, time_scale=1.3)
         want = wh.double_to_pcm16(y[0, :int(yl[0])]).cpu().numpy().astype(np.int32)
-        got, fs2 = _read_wav(out / os.path.basename(p))
+        got, fs2 = read_wav(out / os.path.basename(p))
         assert fs2 == fs and np.array_equal(got, want)

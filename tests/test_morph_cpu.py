@@ -9,20 +9,15 @@ w == 0 shortcut are the same IEEE operations in the same order under -ffp-contra
 through log / exp: 1e-13 relative, the bar tests/test_modify_cpu.py holds modify_warp_sp to (the device log / exp differ
 from libm in the last bits)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_align_cpu as al
 import test_modify_frames_cpu as mf
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+from backends import SENTINEL_F64 as SENTINEL, cpu_backend, lib, rel  # noqa: F401 (lib: a fixture)
 
 _ip = C.POINTER(C.c_int)
-SENTINEL = -7.0
 COUNTS = [(1, 1), (1, 7), (7, 1), (5, 9), (40, 23), (300, 517)]
 TIME_RATES = [0.0, 1e-9, 0.25, 0.3, 1.0 / 3.0, 0.5, 0.9, 1.0 - 1e-9, 1.0]
 TOL = 1e-13
@@ -108,15 +103,9 @@ def statement(A, B, path, rates, curves=None):
     return f0, sp, ap, sa, sb, through
 
 
-def rel(a, b):
-    with np.errstate(all="ignore"):
-        return float(np.max(np.abs(a - b) / np.abs(b))) if a.size else 0.0
-
-
 # ---- a backend: the C calls on arrays that live where the library wants them ---------------------------------------------
 class Backend(al.Backend):
-    """world_hip_morph_batch (and, from tests/test_align_cpu.py, world_hip_align_batch) on NumPy arrays.  Here device
-    memory is host memory; the GPU suite overrides dev / host / addr with torch tensors."""
+    """world_hip_morph_batch (and, from tests/test_align_cpu.py, world_hip_align_batch) on the arrays of backends.Backend"""
 
     def vp(self, d):
         return C.c_void_p(self.addr(d)) if d is not None else None
@@ -182,19 +171,7 @@ class Backend(al.Backend):
         return [self.host(o) for o in outs]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 # ---- inputs, made once and shared (never changed) ------------------------------------------------------------------------

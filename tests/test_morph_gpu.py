@@ -1,7 +1,6 @@
 """Morph of two aligned utterances on the MI355X (include/world_hip.h: world_hip_morph_batch): the cases of
 test_morph_cpu.py through the shipped library, graph replay, the Python layer, an utterance against its own time-stretched
 resynthesis from the waveform to the waveform, and the morph tool."""
-import os
 import subprocess
 import sys
 import wave
@@ -10,41 +9,17 @@ import numpy as np
 import pytest
 
 import test_morph_cpu as cpu
+from backends import ROOT, OnGpu, gpu_backend, wh, write_wav  # noqa: F401 (wh: a fixture)
 from util import utterance
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 @pytest.mark.parametrize("r", cpu.TIME_RATES)
@@ -244,12 +219,6 @@ def test_an_utterance_morphed_half_way_to_its_stretched_resynthesis(wh):
     assert y2_len == y_len and torch.equal(y2, out)
 
 
-def _write_wav(path, q, fs):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(fs)
-        w.writeframes(np.asarray(q).astype("<i2").tobytes())
-
-
 def test_morph_tool_writes_what_the_python_path_computes(wh, tmp_path):
     from world_amd import synth, tools
     fs = 16000
@@ -257,7 +226,7 @@ def test_morph_tool_writes_what_the_python_path_computes(wh, tmp_path):
     for name, seconds, seed, rate in (("a", 0.30, 51, fs), ("b", 0.42, 52, fs), ("c", 0.30, 53, 22050)):
         q = np.round(synth.vowel(rate, seconds, seed=seed).numpy() * 32768).clip(-32768, 32767).astype(np.int16)
         names.append(str(tmp_path / (name + ".wav")))
-        _write_wav(names[-1], q, rate)
+        write_wav(names[-1], q, rate)
     out = tmp_path / "out.wav"
     run = lambda *args: subprocess.run([sys.executable, "-m", "world_amd.tools", "morph", *args], cwd=ROOT, capture_output=True,
                                        text=True, timeout=300)

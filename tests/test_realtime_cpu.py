@@ -9,10 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from backends import EMU_DIR, ROOT, emu  # noqa: F401 (emu: a fixture)
 from util import GOLDEN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
 REF = "/root/reference"
 
 
@@ -86,13 +85,6 @@ def test_realtime_header_compiles_alone(tmp_path, lang):
     cc = "gcc" if lang == "c" else "g++"
     subprocess.run([cc, "-Wall", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "c.o"),
                     str(src)], check=True)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(os.path.join(EMU_DIR, "libworld_emu.so"))
 
 
 @pytest.mark.parametrize("name", NAMES)

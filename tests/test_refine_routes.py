@@ -8,7 +8,8 @@ import os
 import numpy as np
 import pytest
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+from backends import emu  # noqa: F401 (a fixture)
+
 SWITCH = "WORLD_HIP_REFINE_FRAMES"
 
 
@@ -32,14 +33,6 @@ def _both_routes(run):
         if old is not None:
             os.environ[SWITCH] = old
     return new, frames
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import subprocess
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import HostAPI
-    return HostAPI(os.path.join(EMU_DIR, "libworld_emu.so"))
 
 
 @pytest.mark.parametrize("fs", [48000, 16000])

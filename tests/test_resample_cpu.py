@@ -17,18 +17,14 @@ Tolerances.
           and FAST 7.4e-5 / 6.6e-5, through the emulated kernels and on the GPU alike: a margin of 2.5-2.7x under the bars."""
 import ctypes as C
 import math
-import os
-import subprocess
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import SENTINEL_F64 as SENTINEL, cached, cpu_backend, lib, same_bits  # noqa: F401 (lib: a fixture)
 
 _ip = C.POINTER(C.c_int)
-SENTINEL = -7.0
 T = 256                              # outputs per workgroup at these ratios (resample.inc: kResampleThreads)
 BEST = (64, 0.9475937167399596, 14.769656459379492)
 FAST = (16, 0.85, 8.555504641634386)
@@ -92,12 +88,6 @@ def resample(x, fs_in, fs_out, c):
     return acc
 
 
-def same_bits(a, b):
-    """every element bit-equal, NaN compared as equal"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
-
-
 # ---- a backend: the C calls on arrays that live where the library wants them ---------------------------------------------
 def option(design):
     from world_amd.api import WorldHipResampleOption
@@ -115,33 +105,8 @@ def library_table(lib, fs_in, fs_out, design):
     return c
 
 
-class Backend:
-    """world_hip_resample_batch on NumPy arrays.  Here device memory is host memory; the GPU suite overrides dev / host /
-    addr with torch tensors and `fresh` with a new WorldHip."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
-
-    def dev(self, a):
-        return np.ascontiguousarray(a)
-
-    def host(self, d):
-        return d
-
-    def addr(self, d):
-        return d.ctypes.data
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
-
-    @contextmanager
-    def fresh(self):
-        c = self.lib.world_hip_create(0, None)
-        assert c
-        try:
-            yield type(self)(self.lib, c)
-        finally:
-            self.lib.world_hip_destroy(c)
+class Backend(backends.Backend):
+    """world_hip_resample_batch on the arrays of backends.Backend"""
 
     def call(self, n_utt, fs_in, fs_out, design, d_x, x_stride, x_len, d_y, y_stride):
         """the C call itself on device arrays (None: NULL)"""
@@ -165,25 +130,10 @@ class Backend:
         return n_out, self.host(d_y)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 # ---- inputs, made once and shared (never changed) ------------------------------------------------------------------------
-_cache = {}
-
-
 def lengths_for(fs_in, fs_out, design):
     """{1, 2, W, 2 W + 1, 1000, 3001} and the input lengths that put n_out at T - 1, T, T + 1 and 2 T + 1 -- or, where the
     ratio cannot produce that count (8 -> 16 kHz gives even counts only), at the next count it can"""
@@ -199,21 +149,14 @@ def lengths_for(fs_in, fs_out, design):
 
 
 def rows_for(fs_in, fs_out, design):
-    key = ("rows", fs_in, fs_out, design)
-    if key not in _cache:
+    def make():
         rng = np.random.default_rng(fs_in + 3 * fs_out + design[0])
-        _cache[key] = [rng.standard_normal(k) for k in lengths_for(fs_in, fs_out, design)]
-        for r in _cache[key]:
-            r.setflags(write=False)
-    return _cache[key]
+        return [rng.standard_normal(k) for k in lengths_for(fs_in, fs_out, design)]
+    return cached(("rows", fs_in, fs_out, design), make)
 
 
 def lib_table(lib, fs_in, fs_out, design):
-    key = ("table", id(lib), fs_in, fs_out, design)
-    if key not in _cache:
-        _cache[key] = library_table(lib, fs_in, fs_out, design)
-        _cache[key].setflags(write=False)
-    return _cache[key]
+    return cached(("table", id(lib), fs_in, fs_out, design), lambda: library_table(lib, fs_in, fs_out, design))
 
 
 def check_rows(got, n_out, rows, fs_in, fs_out, c):

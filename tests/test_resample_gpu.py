@@ -4,56 +4,22 @@ import os
 import subprocess
 import sys
 import wave
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import test_resample_cpu as cpu
+from backends import ROOT, OnGpu, gpu_backend, pcm16, read_wav, wh, write_wav  # noqa: F401 (wh: a fixture)
 from util import utterance
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-    @contextmanager
-    def fresh(self):
-        from world_amd.api import WorldHip
-        w = WorldHip()
-        try:
-            yield GpuBackend(w)
-        finally:
-            w.close()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 # ---- the cases of the CPU file -------------------------------------------------------------------------------------------
@@ -195,19 +161,6 @@ def test_python_layer_matches_the_c_call_and_validates_quality(wh, be):
 
 
 # ---- the tools -----------------------------------------------------------------------------------------------------------
-def _write_wav(path, x, fs):
-    q = np.round(np.asarray(x) * 32768).clip(-32768, 32767).astype("<i2")
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(fs)
-        w.writeframes(q.tobytes())
-    return str(path)
-
-
-def _read_wav(path):
-    with wave.open(str(path)) as w:
-        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int32), w.getframerate()
-
-
 def _tool(*args):
     return subprocess.run([sys.executable, "-m", "world_amd.tools", *args], cwd=ROOT, capture_output=True, text=True, timeout=300)
 
@@ -215,7 +168,7 @@ def _tool(*args):
 @pytest.fixture(scope="module")
 def wavs(tmp_path_factory):
     d = tmp_path_factory.mktemp("resample_wavs")
-    return {fs: _write_wav(d / f"u{fs}.wav", utterance(fs, seconds, index), fs)
+    return {fs: write_wav(d / f"u{fs}.wav", pcm16(utterance(fs, seconds, index)), fs)
             for fs, seconds, index in ((48000, 0.30, 2), (44100, 0.36, 3), (8000, 0.30, 2))}
 
 
@@ -223,7 +176,7 @@ def test_resample_tool_writes_what_the_python_path_computes(wh, wavs, tmp_path):
     r = _tool("resample", wavs[48000], wavs[44100], "--outdir", str(tmp_path), "--fs", "16000")
     assert r.returncode == 0, r.stdout + r.stderr
     for fs in (48000, 44100):
-        got, rate = _read_wav(tmp_path / os.path.basename(wavs[fs]))
+        got, rate = read_wav(tmp_path / os.path.basename(wavs[fs]))
         x = wh.wavread(wavs[fs])[0]
         y, y_len = wh.resample(x[None].contiguous(), fs, 16000)
         want = wh.double_to_pcm16(y[0, :y_len[0]]).cpu().numpy().astype(np.int32)
@@ -274,7 +227,7 @@ def test_morph_tool_mixes_rates_with_fs_only(wh, wavs, tmp_path):
     assert r.returncode != 0 and "has another sampling rate" in r.stderr and not out.exists()
     r = _tool("morph", wavs[44100], wavs[48000], "-o", str(out), "--fs", "48000")
     assert r.returncode == 0, r.stdout + r.stderr
-    got, rate = _read_wav(out)
+    got, rate = read_wav(out)
     xa, xb = wh.wavread(wavs[44100])[0], wh.wavread(wavs[48000])[0]
     xa = wh.resample(xa[None].contiguous(), 44100, 48000)[0][0]
     y, y_len = tools.morph_waves(wh, xa, xb, 48000, 0.5)
@@ -291,7 +244,7 @@ def test_mcd_and_align_to_mix_rates_with_fs_only(wavs, tmp_path):
     assert r.returncode != 0 and "has another sampling rate" in r.stderr and not os.listdir(tmp_path)
     r = _tool("transform", wavs[44100], "--outdir", str(tmp_path), "--align-to", wavs[48000], "--fs", "16000")
     assert r.returncode == 0, r.stdout + r.stderr
-    got, rate = _read_wav(tmp_path / "u44100.wav")
+    got, rate = read_wav(tmp_path / "u44100.wav")
     assert rate == 16000 and np.abs(got).max() > 0
     # one output frame per frame of the other recording at 16 kHz: its duration, within a frame shift
     with wave.open(wavs[48000]) as w:

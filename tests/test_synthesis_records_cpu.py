@@ -17,16 +17,14 @@ Fixtures.  The rows of these batches are synthetic envelopes coded by the port o
 waveforms only, no parameter rows, and tests/golden/codec.npz holds 12 coded rows per recording at 16 and 48 kHz -- too few
 for the 61-frame utterance, none at 192 kHz and none aperiodic.  Where they fit they are used: case_golden_rows synthesises
 the 12 recorded mel-cepstrum and band-aperiodicity rows of the 16 and 48 kHz recordings as one utterance."""
-import contextlib
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
+import backends
+from backends import ROOT, cpu_backend, lib, smooth_envelope as envelope  # noqa: F401 (lib: a fixture)
 
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
@@ -41,17 +39,6 @@ def ip(a):
 
 
 # ---- fixtures: computed once per shape, shared, never modified -------------------------------------------------------------
-def envelope(fs, fft_size, rows, seed):
-    """smooth positive formant-shaped rows with a tilt, varying from row to row"""
-    rng = np.random.default_rng(seed)
-    k = np.arange(fft_size // 2 + 1) * fs / fft_size
-    env = np.zeros((rows, k.size))
-    for c, bw, a in ((700.0, 130.0, 1.0), (1220.0, 170.0, 0.5), (2600.0, 240.0, 0.25), (3500.0, 300.0, 0.1)):
-        centre = c * (1.0 + 0.1 * rng.uniform(-1, 1, rows))[:, None]
-        env += a / (1.0 + ((k[None, :] - centre) / bw) ** 2)
-    return 1e-3 * env ** 2 + 1e-9
-
-
 def y_lengths(fs, nf):
     return np.array([int((int(n) - 1) * FP / 1000.0 * fs) + 1 for n in nf], dtype=np.int32)
 
@@ -109,35 +96,11 @@ def dense(parts, nf, cols):
 
 
 # ---- a backend: the C calls on arrays that live where the library wants them -----------------------------------------------
-class Backend:
-    """Here device memory is host memory; the GPU suite overrides dev / host / addr / fresh with torch tensors."""
-
-    def __init__(self, lib, ctx):
-        self.lib, self.ctx = lib, ctx
+class Backend(backends.Backend):
+    """the records calls on the arrays of backends.Backend, every one of them float64"""
 
     def dev(self, a):
-        return np.ascontiguousarray(a, dtype=np.float64).copy()
-
-    def host(self, d):
-        return d
-
-    def addr(self, d):
-        return d.ctypes.data
-
-    def ptr(self, d, doubles=0):
-        return C.c_void_p(self.addr(d) + 8 * doubles) if d is not None else None
-
-    def error(self):
-        return self.lib.world_hip_last_error().decode()
-
-    @contextlib.contextmanager
-    def fresh(self):
-        c = self.lib.world_hip_create(0, None)
-        assert c
-        try:
-            yield type(self)(self.lib, c)
-        finally:
-            self.lib.world_hip_destroy(c)
+        return super().dev(np.asarray(a, dtype=np.float64))
 
     def records(self, fs, fft, nf, block, wire, ndim, first_row=FIRST_ROW, cols=None, yl=None, d_block=True):
         """world_hip_synthesis_records -> (rc, y [B, Y]); y starts as zeros"""
@@ -190,19 +153,7 @@ class Backend:
         assert self.lib.world_hip_set_synthesis_pulse_capacity(self.ctx, n) == 0, self.error()
 
 
-@pytest.fixture(scope="module")
-def lib():
-    subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    from world_amd.api import load_library
-    return load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
-
-
-@pytest.fixture(scope="module")
-def be(lib):
-    c = lib.world_hip_create(0, None)
-    assert c
-    yield Backend(lib, c)
-    lib.world_hip_destroy(c)
+be = cpu_backend(Backend)
 
 
 # ---- the three-step routes ------------------------------------------------------------------------------------------------

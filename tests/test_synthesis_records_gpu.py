@@ -2,9 +2,6 @@
 world_hip_realtime_add_coded): the cases of test_synthesis_records_cpu.py through the shipped library -- the reference's
 own decoders and Synthesis (oracle/_ref) as the yardstick where they were built, the port otherwise -- graph replay and the
 command-line tool."""
-import contextlib
-import ctypes as C
-import os
 import subprocess
 import sys
 import wave
@@ -13,49 +10,16 @@ import numpy as np
 import pytest
 
 import test_synthesis_records_cpu as cpu
+from backends import ROOT, OnGpu, gpu_backend, wh  # noqa: F401 (wh: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+class GpuBackend(OnGpu, cpu.Backend):
+    pass
 
 
-class GpuBackend(cpu.Backend):
-    def __init__(self, wh):
-        super().__init__(wh.lib, wh._context())
-
-    def dev(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-    def host(self, d):
-        return d.cpu().numpy()
-
-    def addr(self, d):
-        return d.data_ptr()
-
-    @contextlib.contextmanager
-    def fresh(self):
-        from world_amd.api import WorldHip
-        w = WorldHip()
-        try:
-            yield GpuBackend(w)
-        finally:
-            w.close()
-
-
-@pytest.fixture(scope="module")
-def wh():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from world_amd.api import WorldHip
-    w = WorldHip()
-    yield w
-    w.close()
-
-
-@pytest.fixture(scope="module")
-def be(wh):
-    return GpuBackend(wh)
+be = gpu_backend(GpuBackend)
 
 
 @pytest.fixture(scope="module")
