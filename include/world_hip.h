@@ -695,6 +695,84 @@ WORLD_HIP_API int world_hip_mlpg_batch(WorldHipContext *ctx, int n_utt, int dim,
                                        long long var_utt_stride, long long var_row_stride, int precision, double fill,
                                        double *d_out, long long out_utt_stride, long long out_row_stride);
 
+/* Joint-density Gaussian mixture on the device: the acoustic model of classic voice conversion (Stylianou 1998; Kain 1998;
+ * Toda, Black, Tokuda 2007), fitted on aligned joint rows [x, y] and used to turn source rows x into the per-frame means
+ * and variances of y that world_hip_mlpg_batch consumes.  The reference has no such function; THIS COMMENT IS THE RULE.
+ * A model has M mixtures, 1 <= M <= 256, a source part of Dx dimensions, 1 <= Dx <= 128, a target part of Dy dimensions,
+ * 0 <= Dy <= 128, P = Dx + Dy, and the host parameters w[M], mu[M][P], cov[M][P][P]; cov is symmetric and only its lower
+ * triangle is read.
+ *   prepare (host, no GPU).  world_hip_gmm_prepare computes per mixture, in long double, each value rounded once to double:
+ *            the Cholesky factor Sxx = L L'; U = L^-1 (lower triangular); c = ln w - Dx / 2 ln 2 pi - sum ln L_ii;
+ *            A = Syx Sxx^-1 [Dy][Dx]; v = diag(Syy - A Sxy) [Dy]; mu_x and mu_y as they are.  It returns 1, the reason
+ *            naming the mixture, when a weight is not finite and positive, a pivot is not finite and positive, or an entry of
+ *            v is not positive.  `model` takes world_hip_gmm_model_doubles(M, Dx, Dy) doubles (-1 for a refused shape), which
+ *            the caller copies to the device; the layout is the library's (every matrix padded with zeros to the matrix
+ *            unit's 16-wide tiles, so that no padded operand is ever anything but a zero).  world_hip_gmm_model_parts hands
+ *            back the very doubles the device multiplies by: c[M], mux[M][Dx], muy[M][Dy], U[M][Dx][Dx], A[M][Dy][Dx],
+ *            v[M][Dy]; any pointer may be NULL.
+ *   convert (world_hip_gmm_convert).  Per row t of d_x [rows][Dx] and mixture m:
+ *              d = x_t - mu_x (rounded);  z = U d;  q_tm = c_m - 1/2 sum z^2;  e_tm = mu_y + A d;
+ *              q_max = the largest q_tm, m^ the lowest m that attains it;  s = sum over ascending m of exp(q_tm - q_max);
+ *              loglik_t = q_max + ln s;  gamma_tm = exp(q_tm - q_max) / s  (= exp(q_tm - loglik_t), and a distribution
+ *              however far the row lies from every mixture: the largest term of s is 1).
+ *            mode 0 (the mixture, moment-matched): mean = sum over ascending m of gamma e, var = sum of gamma (v + e^2)
+ *            - mean^2.  mode 1 (the single most likely component, Toda's sub-optimum sequence): mean = e of m^, var = v of
+ *            m^.  Each matrix product is a sum over the ascending inner index on the FP64 matrix unit; sum z^2 adds, for
+ *            each j mod 16, the squares in ascending j and then the sixteen partial sums in ascending order.
+ *            d_mean and d_var are [rows][Dy], d_post [rows][M], d_loglik [rows]; each of the four may be NULL.  With
+ *            Dy = 0 d_mean and d_var must be NULL and the call is the E-step of a Dx-dimensional mixture.  With x carrying
+ *            static + delta (+ delta-delta) features d_mean / d_var are world_hip_mlpg_batch's with precision = 0.
+ *            A row's outputs depend on nothing but the row and the model: not on `rows`, the row's position, the strides,
+ *            the launch shape or a graph replay.  A row with an entry that is not finite yields an unspecified row and no
+ *            other row changes.  Doubles beyond a row's extent and rows at or beyond `rows` are never written.
+ *   statistics (world_hip_gmm_accumulate).  With gamma = d_post [rows][M], z = d_z [rows][P] and the shift s = d_shift [M][P]:
+ *              N_m = sum_t gamma_tm;  S1_m = sum_t gamma_tm (z_t - s_m);  G_m = sum_t (gamma_tm (z_t - s_m)) (z_t - s_m)',
+ *            z - s and gamma (z - s) each rounded, every sum one accumulator on the matrix unit that runs over t ascending
+ *            from the first row to the last, whatever the launch shape; G is written full and bit-symmetric.  The shift is
+ *            the mixture's current mean: it keeps the later G / N - delta delta' free of cancellation.  The statistics of
+ *            two shards (under the same shift) add.
+ *   update (host).  world_hip_gmm_update, in long double rounded once: w = N / total_rows, delta = S1 / N, mu = s + delta,
+ *            cov = G / N - delta delta' + reg I.  It returns 1, naming the mixture, when some N_m is below P + 1 (a starved
+ *            component); nothing is written then.
+ *   fit (world_hip_gmm_fit).  n_iter times: prepare (Dx = P, Dy = 0), the model copied up, convert for gamma and loglik,
+ *            accumulate under the shift mu, the statistics copied down, update.  loglik[i] is the mean log-likelihood BEFORE
+ *            update i: the sum of loglik_t over ascending t in long double, divided by rows, rounded once.  It waits for
+ *            the device every iteration and cannot be captured.  On a refusal from prepare or update it returns 1 and leaves
+ *            w, mu, cov as after the last completed iteration.
+ *   init (world_hip_gmm_init).  w = 1 / M; mu_m = row floor((2 m + 1) rows / (2 M)); cov_m = the diagonal of the data's
+ *            global variance: one accumulate with M = 1, gamma = 1 and the shift equal to row 0, then update with reg = 0.
+ * Strides are counted in doubles.  Refused, before any GPU work and with nothing written (1 is returned, the reason is in
+ * world_hip_last_error): a NULL where a pointer is required, M, Dx, Dy, P or rows out of range, a stride shorter than its row,
+ * mode outside {0, 1}, d_mean or d_var given with Dy = 0, an output range that overlaps an input, the model or another
+ * output, reg negative or not finite, n_iter < 1.
+ * _model_doubles / _prepare / _model_parts / _update are host arithmetic and need no GPU.  convert and accumulate: stream
+ * order and errors as the other batched calls.  convert keeps q and gamma, [rows][M] doubles, and m^, [rows] ints, in the
+ * context's workspace (world_hip_workspace_bytes counts it); once the workspace has the size the call neither allocates nor
+ * copies from the host nor waits, and can be captured.  accumulate needs no workspace.
+ * Time (one MI355X; tools/gmm_bench.py; 10^5 rows, Dx = Dy = 50, M = 64): convert 6.6 ms in either mode; on the joint rows
+ * (P = 100) the E-step 6.8 ms, accumulate 15.1 ms, one iteration of fit 77 ms by the wall clock, most of it the host's
+ * long-double prepare and update and the copies. */
+WORLD_HIP_API long long world_hip_gmm_model_doubles(int M, int Dx, int Dy);
+WORLD_HIP_API int world_hip_gmm_prepare(int M, int Dx, int Dy, const double *w, const double *mu, const double *cov,
+                                        double *model /* host */);
+WORLD_HIP_API int world_hip_gmm_model_parts(int M, int Dx, int Dy, const double *model /* host */, double *c, double *mux,
+                                            double *muy, double *U, double *A, double *v);
+WORLD_HIP_API int world_hip_gmm_convert(WorldHipContext *ctx, int M, int Dx, int Dy, const double *d_model, int rows,
+                                        const double *d_x, long long x_row_stride, int mode, double *d_mean,
+                                        long long mean_row_stride, double *d_var, long long var_row_stride, double *d_post,
+                                        long long post_row_stride, double *d_loglik);
+WORLD_HIP_API int world_hip_gmm_accumulate(WorldHipContext *ctx, int M, int P, int rows, const double *d_z,
+                                           long long z_row_stride, const double *d_post, long long post_row_stride,
+                                           const double *d_shift /* [M][P] */, double *d_N /* [M] */, double *d_S1 /* [M][P] */,
+                                           double *d_G /* [M][P][P] */);
+WORLD_HIP_API int world_hip_gmm_update(int M, int P, const double *N, const double *S1, const double *G, const double *shift,
+                                       double total_rows, double reg, double *w, double *mu, double *cov);
+WORLD_HIP_API int world_hip_gmm_fit(WorldHipContext *ctx, int M, int P, int rows, const double *d_z, long long z_row_stride,
+                                    int n_iter, double reg, double *w, double *mu, double *cov /* host, in-out */,
+                                    double *loglik /* host, [n_iter] or NULL */);
+WORLD_HIP_API int world_hip_gmm_init(WorldHipContext *ctx, int M, int P, int rows, const double *d_z, long long z_row_stride,
+                                     double *w, double *mu, double *cov /* host, out */);
+
 /* Coders on dense device rows (reference src/codec.cpp:217-324).  Rows are independent:
  *   spectrogram / aperiodicity  [rows][fft_size/2+1]
  *   coded spectral envelope     [rows][number_of_dimensions]

@@ -407,6 +407,17 @@ def load_library(path=LIB_PATH):
                                               vp, ll, ll]
         lib.world_hip_mlpg_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, _ip, vp, ll, vp, ll, ll, vp, ll, ll,
                                              C.c_int, C.c_double, vp, ll, ll]
+    if hasattr(lib, "world_hip_gmm_convert"):                        # (likewise)
+        ll, i, d = C.c_longlong, C.c_int, C.c_double
+        lib.world_hip_gmm_model_doubles.argtypes = [i, i, i]
+        lib.world_hip_gmm_model_doubles.restype = ll
+        lib.world_hip_gmm_prepare.argtypes = [i, i, i, vp, vp, vp, vp]
+        lib.world_hip_gmm_model_parts.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp]
+        lib.world_hip_gmm_convert.argtypes = [vp, i, i, i, vp, i, vp, ll, i, vp, ll, vp, ll, vp, ll, vp]
+        lib.world_hip_gmm_accumulate.argtypes = [vp, i, i, i, vp, ll, vp, ll, vp, vp, vp, vp]
+        lib.world_hip_gmm_update.argtypes = [i, i, vp, vp, vp, vp, d, d, vp, vp, vp]
+        lib.world_hip_gmm_fit.argtypes = [vp, i, i, i, vp, ll, i, d, vp, vp, vp, vp]
+        lib.world_hip_gmm_init.argtypes = [vp, i, i, i, vp, ll, vp, vp, vp]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -631,6 +642,43 @@ class HostAPI:
         self.lib.DecodeSpectralEnvelope(_rows(coded), coded.shape[0], fs, fft_size, coded.shape[1], _rows(out))
         return out
 
+    # ---- the Gaussian mixture's host arithmetic (include/world_hip.h: world_hip_gmm_prepare / _model_parts / _update) ----
+    def _gmm(self, name, *args):
+        fn = getattr(self.lib, name)
+        fn.argtypes = [C.c_double if isinstance(a, float) else C.c_int if isinstance(a, int) else C.c_void_p for a in args]
+        fn.restype = C.c_longlong if name.endswith("_doubles") else C.c_int
+        return fn(*(a if isinstance(a, (int, float)) or a is None else a.ctypes.data for a in args))
+
+    def _gmm_check(self, rc, what):
+        if rc != 0:
+            self.lib.world_hip_last_error.restype = C.c_char_p
+            raise RuntimeError(f"{what}: {self.lib.world_hip_last_error().decode()}")
+
+    def gmm_prepare(self, w, mu, cov, dx):
+        """w [M], mu [M][P], cov [M][P][P], the source dimension -> the prepared model's doubles (the library's layout)"""
+        w, mu, cov = _f64(w), _f64(mu), _f64(cov)
+        M, P = (int(v) for v in mu.shape)
+        n = self._gmm("world_hip_gmm_model_doubles", M, int(dx), P - int(dx))
+        self._gmm_check(int(n < 0), "gmm_prepare")
+        model = np.empty(n, dtype=np.float64)
+        self._gmm_check(self._gmm("world_hip_gmm_prepare", M, int(dx), P - int(dx), w, mu, cov, model), "gmm_prepare")
+        return model
+
+    def gmm_model_parts(self, M, dx, dy, model):
+        """-> {"c" [M], "mux" [M][dx], "muy" [M][dy], "U" [M][dx][dx], "A" [M][dy][dx], "v" [M][dy]}: what the device multiplies by"""
+        out = dict(c=np.empty(M), mux=np.empty((M, dx)), muy=np.empty((M, dy)), U=np.empty((M, dx, dx)), A=np.empty((M, dy, dx)),
+                   v=np.empty((M, dy)))
+        self._gmm_check(self._gmm("world_hip_gmm_model_parts", int(M), int(dx), int(dy), _f64(model), *out.values()), "gmm_model_parts")
+        return out
+
+    def gmm_update(self, N, S1, G, shift, total_rows, reg=0.0):
+        """the M-step's finish on the statistics of world_hip_gmm_accumulate -> (w, mu, cov)"""
+        N, S1, G, shift = _f64(N), _f64(S1), _f64(G), _f64(shift)
+        M, P = (int(v) for v in S1.shape)
+        w, mu, cov = np.empty(M), np.empty((M, P)), np.empty((M, P, P))
+        self._gmm_check(self._gmm("world_hip_gmm_update", M, P, N, S1, G, shift, float(total_rows), float(reg), w, mu, cov), "gmm_update")
+        return w, mu, cov
+
 
 class FileAPI:
     """numpy binding of the reference's tools/ library (tools/audioio.h, tools/parameterio.h;
@@ -709,6 +757,14 @@ class FileAPI:
 
     def read_aperiodicity(self, path):
         return self._read_matrix(self.lib.ReadAperiodicity, path)
+
+
+class GmmModel:
+    """a prepared joint-density mixture on the device (WorldHip.gmm_prepare): M mixtures, dx source and dy target
+    dimensions, `data` the model's doubles in the library's layout"""
+
+    def __init__(self, M, dx, dy, data):
+        self.M, self.dx, self.dy, self.data = M, dx, dy, data
 
 
 class Graph:
@@ -1743,6 +1799,97 @@ class WorldHip:
         mean [U][T][n_win D] (or [T][n_win D]); var of the same shape, [U][1][n_win D] or [U][n_win D] (one row per
         utterance) or [n_win D] (one global row); precision=True: var holds 1 / variance.  Returns [U][T][D] (or [T][D])."""
         return self._mlpg_call(True, mean, var, windows, mask, n_frames, precision, fill, out)
+
+    # ---- joint-density Gaussian mixture (include/world_hip.h: world_hip_gmm_*) ----
+    GMM_MODES = {"mixture": 0, "hard": 1}
+
+    def _gmm_lib(self):
+        if not hasattr(self.lib, "world_hip_gmm_convert"):
+            raise RuntimeError("this libworld_hip.so has no Gaussian mixture (world_hip_gmm_convert)")
+        return self.lib
+
+    def _gmm_rows(self, x, cols, what):
+        """a [rows][cols] float64 tensor or view on the device with adjacent columns -> (rows, row stride in doubles)"""
+        t = self.torch
+        assert x.dtype == t.float64 and x.is_cuda and x.device == self.device and x.dim() == 2 and x.shape[1] == cols and \
+            (cols == 1 or x.stride(1) == 1), f"{what}: [rows][{cols}] float64 on {self.device} with adjacent columns"
+        rows = int(x.shape[0])
+        return rows, (int(x.stride(0)) if rows > 1 else max(int(x.stride(0)), cols))
+
+    def gmm_prepare(self, w, mu, cov, dx):
+        """host parameters w [M], mu [M][P], cov [M][P][P] (the lower triangle is read) and the source dimension dx -> the
+        prepared model on the device (a GmmModel: .M, .dx, .dy, .data).  Host arithmetic and one copy."""
+        lib = self._gmm_lib()
+        w, mu, cov = _f64(w), _f64(mu), _f64(cov)
+        M, P = (int(v) for v in mu.shape)
+        dx = int(dx)
+        if w.shape != (M,) or cov.shape != (M, P, P) or not 1 <= dx <= P:
+            raise ValueError(f"gmm_prepare: w [{M}], mu [{M}][{P}], cov [{M}][{P}][{P}] and 1 <= dx <= {P}")
+        n = int(lib.world_hip_gmm_model_doubles(M, dx, P - dx))
+        if n < 0:
+            raise RuntimeError("gmm_prepare: " + lib.world_hip_last_error().decode())
+        host = np.empty(n, dtype=np.float64)
+        self._check(lib.world_hip_gmm_prepare(M, dx, P - dx, w.ctypes.data, mu.ctypes.data, cov.ctypes.data, host.ctypes.data), "gmm_prepare")
+        with self.torch.cuda.device(self.device):
+            return GmmModel(M, dx, P - dx, self.torch.from_numpy(host).to(self.device))
+
+    def _gmm_convert(self, model, x, mode, mean, var, post, loglik):
+        rows, x_rs = self._gmm_rows(x, model.dx, "gmm: x")
+        ptr = lambda a: None if a is None else a.data_ptr()
+        rs = lambda a, c: 0 if a is None else self._gmm_rows(a, c, "gmm: out")[1]
+        for a, c in ((mean, model.dy), (var, model.dy), (post, model.M)):
+            assert a is None or a.shape[0] == rows, f"gmm: an output of {rows} rows"
+        assert loglik is None or (loglik.dtype == self.torch.float64 and loglik.is_contiguous() and tuple(loglik.shape) == (rows,))
+        self._check(self.lib.world_hip_gmm_convert(self._context(), model.M, model.dx, model.dy, model.data.data_ptr(), rows, x.data_ptr(), x_rs,
+                                                   mode, ptr(mean), rs(mean, model.dy), ptr(var), rs(var, model.dy), ptr(post),
+                                                   rs(post, model.M), ptr(loglik)), "gmm_convert")
+
+    def gmm_convert(self, model, x, mode="mixture", out=None):
+        """source rows x [rows][dx] (float64 on the device; a view with a row stride is read where it lies) -> the per-row
+        (mean, var) [rows][dy] of the target under the model: mode "mixture" moment-matches the conditional mixture,
+        "hard" takes the most likely component.  out: a (mean, var) pair of [rows][dy] tensors or views of the caller's.
+        With x = [static, delta, ...] features the pair is what mlpg() consumes."""
+        self._gmm_lib()
+        if mode not in self.GMM_MODES:
+            raise ValueError(f"gmm_convert: mode {mode!r} is neither 'mixture' nor 'hard'")
+        if model.dy == 0:
+            raise ValueError("gmm_convert: the model has no target part")
+        t = self.torch
+        if out is None:
+            out = tuple(t.empty((int(x.shape[0]), model.dy), dtype=t.float64, device=x.device) for _ in range(2))
+        mean, var = out
+        self._gmm_convert(model, x, self.GMM_MODES[mode], mean, var, None, None)
+        return mean, var
+
+    def gmm_posterior(self, model, x):
+        """-> (the responsibilities [rows][M], the log-likelihood [rows]) of the rows' source part under the model"""
+        self._gmm_lib()
+        t = self.torch
+        rows = int(x.shape[0])
+        post, loglik = t.empty((rows, model.M), dtype=t.float64, device=x.device), t.empty(rows, dtype=t.float64, device=x.device)
+        self._gmm_convert(model, x, 0, None, None, post, loglik)
+        return post, loglik
+
+    def gmm_fit(self, z, n_mix, n_iter=20, reg=1e-6, init=None):
+        """EM for a full-covariance mixture of n_mix components on the rows z [rows][P] (float64 on the device, strides
+        honoured).  init: a (w, mu, cov) start (host arrays); None: world_hip_gmm_init's (means spread over the rows, the
+        data's diagonal variance).  Returns host arrays (w [M], mu [M][P], cov [M][P][P], loglik [n_iter]: the mean
+        log-likelihood before each update).  Waits for the device every iteration."""
+        lib = self._gmm_lib()
+        M = int(n_mix)
+        rows, z_rs = self._gmm_rows(z, int(z.shape[1]), "gmm_fit: z")
+        P = int(z.shape[1])
+        if init is None:
+            w, mu, cov = np.empty(M), np.empty((M, P)), np.empty((M, P, P))
+            self._check(lib.world_hip_gmm_init(self._context(), M, P, rows, z.data_ptr(), z_rs, w.ctypes.data, mu.ctypes.data, cov.ctypes.data), "gmm_init")
+        else:
+            w, mu, cov = (np.array(a, dtype=np.float64, order="C") for a in init)
+            if w.shape != (M,) or mu.shape != (M, P) or cov.shape != (M, P, P):
+                raise ValueError(f"gmm_fit: init must be w [{M}], mu [{M}][{P}], cov [{M}][{P}][{P}]")
+        loglik = np.empty(int(n_iter), dtype=np.float64)
+        self._check(lib.world_hip_gmm_fit(self._context(), M, P, rows, z.data_ptr(), z_rs, int(n_iter), float(reg), w.ctypes.data, mu.ctypes.data,
+                                          cov.ctypes.data, loglik.ctypes.data), "gmm_fit")
+        return w, mu, cov, loglik
 
     def probe_machine(self):
         """world_hip_probe_machine (include/world_hip.h): ~50 ms of microbenchmarks that characterise the box"""

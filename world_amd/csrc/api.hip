@@ -29,6 +29,7 @@
 #include "dio.h"
 #include "exchange.h"
 #include "fft_probe.h"
+#include "gmm_host.h"
 #include "machine_probe.h"
 #include "mcep_host.h"
 #include "resample.h"
@@ -2202,6 +2203,166 @@ static void run_mlpg(WorldHipContext *c, int n_utt, int dim, int n_win, int half
                     var_us, var_rs, precision, fill, d_out, out_us, out_rs);
 }
 
+// Joint-density Gaussian mixture (include/world_hip.h: world_hip_gmm_convert / _accumulate / _fit / _init; gmm.inc).  The
+// host arithmetic -- the prepared model, the M-step's finish -- is gmm_host.h's.  q and gamma [rows][M] and the best mixture
+// [rows] are the conversion's workspace.
+static void run_gmm_convert(WorldHipContext *c, int M, int Dx, int Dy, const double *d_model, int rows, const double *d_x,
+                            long long x_rs, int mode, double *d_mean, long long mean_rs, double *d_var, long long var_rs,
+                            double *d_post, long long post_rs, double *d_loglik) {
+  if (const char *why = gmm_shape(M, Dx, Dy)) fail("gmm_convert: %s", why);
+  if (rows < 1) fail("gmm_convert: rows must be positive");
+  if (!d_model || !d_x) fail("gmm_convert: null d_model / d_x");
+  if (mode != 0 && mode != 1) fail("gmm_convert: mode %d is neither 0 (mixture) nor 1 (most likely component)", mode);
+  if (Dy == 0 && (d_mean || d_var)) fail("gmm_convert: d_mean / d_var given, but the model has no target part (Dy = 0)");
+  if (x_rs < Dx) fail("gmm_convert: x_row_stride %lld below the row's %d doubles", x_rs, Dx);
+  if (d_mean && mean_rs < Dy) fail("gmm_convert: mean_row_stride %lld below the row's %d doubles", mean_rs, Dy);
+  if (d_var && var_rs < Dy) fail("gmm_convert: var_row_stride %lld below the row's %d doubles", var_rs, Dy);
+  if (d_post && post_rs < M) fail("gmm_convert: post_row_stride %lld below the row's %d doubles", post_rs, M);
+  const GmmLayout g = gmm_layout(M, Dx, Dy);
+  const size_t r1 = (size_t)rows - 1;
+  refuse_overlap("gmm_convert",
+                 {{d_mean, sizeof(double) * (r1 * mean_rs + Dy), "d_mean"}, {d_var, sizeof(double) * (r1 * var_rs + Dy), "d_var"},
+                  {d_post, sizeof(double) * (r1 * post_rs + M), "d_post"}, {d_loglik, sizeof(double) * (size_t)rows, "d_loglik"}},
+                 {{d_x, sizeof(double) * (r1 * x_rs + Dx), "d_x"}, {d_model, sizeof(double) * g.doubles, "d_model"}});
+  GmmParams p;
+  begin_stage(c, [&](Arena &a) {
+    p.q = a.take<double>((size_t)rows * M);
+    p.best = a.take<int>((size_t)rows);
+  });
+  p.x = d_x; p.model = d_model;
+  p.x_rs = x_rs; p.mean_rs = mean_rs; p.var_rs = var_rs; p.post_rs = post_rs;
+  p.off_c = g.c; p.off_mux = g.mux; p.off_muy = g.muy; p.off_v = g.v; p.off_ut = g.ut; p.off_at = g.at;
+  p.mean = d_mean; p.var = d_var; p.post = d_post; p.loglik = d_loglik;
+  p.rows = rows; p.M = M; p.Dx = Dx; p.Dy = Dy; p.Kp = g.Kp; p.Ep = g.Ep; p.mode = mode;
+  launch_gmm_q(p, c->stream);
+  launch_gmm_posterior(p, c->stream);
+  if (d_mean || d_var) launch_gmm_regress(p, c->stream);
+}
+
+static void check_gmm_rows(const char *name, int M, int P, int rows, const double *d_z, long long z_rs) {
+  if (M < 1 || M > kGmmMaxMix) fail("%s: the number of mixtures must lie in [1, %d]", name, kGmmMaxMix);
+  if (P < 1 || P > kGmmMaxDim) fail("%s: the dimension must lie in [1, %d]", name, kGmmMaxDim);
+  if (rows < 1) fail("%s: rows must be positive", name);
+  if (!d_z) fail("%s: null d_z", name);
+  if (z_rs < P) fail("%s: z_row_stride %lld below the row's %d doubles", name, z_rs, P);
+}
+
+static void run_gmm_accumulate(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_rs,
+                               const double *d_post, long long post_rs, const double *d_shift, double *d_N, double *d_S1,
+                               double *d_G) {
+  check_gmm_rows("gmm_accumulate", M, P, rows, d_z, z_rs);
+  if (!d_post || !d_shift || !d_N || !d_S1 || !d_G) fail("gmm_accumulate: null d_post / d_shift / d_N / d_S1 / d_G");
+  if (post_rs < M) fail("gmm_accumulate: post_row_stride %lld below the row's %d doubles", post_rs, M);
+  const size_t r1 = (size_t)rows - 1, mp = (size_t)M * P;
+  refuse_overlap("gmm_accumulate",
+                 {{d_N, sizeof(double) * (size_t)M, "d_N"}, {d_S1, sizeof(double) * mp, "d_S1"}, {d_G, sizeof(double) * mp * P, "d_G"}},
+                 {{d_z, sizeof(double) * (r1 * z_rs + P), "d_z"}, {d_post, sizeof(double) * (r1 * post_rs + M), "d_post"},
+                  {d_shift, sizeof(double) * mp, "d_shift"}});
+  GmmAccParams p;
+  p.z = d_z; p.post = d_post; p.shift = d_shift; p.z_rs = z_rs; p.post_rs = post_rs;
+  p.N = d_N; p.S1 = d_S1; p.G = d_G; p.rows = rows; p.M = M; p.P = P;
+  launch_gmm_accumulate(p, c->stream);
+}
+
+static void check_gmm_host(const char *name, const double *w, const double *mu, const double *cov) {
+  if (!w || !mu || !cov) fail("%s: null w / mu / cov", name);
+}
+
+// The statistics of one set of rows on the host: N [M], S1 [M][P], G [M][P][P] (accumulate, then copied down; waits).
+struct GmmStats { std::vector<double> N, S1, G; };
+struct GmmDeviceStats { double *N, *S1, *G; };
+static void gmm_stats_down(WorldHipContext *c, int M, int P, const GmmDeviceStats &d, GmmStats *h) {
+  const size_t mp = (size_t)M * P;
+  h->N.resize(M); h->S1.resize(mp); h->G.resize(mp * P);
+  devrt::d2h(h->N.data(), d.N, sizeof(double) * M, c->stream);
+  devrt::d2h(h->S1.data(), d.S1, sizeof(double) * mp, c->stream);
+  devrt::d2h(h->G.data(), d.G, sizeof(double) * mp * P, c->stream);
+  devrt::sync(c->stream);
+}
+
+static void run_gmm_fit(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_rs, int n_iter, double reg,
+                        double *w, double *mu, double *cov, double *loglik) {
+  check_gmm_rows("gmm_fit", M, P, rows, d_z, z_rs);
+  check_gmm_host("gmm_fit", w, mu, cov);
+  if (n_iter < 1) fail("gmm_fit: n_iter must be positive");
+  if (!std::isfinite(reg) || reg < 0) fail("gmm_fit: reg must be finite and not negative");
+  if (devrt::is_capturing(c->stream)) fail("gmm_fit: the fit waits for the device every iteration and cannot be captured");
+  const GmmLayout g = gmm_layout(M, P, 0);
+  const size_t mp = (size_t)M * P;
+  double *d_model = nullptr, *d_post = nullptr, *d_ll = nullptr, *d_shift = nullptr;
+  GmmDeviceStats ds{nullptr, nullptr, nullptr};
+  std::vector<double> model(g.doubles), ll(rows), w2(M), mu2(mp), cov2(mp * P);
+  GmmStats hs;
+  hold_at_floor(
+      c, "gmm_fit",
+      [&](Arena &a) {
+        d_model = a.take<double>(g.doubles);
+        d_post = a.take<double>((size_t)rows * M);
+        d_ll = a.take<double>((size_t)rows);
+        d_shift = a.take<double>(mp);
+        ds.N = a.take<double>((size_t)M);
+        ds.S1 = a.take<double>(mp);
+        ds.G = a.take<double>(mp * P);
+      },
+      [&] {
+        for (int it = 0; it < n_iter; ++it) {
+          const std::string why = gmm_prepare_host(M, P, 0, w, mu, cov, model.data());
+          if (!why.empty()) fail("gmm_fit: iteration %d: %s", it, why.c_str());
+          devrt::h2d(d_model, model.data(), sizeof(double) * g.doubles, c->stream);
+          devrt::h2d(d_shift, mu, sizeof(double) * mp, c->stream);
+          run_gmm_convert(c, M, P, 0, d_model, rows, d_z, z_rs, 0, nullptr, 0, nullptr, 0, d_post, M, d_ll);
+          run_gmm_accumulate(c, M, P, rows, d_z, z_rs, d_post, M, d_shift, ds.N, ds.S1, ds.G);
+          devrt::d2h(ll.data(), d_ll, sizeof(double) * rows, c->stream);
+          gmm_stats_down(c, M, P, ds, &hs);
+          long double sum = 0;
+          for (int t = 0; t < rows; ++t) sum += ll[t];
+          const std::string starved = gmm_update_host(M, P, hs.N.data(), hs.S1.data(), hs.G.data(), mu, (double)rows, reg,
+                                                      w2.data(), mu2.data(), cov2.data());
+          if (!starved.empty()) fail("gmm_fit: iteration %d: %s", it, starved.c_str());
+          if (loglik) loglik[it] = (double)(sum / rows);
+          std::copy(w2.begin(), w2.end(), w);
+          std::copy(mu2.begin(), mu2.end(), mu);
+          std::copy(cov2.begin(), cov2.end(), cov);
+        }
+      });
+}
+
+static void run_gmm_init(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_rs, double *w, double *mu,
+                         double *cov) {
+  check_gmm_rows("gmm_init", M, P, rows, d_z, z_rs);
+  check_gmm_host("gmm_init", w, mu, cov);
+  if (devrt::is_capturing(c->stream)) fail("gmm_init: the call waits for the device and cannot be captured");
+  const size_t p = (size_t)P;
+  double *d_ones = nullptr;
+  GmmDeviceStats ds{nullptr, nullptr, nullptr};
+  begin_stage(c, [&](Arena &a) {
+    d_ones = a.take<double>((size_t)rows);
+    ds.N = a.take<double>(1);
+    ds.S1 = a.take<double>(p);
+    ds.G = a.take<double>(p * p);
+  });
+  launch_gmm_fill(d_ones, (size_t)rows, 1.0, c->stream);
+  run_gmm_accumulate(c, 1, P, rows, d_z, z_rs, d_ones, 1, d_z, ds.N, ds.S1, ds.G);   // (the shift: row 0 where it lies)
+  GmmStats hs;
+  std::vector<double> row0(p), centre((size_t)M * p), w1(1), mu1(p), cov1(p * p);
+  devrt::d2h(row0.data(), d_z, sizeof(double) * p, c->stream);
+  for (int m = 0; m < M; ++m) {
+    const long long t = (2LL * m + 1) * rows / (2LL * M);
+    devrt::d2h(centre.data() + (size_t)m * p, d_z + (size_t)t * z_rs, sizeof(double) * p, c->stream);
+  }
+  gmm_stats_down(c, 1, P, ds, &hs);
+  const std::string why = gmm_update_host(1, P, hs.N.data(), hs.S1.data(), hs.G.data(), row0.data(), (double)rows, 0.0, w1.data(),
+                                          mu1.data(), cov1.data());
+  if (!why.empty()) fail("gmm_init: %d rows are too few for %d dimensions", rows, P);
+  for (int m = 0; m < M; ++m) {
+    w[m] = 1.0 / M;
+    for (size_t i = 0; i < p; ++i) {
+      mu[(size_t)m * p + i] = centre[(size_t)m * p + i];
+      for (size_t j = 0; j < p; ++j) cov[((size_t)m * p + i) * p + j] = i == j ? cov1[i * p + i] : 0.0;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -2955,6 +3116,73 @@ int world_hip_mlpg_batch(WorldHipContext *c, int n_utt, int dim, int n_win, int 
     run_mlpg(c, n_utt, dim, n_win, half_width, win, n_frames, d_mask, mask_utt_stride, d_mean, mean_utt_stride,
              mean_row_stride, d_var, var_utt_stride, var_row_stride, precision, fill, d_out, out_utt_stride, out_row_stride);
   });
+}
+// the host calls of the mixture: 0, or 1 with the reason in world_hip_last_error
+static int gmm_host_call(const std::string &why) {
+  if (why.empty()) return 0;
+  g_last_error = why;
+  return 1;
+}
+long long world_hip_gmm_model_doubles(int M, int Dx, int Dy) {
+  if (const char *why = gmm_shape(M, Dx, Dy)) { g_last_error = std::string("gmm: ") + why; return -1; }
+  return (long long)gmm_layout(M, Dx, Dy).doubles;
+}
+int world_hip_gmm_prepare(int M, int Dx, int Dy, const double *w, const double *mu, const double *cov, double *model) {
+  if (const char *why = gmm_shape(M, Dx, Dy)) return gmm_host_call(std::string("gmm_prepare: ") + why);
+  if (!w || !mu || !cov || !model) return gmm_host_call("gmm_prepare: null w / mu / cov / model");
+  const std::string why = gmm_prepare_host(M, Dx, Dy, w, mu, cov, model);
+  return gmm_host_call(why.empty() ? why : "gmm_prepare: " + why);
+}
+int world_hip_gmm_model_parts(int M, int Dx, int Dy, const double *model, double *c, double *mux, double *muy, double *U,
+                              double *A, double *v) {
+  if (const char *why = gmm_shape(M, Dx, Dy)) return gmm_host_call(std::string("gmm_model_parts: ") + why);
+  if (!model) return gmm_host_call("gmm_model_parts: null model");
+  const GmmLayout g = gmm_layout(M, Dx, Dy);
+  for (int m = 0; m < M; ++m) {
+    if (c) c[m] = model[g.c + m];
+    for (int k = 0; k < Dx; ++k) {
+      if (mux) mux[(size_t)m * Dx + k] = model[g.mux + (size_t)m * g.Kp + k];
+      for (int j = 0; j < Dx; ++j)
+        if (U) U[((size_t)m * Dx + j) * Dx + k] = model[g.ut + ((size_t)m * g.Kp + k) * g.Kp + j];
+      for (int i = 0; i < Dy; ++i)
+        if (A) A[((size_t)m * Dy + i) * Dx + k] = model[g.at + ((size_t)m * g.Kp + k) * g.Ep + i];
+    }
+    for (int i = 0; i < Dy; ++i) {
+      if (muy) muy[(size_t)m * Dy + i] = model[g.muy + (size_t)m * g.Ep + i];
+      if (v) v[(size_t)m * Dy + i] = model[g.v + (size_t)m * g.Ep + i];
+    }
+  }
+  return 0;
+}
+int world_hip_gmm_update(int M, int P, const double *N, const double *S1, const double *G, const double *shift,
+                         double total_rows, double reg, double *w, double *mu, double *cov) {
+  if (M < 1 || M > kGmmMaxMix || P < 1 || P > kGmmMaxDim) return gmm_host_call("gmm_update: M or P out of range");
+  if (!N || !S1 || !G || !shift || !w || !mu || !cov) return gmm_host_call("gmm_update: null N / S1 / G / shift / w / mu / cov");
+  if (!std::isfinite(reg) || reg < 0) return gmm_host_call("gmm_update: reg must be finite and not negative");
+  if (!std::isfinite(total_rows) || !(total_rows > 0)) return gmm_host_call("gmm_update: total_rows must be finite and positive");
+  const std::string why = gmm_update_host(M, P, N, S1, G, shift, total_rows, reg, w, mu, cov);
+  return gmm_host_call(why.empty() ? why : "gmm_update: " + why);
+}
+int world_hip_gmm_convert(WorldHipContext *c, int M, int Dx, int Dy, const double *d_model, int rows, const double *d_x,
+                          long long x_row_stride, int mode, double *d_mean, long long mean_row_stride, double *d_var,
+                          long long var_row_stride, double *d_post, long long post_row_stride, double *d_loglik) {
+  return guarded(c, [&] {
+    run_gmm_convert(c, M, Dx, Dy, d_model, rows, d_x, x_row_stride, mode, d_mean, mean_row_stride, d_var, var_row_stride, d_post,
+                    post_row_stride, d_loglik);
+  });
+}
+int world_hip_gmm_accumulate(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_row_stride,
+                             const double *d_post, long long post_row_stride, const double *d_shift, double *d_N, double *d_S1,
+                             double *d_G) {
+  return guarded(c, [&] { run_gmm_accumulate(c, M, P, rows, d_z, z_row_stride, d_post, post_row_stride, d_shift, d_N, d_S1, d_G); });
+}
+int world_hip_gmm_fit(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_row_stride, int n_iter,
+                      double reg, double *w, double *mu, double *cov, double *loglik) {
+  return guarded(c, [&] { run_gmm_fit(c, M, P, rows, d_z, z_row_stride, n_iter, reg, w, mu, cov, loglik); });
+}
+int world_hip_gmm_init(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_row_stride, double *w,
+                       double *mu, double *cov) {
+  return guarded(c, [&] { run_gmm_init(c, M, P, rows, d_z, z_row_stride, w, mu, cov); });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||

@@ -202,4 +202,32 @@ size_t mlpg_workspace_doubles(int n_utt, int dim, int max_frames, int half_width
 void launch_delta(const MlpgParams &p, int half_width, int n_utt, int max_frames, hipStream_t stream);
 void launch_mlpg(const MlpgParams &p, int half_width, int n_utt, int max_frames, hipStream_t stream);
 
+// Joint-density Gaussian mixture (world_hip_gmm_convert / world_hip_gmm_accumulate; gmm.inc).  `model` is the prepared
+// model on the device (gmm_host.h: GmmLayout; the offsets below are its), Kp and Ep the source and target dimensions padded
+// to 16.  gmm_q writes q [rows][M], gmm_posterior turns it into gamma in place and finds the most likely mixture, gmm_regress
+// reads both.  Strides are counted in doubles.
+constexpr int kGmmMaxPad = 128;     // the largest padded dimension
+struct GmmParams {
+  const double *x;
+  const double *model;
+  long long x_rs, mean_rs, var_rs, post_rs;
+  size_t off_c, off_mux, off_muy, off_v, off_ut, off_at;
+  double *q;                      // workspace [rows][M]: q, then gamma
+  int *best;                      // workspace [rows]: the lowest mixture that attains the largest q
+  double *mean, *var, *post, *loglik;   // outputs, any may be nullptr
+  int rows, M, Dx, Dy, Kp, Ep, mode;
+};
+void launch_gmm_q(const GmmParams &p, hipStream_t stream);
+void launch_gmm_posterior(const GmmParams &p, hipStream_t stream);
+void launch_gmm_regress(const GmmParams &p, hipStream_t stream);
+// N [M], S1 [M][P], G [M][P][P] of rows [0, rows): gamma = post [t][m], the shift [M][P]
+struct GmmAccParams {
+  const double *z, *post, *shift;
+  long long z_rs, post_rs;
+  double *N, *S1, *G;
+  int rows, M, P;
+};
+void launch_gmm_accumulate(const GmmAccParams &p, hipStream_t stream);
+void launch_gmm_fill(double *d, size_t n, double value, hipStream_t stream);
+
 }  // namespace world_hip

@@ -25,8 +25,9 @@
 // The warp's knots depend on each utterance's ratio, so its histc search runs in the kernel instead of a host table.
 // And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end;
 // behind it morph.inc, the frames between two utterances aligned that way (world_hip_morph_batch); and mcep.inc, the
-// all-pass mel-cepstrum of an envelope and back (world_hip_sp2mc / world_hip_mc2sp) on the FP64 matrix unit; last mlpg.inc,
-// dynamic features and the maximum-likelihood trajectory behind them (world_hip_delta_batch / world_hip_mlpg_batch).
+// all-pass mel-cepstrum of an envelope and back (world_hip_sp2mc / world_hip_mc2sp) on the FP64 matrix unit; mlpg.inc,
+// dynamic features and the maximum-likelihood trajectory behind them (world_hip_delta_batch / world_hip_mlpg_batch); last
+// gmm.inc, the joint-density Gaussian mixture between the two (world_hip_gmm_convert / world_hip_gmm_accumulate).
 #include "codec.h"
 #include "fft.h"
 
@@ -454,5 +455,6 @@ void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) 
 #include "morph.inc"
 #include "mcep.inc"
 #include "mlpg.inc"
+#include "gmm.inc"
 
 }  // namespace world_hip

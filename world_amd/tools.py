@@ -18,6 +18,8 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools mcd ref.wav test.wav --mcep 24                      # MCD on all-pass mel-cepstra c1 .. c24
     python -m world_amd.tools deltas a.mgc --dim 60 -o a.mgc.dyn                  # [frames][60] -> [frames][180]: static, delta, delta-delta
     python -m world_amd.tools mlpg mean.mgc.dyn var.mgc.dyn --dim 60 -o a.mgc     # the smooth trajectory under means and variances
+    python -m world_amd.tools vc-train s1.mgc s2.mgc --target t1.mgc t2.mgc --dim 25 --mix 32 --iter 20 -o model.npz
+    python -m world_amd.tools vc-convert model.npz s3.mgc --dim 25 -o s3_as_t.mgc   # goes into features-synthesis as it is
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
 -q of spanalysis, -t of apanalysis).  Files are grouped by sampling rate; only their PCM bytes
@@ -48,6 +50,10 @@ the alignment itself is unchanged.
 maximum-likelihood parameter generation): a file of [frames][3 dim] means and one of as many rows, or of one row, of
 variances give the [frames][dim] trajectory, which goes into `features-synthesis` as it is.  With --lf0 (dim 1) the -1e10
 frames are masked: windows stop at the ends of every voiced run and unvoiced frames stay -1e10.
+`vc-train` fits the classic joint-density Gaussian mixture of voice conversion (world_hip_gmm_fit) on pairs of .mgc files of
+two speakers: per pair the deltas of both, the DTW alignment of the statics without c0, the joint rows [x, dx, y, dy] along
+the path; all rows of all pairs are fitted together and w, mu, cov and the dimensions saved as .npz.  `vc-convert` turns a
+source .mgc into the target speaker's: deltas, world_hip_gmm_convert (the per-frame means and variances of [y, dy]), mlpg.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
 import argparse
@@ -589,6 +595,58 @@ def _mlpg(a):
     print(f"{len(mean)} frames of {n_win} x {dim} -> {a.o} ([{len(mean)}][{dim}])")
 
 
+VC_WINDOWS = WorldHip.DEFAULT_WINDOWS[:2]   # the conversion model sees [static, delta]
+
+
+def vc_joint_rows(wh, src, tgt):
+    """one pair of utterances' statics [T_a][D], [T_b][D] (float64 on the device) -> the joint rows [x, dx, y, dy] along the
+    DTW path of the statics without c0, [path length][4 D]"""
+    xa, xb = wh.deltas(src, windows=VC_WINDOWS), wh.deltas(tgt, windows=VC_WINDOWS)
+    path, path_len, _, _, _ = wh.align(src[None, :, 1:], tgt[None, :, 1:], [len(src)], [len(tgt)])
+    steps = path[0, :int(path_len[0])].long()
+    import torch
+    return torch.cat([xa[steps[:, 0]], xb[steps[:, 1]]], dim=1)
+
+
+def _vc_train(a):
+    import torch
+    if a.dim < 2 or a.mix < 1 or a.iter < 1 or len(a.src) != len(a.target):
+        sys.exit(f"vc-train: --dim {a.dim} (at least 2: c0 and one more), --mix {a.mix}, --iter {a.iter}, {len(a.src)} source and "
+                 f"{len(a.target)} target files (as many of each)")
+    wh = WorldHip()
+    try:
+        rows = [vc_joint_rows(wh, torch.from_numpy(_float_rows("vc-train", s, a.dim)).to(wh.device),
+                              torch.from_numpy(_float_rows("vc-train", t, a.dim)).to(wh.device)) for s, t in zip(a.src, a.target)]
+        z = torch.cat(rows) if len(rows) > 1 else rows[0]
+        w, mu, cov, loglik = wh.gmm_fit(z, a.mix, n_iter=a.iter, reg=a.reg)
+    except (ValueError, RuntimeError) as e:
+        sys.exit(f"vc-train: {e}")
+    np.savez(a.o, w=w, mu=mu, cov=cov, dim=np.int64(a.dim), dx=np.int64(2 * a.dim), loglik=loglik)
+    print(f"{len(a.src)} pair(s), {len(z)} joint rows of {z.shape[1]} -> {a.o} ({a.mix} mixtures; mean log-likelihood "
+          f"{loglik[0]:.4f} -> {loglik[-1]:.4f})")
+
+
+def _vc_convert(a):
+    import torch
+    try:
+        with np.load(a.model) as f:
+            w, mu, cov, dim, dx = f["w"], f["mu"], f["cov"], int(f["dim"]), int(f["dx"])
+    except (OSError, KeyError, ValueError) as e:
+        sys.exit(f"vc-convert: {a.model}: {e}")
+    if a.dim != dim:
+        sys.exit(f"vc-convert: --dim {a.dim}, but the model was trained on {dim} values per frame")
+    x = _float_rows("vc-convert", a.mgc, dim)
+    wh = WorldHip()
+    try:
+        model = wh.gmm_prepare(w, mu, cov, dx)
+        mean, var = wh.gmm_convert(model, wh.deltas(torch.from_numpy(x).to(wh.device), windows=VC_WINDOWS), mode=a.mode)
+        out = wh.mlpg(mean, var, windows=VC_WINDOWS)
+    except (ValueError, RuntimeError) as e:
+        sys.exit(f"vc-convert: {e}")
+    out.cpu().numpy().astype("<f4").tofile(a.o)
+    print(f"{len(x)} frames of {dim} -> {a.o}")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m world_amd.tools", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="tool", required=True)
@@ -696,6 +754,22 @@ def main(argv=None):
     ml.add_argument("--precision", action="store_true", help="VAR holds 1 / variance")
     ml.add_argument("-o", required=True)
     ml.set_defaults(run=_mlpg)
+    vt = sub.add_parser("vc-train", help="pairs of .mgc files of two speakers -> a joint-density Gaussian mixture (model.npz)")
+    vt.add_argument("src", nargs="+", metavar="SRC.mgc")
+    vt.add_argument("--target", nargs="+", required=True, metavar="TGT.mgc", help="the other speaker's files, in the same order")
+    vt.add_argument("--dim", type=int, required=True, metavar="D", help="values per frame (order + 1)")
+    vt.add_argument("--mix", type=int, default=32, metavar="M", help="mixtures")
+    vt.add_argument("--iter", type=int, default=20, metavar="N", help="EM iterations")
+    vt.add_argument("--reg", type=float, default=1e-6, help="added to the diagonal of every covariance")
+    vt.add_argument("-o", required=True, metavar="model.npz")
+    vt.set_defaults(run=_vc_train)
+    vc = sub.add_parser("vc-convert", help="a model and a source .mgc -> the converted .mgc (deltas, conversion, MLPG)")
+    vc.add_argument("model", metavar="model.npz")
+    vc.add_argument("mgc", metavar="A.mgc")
+    vc.add_argument("--dim", type=int, required=True, metavar="D")
+    vc.add_argument("--mode", choices=("mixture", "hard"), default="mixture", help="hard: the most likely component alone")
+    vc.add_argument("-o", required=True)
+    vc.set_defaults(run=_vc_convert)
     for tool in (an, tr, mc, mo, fe):
         tool.add_argument("--fs", type=int, default=None, metavar="F",
                           help="convert every input whose sampling rate differs from F to F on the device first")
