@@ -1,19 +1,30 @@
 """The race-shaking builds (world_amd/csrc/devrt.h: -DWH_JITTER, -DWH_LDS_POISON; built by __graft_entry__.build() into
-world_amd/variants/) must compute the SAME BITS as the product library on the analysis paths.  The frame kernels alias LDS
-regions across phases and place their barriers by hand; a missing barrier or a read of never-written LDS is invisible in
-normal runs (the wavefronts of a workgroup arrive together; a fresh workgroup inherits plausible data) and used to be found
-by reading the code (d4c_frame's select zeroed histograms other wavefronts were still reading).  With random
-multi-thousand-cycle stalls behind every barrier and wave fence, or NaN patterns in every LDS byte a kernel did not write,
-such a bug changes the result."""
+world_amd/variants/) must compute the SAME BITS as the product library.  The kernels alias LDS regions across phases and
+place their barriers by hand; a missing barrier or a read of never-written LDS is invisible in normal runs (the wavefronts
+of a workgroup arrive together; a fresh workgroup inherits plausible data) and used to be found by reading the code
+(d4c_frame's select zeroed histograms other wavefronts were still reading).  With random multi-thousand-cycle
+stalls behind every barrier and wave fence, or NaN patterns in every LDS byte a kernel did not write, such a bug changes
+the result.
+
+Two parts.  The five analysis workloads of round 6 (test_jitter_build_is_bit_identical, test_lds_poison_build_is_bit_identical)
+stay as they were.  FAMILIES below runs every other kernel family of world_amd/csrc the same way, one parametrised case per
+family so that a failure names it: product twice (a family that is not deterministic cannot be judged), jitter three times,
+poison once, and once under WorldHip.profile to require that the kernels the family claims were launched.  The claims are
+the coverage table: test_every_kernel_is_claimed_by_a_family (no GPU) reads the kernel sources and fails for a __global__
+function that neither a family nor EXEMPT names, so a new kernel cannot ship without running under both builds."""
+import glob
 import os
+import re
+import time
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANTS = os.path.join(ROOT, "world_amd", "variants")
+CSRC = os.path.join(ROOT, "world_amd", "csrc")
 
 
 def _lib(name):
@@ -74,6 +85,7 @@ def _same(a, b):
     return all(np.array_equal(x, y) for ua, ub in zip(a, b) for x, y in zip(ua, ub))
 
 
+@gpu
 def test_jitter_build_is_bit_identical():
     from world_amd.api import LIB_PATH
     work = _workloads()
@@ -85,6 +97,7 @@ def test_jitter_build_is_bit_identical():
             assert _same(a, b), f"jitter build, pass {rep}, {name}: results differ from the product build's"
 
 
+@gpu
 def test_lds_poison_build_is_bit_identical():
     from world_amd.api import LIB_PATH
     work = _workloads()
@@ -93,3 +106,665 @@ def test_lds_poison_build_is_bit_identical():
     for (name, *_), a, b in zip(work, want, got):
         assert all(np.isfinite(arr).all() for utt in b for arr in utt), f"poison build, {name}: a NaN pattern reached the output"
         assert _same(a, b), f"poison build, {name}: results differ from the product build's"
+
+
+# ==== every other kernel family ==============================================================================================
+# A family is run(wh) -> [(name, numpy array), ...] on a WorldHip of the library under test (wh.lib_path names the file, for
+# the drop-in symbols), built from deterministic inputs, returning only what the library promises to write: frames below
+# n_frames, samples below the length, rows below `rows`.  Inputs are made once per process (_once) and shared by the runs.
+_made = {}
+
+
+def _once(key, make):
+    if key not in _made:
+        _made[key] = make()
+    return _made[key]
+
+
+def _pad(xs):
+    """1-D torch signals -> ([B, L] zero-padded, lengths)"""
+    import torch
+    L = max(x.numel() for x in xs)
+    xb = torch.zeros((len(xs), L), dtype=torch.float64)
+    for i, x in enumerate(xs):
+        xb[i, :x.numel()] = x
+    return xb, [int(x.numel()) for x in xs]
+
+
+def _signals(fs, specs):
+    """specs: (kind, seconds, seed-or-index, base_f0) -> the padded batch on the host, made once"""
+    from world_amd import synth
+
+    def make():
+        xs = [synth.vowel(fs, sec, seed=k, base_f0=f) if kind == "vowel" else synth.utterance(k, fs, sec) for kind, sec, k, f in specs]
+        return _pad(xs)
+    return _once(("signals", fs, tuple(specs)), make)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _frames(prefix, arrays, nf):
+    """[(name, the valid frames of utterance u)] of tensors [B, F, ...]"""
+    out = []
+    for name, a in arrays:
+        for u, n in enumerate(nf):
+            out.append((f"{prefix}.{name}[{u}]", _np(a[u, :int(n)])))
+    return out
+
+
+def _params(fs, fft, nfs, seed0=0):
+    """util.synth_params of a ragged batch: (f0 [B, F], sp, ap [B, F, fft/2+1] host arrays, padded with 0 / 1 / 1)"""
+    from util import synth_params
+
+    def make():
+        F, nb = max(nfs), fft // 2 + 1
+        f0, sp, ap = np.zeros((len(nfs), F)), np.ones((len(nfs), F, nb)), np.ones((len(nfs), F, nb))
+        for u, n in enumerate(nfs):
+            f0[u, :n], sp[u, :n], ap[u, :n] = synth_params(fs, n, fft, seed=seed0 + u)
+        return f0, sp, ap
+    return _once(("params", fs, fft, tuple(nfs), seed0), make)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+# ---- analysis routes outside the five workloads -----------------------------------------------------------------------------
+def _analyze(wh, tag, fs, specs, **kw):
+    xb, lens = _signals(fs, specs)
+    tpos, f0, sp, ap, nf = wh.analyze(xb.cuda(), fs, x_len=lens, **kw)
+    return _frames(tag, (("tpos", tpos), ("f0", f0), ("sp", sp), ("ap", ap)), nf)
+
+
+def run_harvest_direct_form(wh):
+    """tests/test_gpu_accuracy.py HV_CASES: at 16 kHz a 15 Hz floor puts the longest band filter past half a 4096-point
+    block, so the bank runs in its direct form (hv_band_quirk, hv_band_events, hv_compact_events)"""
+    return _analyze(wh, "16k floor 15", 16000, (("vowel", 0.4, 4, 110.0), ("utt", 0.3, 3, 0.0)), f0_method="harvest", f0_floor=15.0)
+
+
+def run_harvest_ratio_1(wh):
+    """HV_CASES: 11.025 kHz is analysed undecimated (hv_copy_signal, hv_partial_sums) and refined per frame.  Harvest
+    alone: D4C refuses rates below 15.8 kHz"""
+    xb, lens = _signals(11025, (("vowel", 0.4, 5, 150.0), ("utt", 0.3, 3, 0.0)))
+    tpos, f0, nf = wh.harvest(xb.cuda(), 11025, x_len=lens)
+    return _frames("11k", (("tpos", tpos), ("f0", f0)), nf)
+
+
+def run_shared_device(wh):
+    """the '48k low voice' workload on a shared_device context: one utterance keeps the narrow contour shapes"""
+    assert wh.shared_device
+    return _analyze(wh, "48k shared", 48000, (("vowel", 0.8, 2, 62.0),), f0_method="harvest", f0_floor=50.0)
+
+
+def run_dio_speeds(wh):
+    """DIO at speed 12 (decimated: dio_decimate_*) and at speed 1 (dio_copy_signal), then the stages one call each"""
+    xb, lens = _signals(16000, (("utt", 0.4, 3, 0.0), ("vowel", 0.3, 9, 180.0)))
+    x, out = xb.cuda(), []
+    for speed in (12, 1):
+        tpos, f0, nf = wh.dio(x, 16000, x_len=lens, speed=speed)
+        out += _frames(f"dio speed {speed}", (("tpos", tpos), ("f0", f0)), nf)
+    f0 = wh.stonemask(x, 16000, tpos, f0, nf, x_len=lens)
+    sp = wh.cheaptrick(x, 16000, tpos, f0, nf, x_len=lens)
+    ap = wh.d4c(x, 16000, tpos, f0, nf, 1024, x_len=lens)
+    return out + _frames("stages", (("f0", f0), ("sp", sp), ("ap", ap)), nf)
+
+
+def _block(wh, rows, cols):
+    import torch
+    return torch.zeros((rows, cols), dtype=torch.float64, device=wh.device)
+
+
+def run_analyze_records(wh):
+    """the coders fused into ct_frame and d4c_finish: coded records (60 dimensions) and packed records on both wires, ragged"""
+    from world_amd.api import cheaptrick_fft_size, frame_count
+    fs = 16000
+    xb, lens = _signals(fs, (("vowel", 0.4, 7, 130.0), ("utt", 0.3, 3, 0.0)))
+    x, fft = xb.cuda(), cheaptrick_fft_size(fs, 71.0)
+    rows = sum(frame_count(fs, n, 5.0) for n in lens)
+    out = []
+    coded = _block(wh, rows, wh.lib.world_hip_coded_columns(fs, 60))
+    assert sum(wh.analyze_coded(x, fs, coded, x_len=lens, number_of_dimensions=60)) == rows
+    out.append(("coded records", _np(coded)))
+    for wire in (0, 1):
+        block = _block(wh, rows, wh.lib.world_hip_record_columns(fft, wire))
+        assert sum(wh.analyze_packed(x, fs, block, x_len=lens)) == rows
+        out.append((f"packed records wire {wire}", _np(block)))
+    return out
+
+
+def run_spectral_range(wh):
+    """spectral_packed_range over an inner frame range, then a second range on the kept offset scans"""
+    from world_amd.api import cheaptrick_fft_size
+    fs = 16000
+    xb, lens = _signals(fs, (("vowel", 0.4, 7, 130.0), ("utt", 0.3, 3, 0.0)))
+    x, fft = xb.cuda(), cheaptrick_fft_size(fs, 71.0)
+    tpos, f0, nf = wh.harvest(x, fs, x_len=lens)
+    out = []
+    for lo, hi, reuse in ((11, 40, False), (40, 53, True)):
+        rows = int(sum(min(hi, int(n)) - min(lo, int(n)) for n in nf))
+        block = _block(wh, rows, 2 + 2 * (fft // 2 + 1))
+        assert wh.spectral_packed_range(x, fs, tpos, f0, nf, block, lo, hi, x_len=lens, reuse_offsets=reuse) == rows
+        out.append((f"frames {lo}..{hi}", _np(block)))
+    return out
+
+
+def run_cheaptrick_fft_sizes(wh):
+    """ct_frame at a caller-given fft_size: 48 kHz at 4096 (one step above the default) and at 8192"""
+    fs = 48000
+    xb, lens = _signals(fs, (("vowel", 0.3, 21, 120.0),))
+    x = xb.cuda()
+    tpos, f0, nf = wh.harvest(x, fs, x_len=lens)
+    out = []
+    for fft in (4096, 8192):
+        sp = wh.cheaptrick(x, fs, tpos, f0, nf, x_len=lens, fft_size=fft)
+        assert sp.shape[2] == fft // 2 + 1                                # (the size picks the template: cheaptrick.hip)
+        out += _frames(f"fft {fft}", (("sp", sp),), nf)
+    return out
+
+
+# ---- synthesis ------------------------------------------------------------------------------------------------------------
+def _synthesis(wh, fs, fft, nfs=(60, 47)):
+    f0, sp, ap = _params(fs, fft, nfs)
+    yl = [int(n * 5.0 / 1000.0 * fs) for n in nfs]
+    y = wh.synthesis(_dev(f0), _dev(sp), _dev(ap), list(nfs), fft, 5.0, fs, yl)
+    return [(f"y {fs}/{fft}[{u}]", _np(y[u, :n])) for u, n in enumerate(yl)]
+
+
+def run_synthesis(wh):
+    """ragged batch of two, voiced and unvoiced frames, 0.3 s: 16 kHz / 1024 and 48 kHz / 2048 (sy_pulse<4096>); then the
+    shared randn table re-reduced on the device (rng_chunk_sums) against the host's sums"""
+    out = _synthesis(wh, 16000, 1024) + _synthesis(wh, 48000, 2048)
+    ok = wh.verify_tables()
+    assert ok, "verify_tables(): the randn table on the device is not the host's stream"
+    return out + [("verify_tables", np.array([float(ok)]))]
+
+
+def run_synthesis_8192(wh):
+    """48 kHz with fft_size 8192: lg_fft = 13 > 12 launches sy_pulse<8192>, whose spectrum C lives in global memory"""
+    return _synthesis(wh, 48000, 8192)
+
+
+def run_synthesize_records(wh):
+    """Synthesis straight from f64, f32 and coded records (sy_stage_records decodes the coded rows in LDS)"""
+    from world_amd.api import cheaptrick_fft_size, frame_count
+    fs = 16000
+    xb, lens = _signals(fs, (("vowel", 0.4, 7, 130.0), ("utt", 0.3, 3, 0.0)))
+    x, fft = xb.cuda(), cheaptrick_fft_size(fs, 71.0)
+    nf = [frame_count(fs, n, 5.0) for n in lens]
+    yl = [int(n * 5.0 / 1000.0 * fs) for n in nf]
+    out = []
+    for wire, ndim in ((0, 0), (1, 0), (2, 25)):
+        cols = wh.lib.world_hip_coded_columns(fs, ndim) if wire == 2 else wh.lib.world_hip_record_columns(fft, wire)
+        block = _block(wh, sum(nf), cols)
+        if wire == 2:
+            wh.analyze_coded(x, fs, block, x_len=lens, number_of_dimensions=ndim)
+        else:
+            wh.analyze_packed(x, fs, block, x_len=lens)
+        y = wh.synthesize_records(block, nf, fs, fft, 5.0, yl, wire=wire, number_of_dimensions=ndim)
+        out += [(f"wire {wire} y[{u}]", _np(y[u, :n])) for u, n in enumerate(yl)]
+    return out
+
+
+# ---- real-time ------------------------------------------------------------------------------------------------------------
+def run_realtime(wh):
+    """three streams on chunk plans of their own (tests/test_realtime_cpu.py _stream_plans), a ring of 4 pointers that
+    wraps several times, stream 2 fed with coded rows; then the drop-in WorldSynthesizer symbols of the same library"""
+    from test_realtime_cpu import _lone_run, _stream_plans
+    from world_amd.api import HostAPI
+    fs, fft, bs, P, ndim = 16000, 1024, 64, 4, 25
+    plans = _once(("rt plans",), lambda: _stream_plans(3, fs, fft, 48, seed=3))
+    rt = wh.realtime(len(plans), fs, 5.0, fft, bs, P)
+    dev = [(_dev(sp), _dev(ap)) for _, sp, ap, _ in plans]
+    sp2, ap2 = dev[2]
+    import torch
+    coded = torch.cat([wh.code_spectral_envelope(sp2, fs, fft, ndim), wh.code_aperiodicity(ap2, fs, fft)], dim=1).contiguous()
+    outs, pos, k, adds = [[] for _ in plans], [0] * len(plans), [0] * len(plans), [0] * len(plans)
+    try:
+        while True:
+            busy = False
+            for s, (f0, _, _, chunks) in enumerate(plans):
+                if k[s] < len(chunks):
+                    n, at = chunks[k[s]], pos[s]
+                    if s == 2:
+                        r = rt.add_coded(s, f0[at:at + n], coded[at:, :ndim], coded[at:, ndim:])
+                    else:
+                        r = rt.add(s, f0[at:at + n], dev[s][0][at:], dev[s][1][at:])
+                    if r == 1:
+                        pos[s] += n
+                        k[s] += 1
+                        adds[s] += 1
+                    busy = True
+            while True:
+                out, produced = rt.synthesize()
+                host = _np(out)
+                for s in np.nonzero(produced)[0]:
+                    outs[s].append(host[s].copy())
+                if not produced.any():
+                    break
+            if not busy:
+                break
+    finally:
+        rt.close()
+    assert min(adds) > P, f"the rings did not wrap: {adds} adds into {P} pointers"
+    res = [(f"stream {s}", np.concatenate(o)) for s, o in enumerate(outs)]
+    assert all(a.size > 0 for _, a in res)
+    lone = _lone_run(HostAPI(wh.lib_path), plans[0], fs, fft, bs, P)
+    assert lone.size > 0
+    return res + [("drop-in stream 0", lone)]
+
+
+# ---- coders ---------------------------------------------------------------------------------------------------------------
+CODER_SHAPES = [(16000, 1024), (48000, 2048), (48000, 4096), (16000, 128)]
+CODER_DIMS = (1, 25, 60)
+CODER_ROWS = 37
+
+
+def run_coders(wh):
+    """tests/test_codec.py's shapes, 37 rows.  The coder admits fft_size / 4 + 1 dimensions at the most: the 128-point
+    shape takes its 33 in place of 60.  Every fourth decoded aperiodicity row is an aperiodic frame (mean band value above
+    -0.5 dB), as there"""
+    from backends import envelope
+    from util import synth_params
+    out = []
+    for fs, fft in CODER_SHAPES:
+        sp = _dev(_once(("envelope", fs, fft), lambda: envelope(fs, fft, CODER_ROWS, fs + fft)))
+        ap = _dev(_once(("ap", fs, fft), lambda: synth_params(fs, CODER_ROWS, fft, seed=1)[2]))
+        for ndim in sorted({min(d, fft // 4 + 1) for d in CODER_DIMS}):
+            coded = wh.code_spectral_envelope(sp, fs, fft, ndim)
+            back = wh.decode_spectral_envelope(coded, fs, fft)
+            assert coded.shape == (CODER_ROWS, ndim) and back.shape == sp.shape
+            out += [(f"{fs}/{fft}/{ndim} coded sp", _np(coded)), (f"{fs}/{fft}/{ndim} decoded sp", _np(back))]
+        coded = wh.code_aperiodicity(ap, fs, fft)
+        out.append((f"{fs}/{fft} coded ap", _np(coded)))
+        coded[::4] = -0.3
+        out.append((f"{fs}/{fft} decoded ap", _np(wh.decode_aperiodicity(coded, fs, fft))))
+    return out
+
+
+# ---- modification ---------------------------------------------------------------------------------------------------------
+def run_modify(wh):
+    """modify with an F0 scale, a formant shift and a log-F0 target (modify_f0's three reductions), f0_statistics, and
+    resynthesize end to end"""
+    fs, fft, nfs = 16000, 1024, (60, 47)
+    f0, sp, _ = _params(fs, fft, nfs)
+    d_f0, d_sp = _dev(f0), _dev(sp)
+    out = [("f0 statistics", _np(wh.f0_statistics(d_f0, list(nfs))))]
+    f0m, spm = wh.modify(d_f0, d_sp, list(nfs), fs, fft, f0_scale=[1.25, 0.8], formant_shift=[1.15, 0.87],
+                         log_f0_target=([5.0, 4.7], [0.25, 0.1]))
+    out += _frames("modify", (("f0", f0m), ("sp", spm)), nfs)
+    xb, lens = _signals(fs, (("vowel", 0.4, 7, 130.0), ("utt", 0.3, 3, 0.0)))
+    y, yl = wh.resynthesize(xb.cuda(), fs, x_len=lens, f0_scale=[1.2, 0.9], formant_shift=[0.9, 1.1], time_scale=1.25,
+                            log_f0_target=([5.1, 4.9], [0.2, 0.15]))
+    return out + [(f"resynthesize y[{u}]", _np(y[u, :int(n)])) for u, n in enumerate(yl)]
+
+
+def run_modify_frames(wh):
+    """modify_frames behind a non-integer time map with per-frame curves, and resynthesize_frames end to end"""
+    import torch
+    from world_amd.api import frame_count, uniform_time_map
+    fs, fft, nfs, O = 16000, 1024, (60, 47), 71
+    f0, sp, ap = _params(fs, fft, nfs)
+    n_out = [71, 52]
+    tm = torch.stack([torch.nn.functional.pad(uniform_time_map(n, o), (0, O - o)) for n, o in zip(nfs, n_out)])
+    j = torch.arange(O, dtype=torch.float64, device=wh.device)
+    curves = dict(f0_scale=(1.0 + 0.2 * torch.sin(j / 7.0))[None].repeat(2, 1), formant_shift=(1.0 + 0.1 * torch.cos(j / 11.0))[None].repeat(2, 1),
+                  ap_gain=(0.8 + 0.4 * (j / O))[None].repeat(2, 1), f0_target=torch.where(j % 9 == 0, 200.0 + j, torch.zeros_like(j))[None].repeat(2, 1))
+    outs = wh.modify_frames(_dev(f0), _dev(sp), _dev(ap), list(nfs), fs, fft, n_out=n_out, time_map=tm, **curves)
+    out = _frames("modify_frames", zip(("f0", "sp", "ap"), outs), n_out)
+    xb, lens = _signals(fs, (("vowel", 0.4, 7, 130.0), ("utt", 0.3, 3, 0.0)))
+    nf = [frame_count(fs, n, 5.0) for n in lens]
+    n_out = [int(nf[0] * 1.3), int(nf[1] * 0.8)]
+    O = max(n_out)
+    tm = torch.stack([torch.nn.functional.pad(uniform_time_map(n, o), (0, O - o)) for n, o in zip(nf, n_out)])
+    j = torch.arange(O, dtype=torch.float64, device=wh.device)
+    y, yl = wh.resynthesize_frames(xb.cuda(), fs, x_len=lens, n_out=n_out, time_map=tm, f0_scale=(1.0 + 0.1 * torch.sin(j / 5.0)),
+                                   formant_shift=[1.1, 0.95])
+    return out + [(f"resynthesize_frames y[{u}]", _np(y[u, :int(n)])) for u, n in enumerate(yl)]
+
+
+# ---- alignment and morph --------------------------------------------------------------------------------------------------
+ALIGN_PAIRS = [(17, 45), (130, 97)]                       # neither a multiple of align_cost's 16 x 32 tile
+ALIGN_LONG = (2050, 2061)                                 # its longest diagonals pass kAlignAhead * kAlignDpThreads = 2048 cells
+
+
+def _align_features(pairs, D, seed):
+    def make():
+        rng = np.random.default_rng(seed)
+        Fa, Fb = max(p[0] for p in pairs), max(p[1] for p in pairs)
+        a, b = np.zeros((len(pairs), Fa, D)), np.zeros((len(pairs), Fb, D))
+        for u, (na, nb) in enumerate(pairs):
+            walk = np.cumsum(rng.standard_normal((max(na, nb), D)), axis=0)
+            a[u, :na] = walk[np.linspace(0, len(walk) - 1, na).astype(int)] + 0.1 * rng.standard_normal((na, D))
+            b[u, :nb] = walk[np.linspace(0, len(walk) - 1, nb).astype(int)] + 0.1 * rng.standard_normal((nb, D))
+        return a, b
+    return _once(("align", tuple(pairs), D, seed), make)
+
+
+def _align(wh, tag, pairs, D, seed):
+    a, b = _align_features(pairs, D, seed)
+    na, nb = [p[0] for p in pairs], [p[1] for p in pairs]
+    path, path_len, summary, map_b, map_a = wh.align(_dev(a), _dev(b), na, nb)
+    out = [(f"{tag} path_len", _np(path_len)), (f"{tag} summary", _np(summary))]
+    for u, k in enumerate(_np(path_len)):
+        out += [(f"{tag} path[{u}]", _np(path[u, :int(k)])), (f"{tag} map_b[{u}]", _np(map_b[u, :nb[u]])), (f"{tag} map_a[{u}]", _np(map_a[u, :na[u]]))]
+    return out, path, path_len
+
+
+def run_align(wh):
+    out, _, _ = _align(wh, "ragged", ALIGN_PAIRS, 24, 5)
+    assert min(ALIGN_LONG) > 2048
+    long_out, _, _ = _align(wh, "long", [ALIGN_LONG], 3, 6)
+    return out + long_out
+
+
+def run_morph(wh):
+    """morph along align's path: a constant rate, then per-frame rates as a cross-fade does"""
+    import torch
+    fs, fft = 16000, 1024
+    _, path, path_len = _align(wh, "ragged", ALIGN_PAIRS, 24, 5)
+    na, nb = [p[0] for p in ALIGN_PAIRS], [p[1] for p in ALIGN_PAIRS]
+    A, B = _params(fs, fft, na, seed0=0), _params(fs, fft, nb, seed0=5)
+    a, b = tuple(_dev(v) for v in A), tuple(_dev(v) for v in B)
+    f0, sp, ap, no = wh.morph(a, b, na, nb, fs, fft, path=path, path_len=path_len, rate=0.3)
+    out = _frames("constant", (("f0", f0), ("sp", sp), ("ap", ap)), no)
+    O = max(wh.morph_length(x, y, 0.5) for x, y in zip(na, nb))
+    fade = torch.linspace(0.0, 1.0, O, dtype=torch.float64, device=wh.device)
+    f0, sp, ap, no, pos_a, pos_b = wh.morph(a, b, na, nb, fs, fft, path=path, path_len=path_len, time_rate=0.5, f0_rate=fade, sp_rate=fade,
+                                            ap_rate=1.0 - fade, want_positions=True)
+    return out + _frames("fade", (("f0", f0), ("sp", sp), ("ap", ap), ("pos_a", pos_a), ("pos_b", pos_b)), no)
+
+
+# ---- resampling -----------------------------------------------------------------------------------------------------------
+# (fs_in, fs_out): interpolation, a rational ratio, integer decimation by 3, by 4 (resample.inc: L == 1 and M a multiple of 4
+# pads the LDS rows -- resample_decim_pad), equal rates
+RESAMPLE_PAIRS = [(16000, 48000), (44100, 48000), (48000, 16000), (48000, 12000), (16000, 16000)]
+
+
+def run_resample(wh):
+    out = []
+    for fs_in, fs_out in RESAMPLE_PAIRS:
+        lens = [int(0.1 * fs_in) + 3, int(0.07 * fs_in)]
+        x = _once(("noise", fs_in), lambda: 0.3 * np.random.default_rng(fs_in).standard_normal((2, max(lens))))
+        for quality in ("best", "fast"):
+            y, yl = wh.resample(_dev(x), fs_in, fs_out, x_len=lens, quality=quality)
+            out += [(f"{fs_in}->{fs_out} {quality}[{u}]", _np(y[u, :int(n)])) for u, n in enumerate(yl)]
+    return out
+
+
+# ---- mel-cepstra ----------------------------------------------------------------------------------------------------------
+def run_mcep(wh):
+    """tests/test_mcep_gpu.py's shapes: 512-point envelopes, 67 rows (the last row tile is partial), orders 24 / 100 / 200
+    (mcep_encode_64 / _128 / _256), back through mcep_decode, and one call on the strided view packed records give"""
+    import torch
+    from backends import envelope
+    fft, rows, alpha = 512, 67, 0.42
+    K = fft // 2 + 1
+    sp = _dev(_once(("envelope", 16000, fft, rows), lambda: envelope(16000, fft, rows, 13)))
+    out = []
+    for order in (24, 100, 200):
+        mc = wh.sp2mc(sp, order, alpha)
+        out += [(f"sp2mc {order}", _np(mc)), (f"mc2sp {order}", _np(wh.mc2sp(mc, alpha, fft)))]
+    block = torch.full((rows, 2 + 2 * K), -7.0, dtype=torch.float64, device=wh.device)
+    block[:, 2:2 + K] = sp
+    return out + [("sp2mc strided", _np(wh.sp2mc(block[:, 2:2 + K], 24, alpha)))]
+
+
+# ---- deltas and MLPG ------------------------------------------------------------------------------------------------------
+MLPG_LENS = (1, 2, 203)
+MLPG_DIMS = (1, 60, 65)
+
+
+def run_mlpg(wh):
+    """window half-widths 0 / 1 / 2 (delta_rows_0 / _1 / _2; mlpg_static / mlpg_sweeps_2 / mlpg_sweeps_4), frames 1, 2 and
+    203 in one ragged batch, a mask of several runs, per-frame, per-utterance and global variances"""
+    import test_mlpg_cpu as cpu
+    U, T = len(MLPG_LENS), max(MLPG_LENS)
+    out = []
+    for wname, win in cpu.WINDOWS.items():
+        n_win = win.shape[0]
+        for D in MLPG_DIMS:
+            def make():
+                rng = np.random.default_rng(100 * n_win + D)
+                mask = rng.random((U, T)) < 0.9
+                mask[2, 40:43] = mask[2, 90] = mask[2, 150:170] = False
+                mask[2, 0] = mask[0, 0] = True
+                return (rng.standard_normal((U, T, D)), mask, rng.standard_normal((U, T, n_win * D)), cpu.spread(rng, 3, (U, T, n_win * D)))
+            c, mask, mean, var = _once(("mlpg", wname, D), make)
+            d_mask, d_mean, d_var = _dev(mask), _dev(mean), _dev(var)
+            windows = [list(r) for r in win]
+            dl = wh.deltas(_dev(c), windows=windows, mask=d_mask, fill=cpu.FILL, n_frames=MLPG_LENS)
+            out += _frames(f"{wname} D{D}", (("deltas", dl),), MLPG_LENS)
+            for kind, v, m in (("frame", d_var, d_mask), ("utterance", d_var[:, 0].contiguous(), None), ("global", d_var[0, 0].contiguous(), d_mask)):
+                gen = wh.mlpg(d_mean, v, windows=windows, mask=m, fill=cpu.FILL, n_frames=MLPG_LENS, precision=kind == "utterance")
+                out += _frames(f"{wname} D{D} {kind}", (("mlpg", gen),), MLPG_LENS)
+    return out
+
+
+# ---- the Gaussian mixture -------------------------------------------------------------------------------------------------
+def run_gmm(wh):
+    """test_gmm_cpu.CONVERT in both modes (gmm_q, gmm_regress, gmm_posterior), ACCUMULATE (gmm_accumulate), and two
+    iterations of the fit on two_clusters() from the given and from the default start"""
+    import test_gmm_cpu as cpu
+    from backends import OnGpu
+
+    class GpuBackend(OnGpu, cpu.Backend):
+        pass
+
+    be = GpuBackend(wh)
+    out = []
+    for M, dx, dy, rows, strided in cpu.CONVERT:
+        model, parts = cpu.prepared(be, M, dx, dy)
+        d_model, x = be.model_dev(model), cpu.rows_near(parts, rows, 11)
+        for mode in (0, 1):
+            got = be.convert(M, dx, dy, d_model, x, mode=mode, slack=3 if strided else 0, before=1 if strided else 0)
+            out += [(f"convert M{M} dx{dx} dy{dy} rows{rows} mode{mode} {k}", v) for k, v in got.items()]
+    M, dx, dy, rows = 5, 17, 16, 130
+    model, parts = cpu.prepared(be, M, dx, dy)
+    gm = wh.gmm_prepare(*cpu.random_model(M, dx, dy, 1), dx)
+    post, loglik = wh.gmm_posterior(gm, _dev(cpu.rows_near(parts, rows, 47)))
+    out += [("posterior", _np(post)), ("posterior loglik", _np(loglik))]
+    for M, P, rows in cpu.ACCUMULATE:
+        for name, v in zip(("N", "S1", "G"), be.accumulate(*cpu.stats_inputs(M, P, rows), slack=2)):
+            out.append((f"accumulate M{M} P{P} rows{rows} {name}", v))
+    z, w0, mu0, cov0 = cpu.two_clusters()
+    for tag, init in (("given start", (w0, mu0, cov0)), ("default start", None)):
+        for name, v in zip(("w", "mu", "cov", "loglik"), wh.gmm_fit(_dev(z), 2, n_iter=2, reg=1e-6, init=init)):
+            out.append((f"fit {tag} {name}", v))
+    return out
+
+
+# ---- plumbing -------------------------------------------------------------------------------------------------------------
+def run_plumbing(wh):
+    import torch
+    fs, fft, nfs = 16000, 1024, (23, 9)
+    f0, sp, ap = _params(fs, fft, nfs)
+    tpos = np.arange(max(nfs))[None].repeat(2, 0) * 0.005
+    block = _block(wh, sum(nfs) + 2, 2 + 2 * (fft // 2 + 1))
+    wh.pack_results(_dev(tpos), _dev(f0), _dev(sp), _dev(ap), list(nfs), block, first_row=1)
+    out = [("packed", _np(block))]
+    out += _frames("unpacked", zip(("tpos", "f0", "sp", "ap"), wh.unpack_results(block, list(nfs), first_row=1)), nfs)
+    pcm = _once(("pcm",), lambda: np.random.default_rng(9).integers(-32768, 32768, 3001).astype(np.int16))
+    out.append(("pcm16_to_double", _np(wh.pcm16_to_double(_dev(pcm)))))
+    raw = _dev(pcm.view(np.uint8)[:3000])
+    for nbit in (8, 16, 24):
+        out.append((f"pcm_to_double {nbit}", _np(wh.pcm_to_double(raw, nbit))))
+    out.append(("double_to_pcm16", _np(wh.double_to_pcm16(_dev(pcm.astype(np.float64) / 30000.0)))))
+    # the per-frame transform alone: a 2048-point static plan, a 512-point run-time plan, radix 8 and radix 16 last stages
+    for N, static, max_lr in ((2048, True, 3), (512, False, 3), (512, False, 4)):
+        x = _dev(_once(("fft rows", N), lambda: np.random.default_rng(N).standard_normal((3, N))))
+        spec = wh.probe_rfft(x, max_lr=max_lr, static_plan=static)
+        out += [(f"rfft {N} {static} {max_lr}", _np(spec)), (f"irfft {N} {static} {max_lr}", _np(wh.probe_irfft(spec, max_lr=max_lr, static_plan=static)))]
+    torch.cuda.synchronize()
+    return out
+
+
+# ---- the coverage table: which kernels (world_amd/csrc: __global__ void NAME) each family launches -------------------------
+_CONTOUR = ("hc_step12_sections", "hc_extend", "hc_merge", "hc_smooth", "hc_output")
+_HARVEST_TAIL = ("hv_remove_mean", "hv_raw_candidates", "hv_detect", "hv_prune") + _CONTOUR
+_FUSED_SPECTRAL = ("spectral_prepare", "ct_frame", "d4c_lovetrain", "d4c_frame", "d4c_finish")
+_SYNTHESIS = ("sy_increments", "sy_phase_serial", "sy_detect", "sy_compact", "sy_pulse", "sy_overlap_add")
+_HARVEST_FFT = ("hv_decimate_fwd", "hv_decimate_bwd", "hv_band_spectra", "hv_block_spectra", "hv_band_events_fft") + _HARVEST_TAIL
+
+# Measured on one MI355X, the whole test of a family (seven passes and four contexts): modify-frames 0.78 s,
+# harvest-direct-form 0.68 s, gmm 0.24 s, realtime 0.17 s, mcep 0.14 s, synthesis 0.13 s, mlpg and shared-device 0.12 s, every
+# other family below 0.1 s; one jitter pass 0.17 s (harvest-direct-form) and 0.03 s or less elsewhere.
+FAMILIES = {
+    # name: (run, the kernels it must launch, WorldHip keyword arguments)
+    "harvest-direct-form": (run_harvest_direct_form, ("hv_decimate_fwd", "hv_decimate_bwd", "hv_band_quirk", "hv_band_events", "hv_compact_events")
+                            + _HARVEST_TAIL + _FUSED_SPECTRAL, {}),
+    "harvest-ratio-1": (run_harvest_ratio_1, ("hv_copy_signal", "hv_partial_sums", "hv_refine_frames") + _HARVEST_TAIL, {}),
+    "shared-device": (run_shared_device, _HARVEST_FFT + _FUSED_SPECTRAL, dict(shared_device=True)),
+    "dio-speeds": (run_dio_speeds, ("dio_decimate_fwd", "dio_decimate_bwd", "dio_copy_signal", "dio_partial_sums", "dio_remove_mean", "dio_lowcut",
+                                    "dio_nyquist_slices", "dio_nyquist_bins", "dio_band_quirk", "dio_band_events", "dio_compact_events",
+                                    "dio_candidates", "dio_step1", "dio_step2", "dio_track_sweeps", "dio_time_axis", "sm_frame", "ct_prepare",
+                                    "ct_frame", "d4c_prepare1", "d4c_lovetrain", "d4c_frame", "d4c_finish"), {}),
+    "analyze-records": (run_analyze_records, _HARVEST_FFT + ("hv_refine",) + _FUSED_SPECTRAL + ("ct_frame_coded",), {}),
+    "spectral-range": (run_spectral_range, ("ct_frame", "d4c_lovetrain", "d4c_frame", "d4c_finish"), {}),
+    "cheaptrick-fft-sizes": (run_cheaptrick_fft_sizes, ("ct_prepare", "ct_frame"), {}),
+    "synthesis": (run_synthesis, _SYNTHESIS + ("rng_stream_fill", "rng_chunk_sums"), {}),
+    "synthesis-8192": (run_synthesis_8192, _SYNTHESIS, {}),
+    "synthesize-records": (run_synthesize_records, ("sy_stage_records",) + _SYNTHESIS, {}),
+    "realtime": (run_realtime, ("rt_pulse", "rt_overlap_add", "rt_store_rows", "rt_store_coded_rows", "codec_code_sp", "codec_code_ap"), {}),
+    "coders": (run_coders, ("codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap"), {}),
+    "modify": (run_modify, ("modify_f0", "modify_warp_sp") + _SYNTHESIS, {}),
+    "modify-frames": (run_modify_frames, ("modify_frames_f0", "modify_frames_sp", "modify_frames_ap") + _SYNTHESIS, {}),
+    "align": (run_align, ("align_cost", "align_dp", "align_path"), {}),
+    "morph": (run_morph, ("align_cost", "align_dp", "align_path", "morph_positions", "morph_frames_f0", "morph_frames_sp", "morph_frames_ap"), {}),
+    "resample": (run_resample, ("resample_poly", "resample_decim", "resample_decim_pad", "resample_copy"), {}),
+    "mcep": (run_mcep, ("mcep_encode_64", "mcep_encode_128", "mcep_encode_256", "mcep_decode"), {}),
+    "mlpg": (run_mlpg, ("delta_rows_0", "delta_rows_1", "delta_rows_2", "mlpg_static", "mlpg_sweeps_2", "mlpg_sweeps_4"), {}),
+    "gmm": (run_gmm, ("gmm_q", "gmm_regress", "gmm_posterior", "gmm_accumulate", "gmm_fill"), {}),
+    "plumbing": (run_plumbing, ("ex_pack_rows", "ex_unpack_rows", "pcm16_to_double", "pcm_bytes_to_double", "double_to_pcm16",
+                                "fft_probe_rfft<3, 11>", "fft_probe_irfft<3, 11>", "fft_probe_rfft<3>", "fft_probe_irfft<3>",
+                                "fft_probe_rfft<4>", "fft_probe_irfft<4>"), {}),
+}
+# profile labels that are not the kernel's own name (devrt::launch_blocks("label", kernel<...>, ...))
+LABELS = {"ct_frame_coded": "ct_frame"}
+# kernels that run only while a process-wide table is built: asserted on the first pass of the jitter library, which nothing
+# but this module loads (the product library's table may stand already when another module's context is still alive)
+COLD_ONLY = ("rng_stream_fill",)
+EXEMPT = {
+    "mp_fill": "machine probe: measures the hardware (world_hip_probe_machine), no result to compare",
+    "mp_touch": "machine probe: measures the hardware, no result to compare",
+    "mp_chase": "machine probe: measures memory latency, no result to compare",
+    "mp_fp64_load": "machine probe: measures the clock under FP64 load, no result to compare",
+    "mp_lds": "machine probe: measures the LDS round trip, no result to compare",
+}
+
+
+def _kernel_of(label):
+    """the __global__ function a profile label or a claim names: 'fft_probe_rfft<3, 11>' -> 'fft_probe_rfft'"""
+    base = re.match(r"\(?\s*(\w+)", label).group(1)
+    return LABELS.get(base, base)
+
+
+def kernels_in_source():
+    """every `__global__ void [__launch_bounds__(...)] [ATTRIBUTE_MACRO] name(` of world_amd/csrc/*.hip and *.inc"""
+    pattern = re.compile(r"__global__\s+void\s+(?:__launch_bounds__\s*\([^)]*\)\s*)?(?:[A-Z][A-Z0-9_]*\s+)?(\w+)\s*\(")
+    names = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.inc"))):
+        with open(path) as f:
+            for name in pattern.findall(f.read()):
+                names.setdefault(name, os.path.basename(path))
+    return names
+
+
+def claimed_kernels():
+    return {_kernel_of(k) for _, kernels, _ in FAMILIES.values() for k in kernels}
+
+
+def unclaimed_kernels(source, claimed, exempt):
+    return sorted(k for k in source if k not in claimed and k not in exempt)
+
+
+def test_every_kernel_is_claimed_by_a_family():
+    source = kernels_in_source()
+    assert len(source) > 100 and "d4c_frame" in source and "mcep_encode_64" in source and "align_dp" in source, "the scan lost the kernels"
+    missing = unclaimed_kernels(source, claimed_kernels(), EXEMPT)
+    assert not missing, ("kernels that no family of tests/test_gpu_checked_builds.py runs under the jitter and LDS-poison builds: "
+                         + ", ".join(f"{k} ({source[k]})" for k in missing))
+    stale = sorted(k for k in (claimed_kernels() | set(EXEMPT)) if k not in source)
+    assert not stale, f"claimed or exempt, but no longer in world_amd/csrc: {stale}"
+    assert all(k.startswith("mp_") and reason for k, reason in EXEMPT.items())
+    # the scan itself: a kernel taken out of the table is reported
+    assert unclaimed_kernels(source, claimed_kernels() - {"align_dp"}, EXEMPT) == ["align_dp"]
+
+
+# ---- the helper -----------------------------------------------------------------------------------------------------------
+def _open(lib_path, kw):
+    from world_amd.api import WorldHip
+    wh = WorldHip(device=0, lib_path=lib_path, **kw)
+    wh.lib_path = lib_path
+    return wh
+
+
+def _run_family(lib_path, run, kw, repeats=1, profile_first=False):
+    """-> ([result of each pass], {kernel: launches} of the first pass when profiled, seconds per pass)"""
+    import torch
+    wh = _open(lib_path, kw)
+    results, launches, seconds = [], {}, []
+    try:
+        for rep in range(repeats):
+            t0 = time.perf_counter()
+            if profile_first and rep == 0:
+                got = []
+                prof = wh.profile(lambda: got.append(run(wh)))
+                res = got[0]
+                for label, ms in prof.items():
+                    launches[label] = launches.get(label, 0) + len(ms)
+            else:
+                res = run(wh)
+            torch.cuda.synchronize()
+            seconds.append(time.perf_counter() - t0)
+            results.append(res)
+    finally:
+        wh.close()
+    return results, launches, seconds
+
+
+def _differences(want, got):
+    from backends import same_bits
+    assert [n for n, _ in want] == [n for n, _ in got], "the passes returned different outputs"
+    return [n for (n, a), (_, b) in zip(want, got) if not same_bits(a, b)]
+
+
+def _launched(launches, claim):
+    """a claim with template arguments names the profile label itself; a bare name any label of that kernel"""
+    if "<" in claim:
+        return any(label.strip("()") == claim for label in launches)
+    return any(label == claim or _kernel_of(label) == claim for label in launches)
+
+
+@gpu
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_family_on_the_checked_builds(family):
+    from world_amd.api import LIB_PATH
+    run, kernels, kw = FAMILIES[family]
+    (first, second), _, t_product = _run_family(LIB_PATH, run, kw, repeats=2)
+    assert first, f"{family}: nothing to compare"
+    bad = _differences(first, second)
+    assert not bad, f"{family}: the product build is not deterministic in {bad[:8]}: the family cannot be judged"
+    # routes: what the family claims was launched
+    _, launches, _ = _run_family(LIB_PATH, run, kw, profile_first=True)
+    missing = [k for k in kernels if k not in COLD_ONLY and not _launched(launches, k)]
+    assert not missing, f"{family}: claims {missing}, launched {sorted(launches)}"
+    # jitter: three passes, the stalls fall differently every time
+    passes, cold, t_jitter = _run_family(_lib("jitter"), run, kw, repeats=3, profile_first=True)
+    missing = [k for k in kernels if k in COLD_ONLY and not _launched(cold, k)]
+    assert not missing, f"{family}: claims {missing}, the jitter build's first pass launched {sorted(cold)}"
+    for rep, res in enumerate(passes):
+        bad = _differences(first, res)
+        assert not bad, f"{family}: jitter build, pass {rep}: {bad[:8]} differ from the product build's"
+    # poison: no NaN pattern where the product build has a number, and the same bits
+    (res,), _, t_poison = _run_family(_lib("poison"), run, kw)
+    for (name, a), (_, b) in zip(first, res):
+        a, b = np.asarray(a), np.asarray(b)
+        if a.dtype.kind == "f":
+            assert a.shape == b.shape and np.all(np.isfinite(b) | ~np.isfinite(a)), f"{family}: poison build, {name}: a NaN pattern reached the output"
+    bad = _differences(first, res)
+    assert not bad, f"{family}: poison build: {bad[:8]} differ from the product build's"
+    print(f"{family}: product {min(t_product):.2f} s, jitter {max(t_jitter):.2f} s a pass, poison {t_poison[0]:.2f} s; "
+          f"{len(first)} outputs, {sum(launches.values())} launches")

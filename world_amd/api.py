@@ -861,7 +861,7 @@ class WorldHip:
             raise RuntimeError("profile: " + self.lib.world_hip_last_error().decode())
         out = {}
         for line in buf.value.decode().splitlines():
-            name, ms = line.split()
+            name, ms = line.rsplit(None, 1)      # (a template's label has blanks: "(fft_probe_rfft<3, 11>) 0.01")
             out.setdefault(name, []).append(float(ms))
         return out
 

@@ -59,6 +59,7 @@ __global__ void __launch_bounds__(256) codec_code_sp(CodecParams p) {
     const int dest = (i & 1) ? md / 2 + (md - 1 - i) / 2 : i / 2;
     rfft_in(Z, dest) = v;
   }
+  lds_dead(lg, md + 2);                                               // the log row has gone into Z: the transform reads Z alone
   const double norm = sqrt(static_cast<double>(md));
   double *out = p.out + (size_t)row * (p.out_stride ? p.out_stride : (size_t)p.ndim);
   block_rfft(Z, p.lg_md, tw, [&](int k, double re, double im) {
@@ -95,6 +96,7 @@ __device__ __forceinline__ void decode_sp_row(const DecodeTables p, const double
     mel[2 + 2 * i] = Z[fft_slot(plan, md - 1 - i)].re;
   }
   __syncthreads();
+  lds_dead(Z, 2 * md);                                                // the transform has gone into mel: the interpolation reads mel alone
   if (tid == 0) { mel[0] = mel[1]; mel[md + 1] = mel[md]; }
   __syncthreads();
   for (int j = tid; j < nb; j += nt) {
@@ -355,6 +357,7 @@ __global__ void __launch_bounds__(256) modify_f0(ModifyParams p) {
       if (voiced_f0(v)) { sum += log(v); count += 1.0; }
     }
     block_sum2(sum, count, scratch);
+    lds_dead(scratch, 64);                            // (count is the workgroup's: the branch below is uniform)
     if (count > 0.0) {
       mu = sum / count;
       // one correction of the mean by its residuals: a constant track then has mu exactly its ln f0, hence sigma_s = 0
@@ -364,6 +367,7 @@ __global__ void __launch_bounds__(256) modify_f0(ModifyParams p) {
         if (voiced_f0(v)) res += log(v) - mu;
       }
       mu += block_sum(res, scratch + 64) / count;
+      lds_dead(scratch + 64, 16);
       double ss = 0.0;
       for (int i = tid; i < n; i += nt) {
         const double v = in[i];

@@ -252,7 +252,7 @@ __device__ __forceinline__ int xcd_grouped(int b, int n) {
   return b - r + (r % 8) * kXcdRun + r / 8;
 }
 
-// ---- race-shaking builds (test infrastructure; python -m world_amd.build --checked; tests/test_gpu_parity.py) ----------
+// ---- race-shaking builds (test infrastructure; python -m world_amd.build --checked; tests/test_gpu_checked_builds.py) --
 // The frame kernels alias LDS regions across phases and place their barriers by hand (d4c_frame: 63 of them), and a
 // missing one is invisible in normal runs: the wavefronts of a workgroup execute the same instruction stream and arrive
 // together (round 3-4 shipped a select that zeroed histograms aliasing a transform buffer other wavefronts were still
@@ -267,7 +267,12 @@ __device__ __forceinline__ int xcd_grouped(int b, int n) {
 //                    otherwise inherits the previous one's data, usually the same kernel's: plausible values), and
 //                    lds_dead(ptr, n) marks fill a region whose contents nobody may read any more.  (This build ADDS
 //                    barriers around the fills, so it is a separate build from the jitter one.)
-// The GPU suite runs the analysis paths on both and requires results bit-identical to the product build's.
+// The GPU suite runs EVERY kernel family on both -- the analysis workloads, and one workload per family of synthesis,
+// real-time synthesis, the coders, modification, alignment, morph, resampling, mel-cepstra, MLPG, the Gaussian mixture
+// and the plumbing kernels -- and requires results bit-identical to the product build's.  The families name the kernels
+// they launch; a CPU test of the same file reads these sources and fails for a __global__ function no family names (the
+// mp_* machine probes excepted: they measure, they have no result).  A new kernel therefore comes with a workload there,
+// and with lds_dead() marks where it hands an LDS region from one use to the next.
 #ifndef WORLD_EMU
 #if defined(WH_JITTER)
 __device__ __forceinline__ void jitter() {

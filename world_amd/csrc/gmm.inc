@@ -165,7 +165,9 @@ template <bool REGRESS> __device__ __forceinline__ void gmm_product(const GmmPar
           }
         }
       }
+      lds_dead(red, BM * kGmmRed);                          // the next mixture's weights / squares start afresh
     }
+    lds_dead(bs, kGmmChunk * ldb + kGmmChunk);              // the chunk and its mu_x: the next one is read only where it is written
     __syncthreads();
     k0 += kGmmChunk;
     if (k0 >= Kp) {

@@ -234,6 +234,7 @@ __device__ __forceinline__ void minimum_phase(cplx *Z, cplx *C, const double *LG
     C[k] = m;
   }
   __syncthreads();
+  lds_dead(Z, 2 * N);                                // the spectrum is in C: whoever takes Z next writes before it reads
 }
 
 // One pulse's response, the body both pulse kernels share.  NMAX: the largest fft_size of the instantiation (a thread's
@@ -316,6 +317,11 @@ __device__ __forceinline__ void pulse_response(char *lds, double *slot, int lgn,
         if (i < N) per[q] = i < H ? -dc * dc_remover[i] : rfft_in(Z, i - H) - dc * dc_remover[i];
       }
     }
+    // the periodic response waits in registers: its transform, its spectrum and the reduction's scratch are handed to
+    // the aperiodic half (has_periodic is the workgroup's: uniform)
+    lds_dead(Z, 2 * N);
+    if (!c_global) lds_dead(C, 2 * nb);
+    lds_dead(scratch, 64);
   }
 
   // ---- aperiodic response (GetAperiodicResponse)
