@@ -15,6 +15,7 @@
 // Nothing here is shipped; the unit lives in its own shared object (tests/emu/Makefile) whose inline functions stay
 // local, so its WAVE = 64 spellings of devrt.h / fft.h cannot be merged with the one-lane spellings of the other units.
 #pragma once
+#include <atomic>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -87,7 +88,10 @@ static inline void __syncthreads() { simt::barrier(); }
 // launches, so it needs none of it) --------------------------------------------------------------------------------------
 namespace devrt {
 // (device memory is the host's: the few host-side helpers units call between launches)
-static inline void *dmalloc(size_t bytes) { void *p = malloc(bytes ? bytes : 1); memset(p, 0xA5, bytes); return p; }
+// (0xFF bytes: a NaN as double, -1 as int -- emu_rt.cpp; the counter is this library's own, beside the one libworld_emu.so exports)
+inline std::atomic<unsigned long long> g_poisoned_bytes{0};
+static inline void dpoison(void *dst, size_t n, hipStream_t) { if (n) { memset(dst, 0xFF, n); g_poisoned_bytes += n; } }
+static inline void *dmalloc(size_t bytes) { void *p = malloc(bytes ? bytes : 1); dpoison(p, bytes, nullptr); return p; }
 static inline void dfree(void *p) { free(p); }
 static inline void h2d(void *dst, const void *src, size_t n, hipStream_t) { memcpy(dst, src, n); }
 static inline void d2h(void *dst, const void *src, size_t n, hipStream_t) { memcpy(dst, src, n); }

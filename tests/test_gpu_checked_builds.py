@@ -1,5 +1,5 @@
-"""The race-shaking builds (world_amd/csrc/devrt.h: -DWH_JITTER, -DWH_LDS_POISON; built by __graft_entry__.build() into
-world_amd/variants/) must compute the SAME BITS as the product library.  The kernels alias LDS regions across phases and
+"""The checked builds (world_amd/csrc/devrt.h: -DWH_JITTER, -DWH_LDS_POISON, -DWH_HBM_POISON; built by __graft_entry__.build()
+into world_amd/variants/) must compute the SAME BITS as the product library.  The kernels alias LDS regions across phases and
 place their barriers by hand; a missing barrier or a read of never-written LDS is invisible in normal runs (the wavefronts
 of a workgroup arrive together; a fresh workgroup inherits plausible data) and used to be found by reading the code
 (d4c_frame's select zeroed histograms other wavefronts were still reading).  With random multi-thousand-cycle
@@ -11,7 +11,17 @@ stay as they were.  FAMILIES below runs every other kernel family of world_amd/c
 family so that a failure names it: product twice (a family that is not deterministic cannot be judged), jitter three times,
 poison once, and once under WorldHip.profile to require that the kernels the family claims were launched.  The claims are
 the coverage table: test_every_kernel_is_claimed_by_a_family (no GPU) reads the kernel sources and fails for a __global__
-function that neither a family nor EXEMPT names, so a new kernel cannot ship without running under both builds."""
+function that neither a family nor EXEMPT names, so a new kernel cannot ship without running under both builds.
+
+Global memory gets the same treatment (-DWH_HBM_POISON: every carve of the arena and every reused device buffer refilled with
+0xFF bytes -- NaN as a double, -1 as an int -- before the call writes it).  A fresh context hides a missing initialisation
+(fresh pages are zero) and a reused one hides a read past what was written (the leftovers are the same call's, hence
+correct), so: the five workloads in one hbm context (test_hbm_poison_build_is_bit_identical); a fourth leg of every
+family, two hbm passes in one context, the second over the first's real leftovers; every family with a plain context in
+ONE context, forwards and backwards, on the product and on the hbm library (test_families_share_one_context); and a family
+over the drop-in symbols at shrinking and growing lengths (dropin-lengths).  The library's own counter of filled bytes must
+rise, so that a misspelt macro is not a clean run.  test_every_carve_poisons_the_emulated_workspace (no GPU) pins the same
+fills, which the host emulation does unconditionally, entry kind by entry kind."""
 import glob
 import os
 import re
@@ -106,6 +116,24 @@ def test_lds_poison_build_is_bit_identical():
     for (name, *_), a, b in zip(work, want, got):
         assert all(np.isfinite(arr).all() for utt in b for arr in utt), f"poison build, {name}: a NaN pattern reached the output"
         assert _same(a, b), f"poison build, {name}: results differ from the product build's"
+
+
+@gpu
+def test_hbm_poison_build_is_bit_identical():
+    """the five workloads in ONE context of the -DWH_HBM_POISON library: every stage of every workload finds its workspace --
+    grown by the 48 kHz batch, reused by the shorter shapes behind it -- refilled with 0xFF bytes"""
+    from world_amd.api import LIB_PATH, load_library
+    work = _workloads()
+    want = _run(LIB_PATH, work)[0]
+    counter = _poison_counter(load_library(_lib("hbm")))
+    before = counter()
+    got = _run(_lib("hbm"), work)[0]
+    assert counter() > before, "hbm build: the poison counter did not rise"
+    for (name, *_), a, b in zip(work, want, got):
+        for ua, ub in zip(a, b):
+            for x, y in zip(ua, ub):
+                assert x.shape == y.shape and np.all(np.isfinite(y) | ~np.isfinite(x)), f"hbm build, {name}: a NaN pattern reached the output"
+        assert _same(a, b), f"hbm build, {name}: results differ from the product build's"
 
 
 # ==== every other kernel family ==============================================================================================
@@ -601,6 +629,41 @@ def run_plumbing(wh):
     return out
 
 
+# ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
+DROPIN_SECONDS = (0.5, 0.2, 0.31)
+
+
+def run_dropin_lengths(wh):
+    """the reference's own entry points (HostAPI on the library under test, as run_realtime does) on one 16 kHz utterance cut
+    to 0.5 s, 0.2 s and 0.31 s, in that order, through the library's one slot pool: the slot's device buffers and its resident
+    copy of the signal are sized by the longest call so far, so the shorter calls run with a longer call's tail behind their
+    data (and, from the second pass in a process on, the 0.5 s call with the 0.31 s call's data under its own)"""
+    from world_amd import synth
+    from world_amd.api import HostAPI
+    fs, ndim = 16000, 25
+
+    def make():
+        full = synth.utterance(3, fs, max(DROPIN_SECONDS)).numpy()
+        return [np.ascontiguousarray(full[:int(s * fs)]) for s in DROPIN_SECONDS]
+    H = HostAPI(wh.lib_path)
+    fft = H.cheaptrick_fft_size(fs)
+    out = []
+    for sec, x in zip(DROPIN_SECONDS, _once(("dropin cuts",), make)):
+        tp, f0 = H.harvest(x, fs)
+        tp_d, f0_d = H.dio(x, fs)
+        f0_s = H.stonemask(x, fs, tp_d, f0_d)
+        sp = H.cheaptrick(x, fs, tp, f0)
+        ap = H.d4c(x, fs, tp, f0, fft)
+        assert sp.shape == ap.shape == (len(f0), fft // 2 + 1) and (f0 > 0).any()
+        y = H.synthesis(f0, sp, ap, fft, 5.0, fs, len(x))
+        coded_sp, coded_ap = H.code_spectral_envelope(sp, fs, fft, ndim), H.code_aperiodicity(ap, fs, fft)
+        out += [(f"{sec} s {name}", a) for name, a in (
+            ("harvest tpos", tp), ("harvest f0", f0), ("dio tpos", tp_d), ("dio f0", f0_d), ("stonemask f0", f0_s), ("sp", sp), ("ap", ap),
+            ("y", y), ("coded sp", coded_sp), ("decoded sp", H.decode_spectral_envelope(coded_sp, fs, fft)), ("coded ap", coded_ap),
+            ("decoded ap", H.decode_aperiodicity(coded_ap, fs, fft)))]
+    return out
+
+
 # ---- the coverage table: which kernels (world_amd/csrc: __global__ void NAME) each family launches -------------------------
 _CONTOUR = ("hc_step12_sections", "hc_extend", "hc_merge", "hc_smooth", "hc_output")
 _HARVEST_TAIL = ("hv_remove_mean", "hv_raw_candidates", "hv_detect", "hv_prune") + _CONTOUR
@@ -611,6 +674,10 @@ _HARVEST_FFT = ("hv_decimate_fwd", "hv_decimate_bwd", "hv_band_spectra", "hv_blo
 # Measured on one MI355X, the whole test of a family (seven passes and four contexts): modify-frames 0.78 s,
 # harvest-direct-form 0.68 s, gmm 0.24 s, realtime 0.17 s, mcep 0.14 s, synthesis 0.13 s, mlpg and shared-device 0.12 s, every
 # other family below 0.1 s; one jitter pass 0.17 s (harvest-direct-form) and 0.03 s or less elsewhere.
+# With the hbm leg (nine passes and five contexts): harvest-direct-form 0.85 s, modify-frames 0.82 s, mlpg 0.28 s, dropin-lengths
+# 0.26 s, realtime 0.22 s, mcep 0.18 s, gmm 0.16 s, shared-device and synthesis 0.15 s, every other family 0.12 s or less; one
+# hbm pass 0.17 s (harvest-direct-form) and 0.03 s or less elsewhere, filling 3 MiB (mcep) to 486 MiB (dropin-lengths: every
+# slot buffer at every call); test_families_share_one_context 0.6 s on either library.
 FAMILIES = {
     # name: (run, the kernels it must launch, WorldHip keyword arguments)
     "harvest-direct-form": (run_harvest_direct_form, ("hv_decimate_fwd", "hv_decimate_bwd", "hv_band_quirk", "hv_band_events", "hv_compact_events")
@@ -640,7 +707,14 @@ FAMILIES = {
     "plumbing": (run_plumbing, ("ex_pack_rows", "ex_unpack_rows", "pcm16_to_double", "pcm_bytes_to_double", "double_to_pcm16",
                                 "fft_probe_rfft<3, 11>", "fft_probe_irfft<3, 11>", "fft_probe_rfft<3>", "fft_probe_irfft<3>",
                                 "fft_probe_rfft<4>", "fft_probe_irfft<4>"), {}),
+    "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
+                                                            "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
+                       + _SYNTHESIS, {}),
 }
+# Families whose calls carve nothing from the arena and keep no buffer of their own between calls (cached tables apart): a
+# second pass in the same context has nothing to refill, so the hbm build's counter need only rise in the first (the tables'
+# allocation).  Every other family must see it rise in both passes.
+NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing")
 # profile labels that are not the kernel's own name (devrt::launch_blocks("label", kernel<...>, ...))
 LABELS = {"ct_frame_coded": "ct_frame"}
 # kernels that run only while a process-wide table is built: asserted on the first pass of the jitter library, which nothing
@@ -693,6 +767,104 @@ def test_every_kernel_is_claimed_by_a_family():
     assert unclaimed_kernels(source, claimed_kernels() - {"align_dp"}, EXEMPT) == ["align_dp"]
 
 
+def _exports(path, symbol):
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return any(line.split()[-1] == symbol for line in out.splitlines() if line.strip())
+
+
+def test_every_carve_poisons_the_emulated_workspace():
+    """The host emulation refills what -DWH_HBM_POISON refills (devrt::dpoison, 0xFF bytes = NaN / -1), always: the counter
+    rises across a call of each entry kind -- begin_stage (Harvest), a spectral stage without and with reuse_offsets,
+    hold_at_floor (resynthesize), a drop-in call -- by at least what that kind promises to fill, and the results stay what
+    they were: the reused offsets and the LoveTrain pass survive a reuse call's fill, the analysis held at the floor survives
+    the stages' fills above it.  Only the checked build exports the counter."""
+    import ctypes as C
+    from backends import emu_library, new_context
+    from world_amd import synth
+    from world_amd.api import LIB_PATH, CheapTrickOption, D4COption, HarvestOption, HostAPI, cheaptrick_fft_size, frame_count, modifications
+    assert not _exports(LIB_PATH, "world_hip_debug_poisoned_bytes"), "the product library exports the checked build's counter"
+    assert _exports(_lib("hbm"), "world_hip_debug_poisoned_bytes"), "libworld_hip_hbm.so was built without -DWH_HBM_POISON"
+    L = emu_library()
+    L.world_hip_debug_poisoned_bytes.restype = C.c_ulonglong
+    poisoned = L.world_hip_debug_poisoned_bytes
+    fs, ip = 16000, C.POINTER(C.c_int)
+    vp = lambda a: C.c_void_p(a.ctypes.data)
+    h, c, d = HarvestOption(71.0, 800.0, 5.0), CheapTrickOption(-0.15, 71.0, cheaptrick_fft_size(fs, 71.0)), D4COption(0.85)
+    fft, nb = c.fft_size, c.fft_size // 2 + 1
+
+    def batch(seconds):
+        xs = [synth.vowel(fs, s, seed=11 + u, base_f0=140.0 + 60 * u).numpy() for u, s in enumerate(seconds)]
+        x = np.zeros((len(xs), max(len(v) for v in xs)))
+        for u, v in enumerate(xs):
+            x[u, :len(v)] = v
+        xl = np.array([len(v) for v in xs], dtype=np.int32)
+        return x, xl, np.array([frame_count(fs, int(n), 5.0) for n in xl], dtype=np.int32)
+
+    ctx = new_context(L)
+    try:
+        def harvest(x, xl, nf):
+            F = int(nf.max())
+            tp, f0 = np.zeros((len(xl), F)), np.zeros((len(xl), F))
+            assert L.world_hip_harvest_batch(ctx, len(xl), fs, vp(x), x.shape[1], xl.ctypes.data_as(ip), C.byref(h), F, vp(tp), vp(f0)) == 0
+            return tp, f0
+
+        # begin_stage: a long call sizes the arena, the short one behind it finds all of it refilled (and allocates nothing)
+        harvest(*batch((0.3, 0.22)))
+        x, xl, nf = batch((0.12, 0.09))
+        B, F = len(xl), int(nf.max())
+        cap, before = int(L.world_hip_workspace_bytes(ctx)), poisoned()
+        tp, f0 = harvest(x, xl, nf)
+        assert cap > 0 and int(L.world_hip_workspace_bytes(ctx)) == cap and poisoned() - before >= cap
+        assert (f0 > 0).any() and np.isfinite(f0).all()
+        tp_lone, f0_lone = harvest(x[:1, :xl[0]].copy(), xl[:1], nf[:1])
+        assert np.array_equal(f0_lone[0], f0[0, :nf[0]])
+
+        # the spectral stages, whole and in frame ranges: fresh claims are refilled; a reuse_offsets call refills nothing of
+        # CheapTrick's (all it carves is the prepared offsets) and only the scratch behind D4C's prepared arrays
+        args = (ctx, B, fs, vp(x), x.shape[1], xl.ctypes.data_as(ip), nf.ctypes.data_as(ip), F, vp(tp), vp(f0))
+        sp_full, ap_full = np.zeros((B, F, nb)), np.zeros((B, F, nb))
+        assert L.world_hip_cheaptrick_batch(*args, C.byref(c), vp(sp_full)) == 0
+        assert L.world_hip_d4c_batch(*args, fft, C.byref(d), vp(ap_full)) == 0
+        assert np.isfinite(sp_full).all() and np.isfinite(ap_full).all() and (ap_full[f0 > 0] < 0.5).any()
+        sp, ap = np.full((B, F, nb), -1.0), np.full((B, F, nb), -1.0)
+        rises = {}
+        for lo, hi, reuse in ((0, 9, 0), (9, 17, 1), (17, F, 1)):
+            before = poisoned()
+            assert L.world_hip_cheaptrick_batch_range(*args, C.byref(c), lo, hi, reuse, vp(sp)) == 0, L.world_hip_last_error()
+            rises["ct", reuse] = poisoned() - before
+            before = poisoned()
+            assert L.world_hip_d4c_batch_range(*args, fft, C.byref(d), lo, hi, reuse, vp(ap)) == 0, L.world_hip_last_error()
+            rises["d4c", reuse] = poisoned() - before
+        assert rises["ct", 0] >= 4 * B * F and rises["ct", 1] == 0
+        assert rises["d4c", 1] >= 8 * 16 * B * F and rises["d4c", 0] >= rises["d4c", 1] + 8 * B * F + 4 * 2 * B * F
+        for u, n in enumerate(nf):                                              # what the first range prepared was still intact
+            assert np.array_equal(sp[u, :n], sp_full[u, :n]) and np.array_equal(ap[u, :n], ap_full[u, :n])
+
+        # hold_at_floor: the whole arena before its carve; the analysis it holds there survives the stages above
+        yl = np.array([L.world_hip_resynthesis_length(fs, int(n), 5.0, 1.0) for n in nf], dtype=np.int32)
+        y = np.zeros((B, int(yl.max())))
+        before = poisoned()
+        assert L.world_hip_resynthesize_batch(ctx, B, fs, vp(x), x.shape[1], xl.ctypes.data_as(ip), C.byref(h), C.byref(c), C.byref(d),
+                                              modifications(B, 1.0, 1.0, None), 1.0, yl.ctypes.data_as(ip), y.shape[1], vp(y)) == 0
+        assert poisoned() - before >= int(L.world_hip_workspace_bytes(ctx))
+        y2 = np.zeros_like(y)
+        assert L.world_hip_synthesis_batch(ctx, B, fs, 5.0, fft, nf.ctypes.data_as(ip), F, vp(f0), vp(sp_full), vp(ap_full),
+                                           yl.ctypes.data_as(ip), y.shape[1], vp(y2)) == 0
+        assert np.array_equal(y, y2) and np.max(np.abs(y)) > 0
+
+        # a drop-in call: the slot's buffers and the resident signal, a shorter signal behind a longer one
+        H = HostAPI(L._name)
+        x_long, x_short = np.ascontiguousarray(x[0, :xl[0]]), np.ascontiguousarray(x[1, :xl[1]])
+        H.harvest(x_long, fs)
+        before = poisoned()
+        tp_d, f0_d = H.harvest(x_short, fs)
+        assert poisoned() - before >= 8 * len(x_long) + 2 * 8 * int(nf[0])     # the resident signal's capacity, two frame buffers'
+        assert np.array_equal(f0_d, f0[1, :nf[1]]) and np.array_equal(tp_d, tp[1, :nf[1]])
+    finally:
+        L.world_hip_destroy(ctx)
+
+
 # ---- the helper -----------------------------------------------------------------------------------------------------------
 def _open(lib_path, kw):
     from world_amd.api import WorldHip
@@ -701,13 +873,25 @@ def _open(lib_path, kw):
     return wh
 
 
-def _run_family(lib_path, run, kw, repeats=1, profile_first=False):
-    """-> ([result of each pass], {kernel: launches} of the first pass when profiled, seconds per pass)"""
+def _poison_counter(lib):
+    """world_hip_debug_poisoned_bytes of a loaded -DWH_HBM_POISON library: absent, the build is not what its name says"""
+    import ctypes as C
+    fn = getattr(lib, "world_hip_debug_poisoned_bytes", None)
+    assert fn is not None, "the library does not export world_hip_debug_poisoned_bytes: it was not built with -DWH_HBM_POISON"
+    fn.restype = C.c_ulonglong
+    return fn
+
+
+def _run_family(lib_path, run, kw, repeats=1, profile_first=False, poisoned=None):
+    """-> ([result of each pass], {kernel: launches} of the first pass when profiled, seconds per pass); poisoned: a list
+    that receives the bytes the library's dpoison filled during each pass (the hbm build)"""
     import torch
     wh = _open(lib_path, kw)
     results, launches, seconds = [], {}, []
+    counter = _poison_counter(wh.lib) if poisoned is not None else None
     try:
         for rep in range(repeats):
+            before = counter() if counter else 0
             t0 = time.perf_counter()
             if profile_first and rep == 0:
                 got = []
@@ -720,6 +904,8 @@ def _run_family(lib_path, run, kw, repeats=1, profile_first=False):
             torch.cuda.synchronize()
             seconds.append(time.perf_counter() - t0)
             results.append(res)
+            if counter:
+                poisoned.append(counter() - before)
     finally:
         wh.close()
     return results, launches, seconds
@@ -729,6 +915,14 @@ def _differences(want, got):
     from backends import same_bits
     assert [n for n, _ in want] == [n for n, _ in got], "the passes returned different outputs"
     return [n for (n, a), (_, b) in zip(want, got) if not same_bits(a, b)]
+
+
+def _no_poison_in(family, what, want, got):
+    """finite wherever the product build's result is"""
+    for (name, a), (_, b) in zip(want, got):
+        a, b = np.asarray(a), np.asarray(b)
+        if a.dtype.kind == "f":
+            assert a.shape == b.shape and np.all(np.isfinite(b) | ~np.isfinite(a)), f"{family}: {what}, {name}: a NaN pattern reached the output"
 
 
 def _launched(launches, claim):
@@ -745,6 +939,7 @@ def test_family_on_the_checked_builds(family):
     run, kernels, kw = FAMILIES[family]
     (first, second), _, t_product = _run_family(LIB_PATH, run, kw, repeats=2)
     assert first, f"{family}: nothing to compare"
+    _made.setdefault(("fresh", family), first)                # (test_families_share_one_context compares with it)
     bad = _differences(first, second)
     assert not bad, f"{family}: the product build is not deterministic in {bad[:8]}: the family cannot be judged"
     # routes: what the family claims was launched
@@ -766,5 +961,55 @@ def test_family_on_the_checked_builds(family):
             assert a.shape == b.shape and np.all(np.isfinite(b) | ~np.isfinite(a)), f"{family}: poison build, {name}: a NaN pattern reached the output"
     bad = _differences(first, res)
     assert not bad, f"{family}: poison build: {bad[:8]} differ from the product build's"
-    print(f"{family}: product {min(t_product):.2f} s, jitter {max(t_jitter):.2f} s a pass, poison {t_poison[0]:.2f} s; "
-          f"{len(first)} outputs, {sum(launches.values())} launches")
+    # hbm: two passes in one context, every carve refilled with 0xFF bytes -- the first over fresh allocations, the second over
+    # the first's real leftovers.  No NaN where the product build has a number, the product's bits, and fills that happened
+    filled = []
+    passes, _, t_hbm = _run_family(_lib("hbm"), run, kw, repeats=2, poisoned=filled)
+    for rep, res in enumerate(passes):
+        _no_poison_in(family, f"hbm build, pass {rep}", first, res)
+        bad = _differences(first, res)
+        assert not bad, f"{family}: hbm build, pass {rep}: {bad[:8]} differ from the product build's"
+    assert len(filled) == 2 and filled[0] > 0 and (filled[1] > 0 or family in NO_WORKSPACE), \
+        f"{family}: hbm build: the poison counter rose by {filled} bytes over the two passes"
+    print(f"{family}: product {min(t_product):.2f} s, jitter {max(t_jitter):.2f} s a pass, poison {t_poison[0]:.2f} s, "
+          f"hbm {max(t_hbm):.2f} s a pass ({max(filled) / 2 ** 20:.1f} MiB filled); {len(first)} outputs, {sum(launches.values())} launches")
+
+
+def _fresh(family):
+    """the family's result in a fresh context of the product library, computed once per process"""
+    from world_amd.api import LIB_PATH
+    run, _, kw = FAMILIES[family]
+    return _once(("fresh", family), lambda: _run_family(LIB_PATH, run, kw)[0][0])
+
+
+@gpu
+@pytest.mark.parametrize("build", ["product", "hbm"])
+def test_families_share_one_context(build):
+    """Every family whose WorldHip takes no keyword arguments, in ONE context: in table order, then in reverse order, so that
+    every stage meets the leftovers of another feature's calls -- MLPG's 1- and 2-frame utterances carve where a long Harvest arena lay, the
+    drop-in slots and the cached tables are whatever the families before left -- and must still compute its fresh-context
+    result.  On the product library this is the only test where a stage reads behind REAL foreign leftovers; on the hbm
+    library the same sequence runs with every carve refilled.  (shared-device keeps a context of its own: its hint is a
+    property of the context.)"""
+    import torch
+    from world_amd.api import LIB_PATH
+    names = [f for f, (_, _, kw) in FAMILIES.items() if not kw]
+    assert len(names) == len(FAMILIES) - 1 and "shared-device" not in names
+    want = {f: _fresh(f) for f in names}
+    wh = _open(LIB_PATH if build == "product" else _lib(build), {})
+    counter = _poison_counter(wh.lib) if build == "hbm" else None
+    t0 = time.perf_counter()
+    try:
+        for order, sequence in (("table order", names), ("reverse order", names[::-1])):
+            before = counter() if counter else 0
+            for f in sequence:
+                res = FAMILIES[f][0](wh)
+                torch.cuda.synchronize()
+                if build == "hbm":
+                    _no_poison_in(f, f"{build} build, shared context, {order}", want[f], res)
+                bad = _differences(want[f], res)
+                assert not bad, f"{f}: {build} build, shared context, {order}: {bad[:8]} differ from the fresh context's"
+            assert counter is None or counter() > before, f"hbm build, shared context, {order}: the poison counter did not rise"
+    finally:
+        wh.close()
+    print(f"shared context, {build}: {len(names)} families twice in {time.perf_counter() - t0:.2f} s")

@@ -65,9 +65,10 @@ def build(force=False, verbose=False):
 
 
 VAR_DIR = os.path.join(HERE, "variants")
-# the race-shaking builds of devrt.h (test infrastructure: the GPU suite requires their results to be bit-identical to the
-# product library's).  Not the product: nothing loads them unless a test names them.
-CHECKED = {"jitter": "-DWH_JITTER", "poison": "-DWH_LDS_POISON"}
+# the checked builds of devrt.h -- two that shake races out, one that refills every workspace carve and reused device buffer
+# with 0xFF bytes (test infrastructure: the GPU suite requires their results to be bit-identical to the product library's).
+# Not the product: nothing loads them unless a test names them.
+CHECKED = {"jitter": "-DWH_JITTER", "poison": "-DWH_LDS_POISON", "hbm": "-DWH_HBM_POISON"}
 
 
 def build_variant(name, flags):

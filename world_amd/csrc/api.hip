@@ -455,6 +455,7 @@ static void arena_reset(WorldHipContext *c) {
 template <class Carve> static void begin_stage(WorldHipContext *c, Carve carve) {
   ensure_arena(c, measure(carve));
   arena_reset(c);
+  devrt::dpoison(c->arena.base + c->arena.floor, c->arena.cap - c->arena.floor, c->stream);   // (what a call holds at the floor stays)
   carve(c->arena);
   open_uploads(c);
 }
@@ -472,6 +473,7 @@ template <class Carve, class Body> static void hold_at_floor(WorldHipContext *c,
     c->arena.floor = 0;
     ensure_arena(c, std::max(measure(carve), want));
     arena_reset(c);
+    devrt::dpoison(c->arena.base, c->arena.cap, c->stream);
     carve(c->arena);
     c->arena.floor = c->arena.used;
     try {
@@ -545,6 +547,9 @@ static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c,
     t.fft = 1 << ct->lg_fft; t.f0 = ct->f0; t.tpos = ct->tpos; t.opt = ct->f0_floor;
     t.lo = 0; t.hi = c->arena.used;
     claim_prepared(c, c->prep_ct, c->prep_d4c, t, ct->skip_prepare != 0, "CheapTrick");
+    // (the claim starts at 0 whatever a call holds at the floor, the carve above it: only the carve is this stage's to lose.
+    // With skip_prepare everything CheapTrick carves is what the earlier call prepared.)
+    if (!ct->skip_prepare) devrt::dpoison(c->arena.base + c->arena.floor, c->arena.used - c->arena.floor, c->stream);
   }
   if (d4c) {
     c->arena.reset();
@@ -552,6 +557,10 @@ static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c,
     t.fft = d4c->fft_out; t.f0 = d4c->f0; t.tpos = d4c->tpos; t.opt = d4c->threshold;
     t.lo = reinterpret_cast<char *>(d4c->ap0) - c->arena.base; t.hi = c->arena.used;      // (ap0: D4C's first array)
     claim_prepared(c, c->prep_d4c, c->prep_ct, t, d4c->skip_prepare != 0, "D4C");
+    // from ap0: CheapTrick's part below it survives a D4C call, as the layout intends.  With skip_prepare ap0 .. draws1 are
+    // what the earlier call prepared; coarse and park_ws behind them are scratch that every call writes before it reads.
+    char *lo = reinterpret_cast<char *>(d4c->skip_prepare ? d4c->coarse : d4c->ap0);
+    devrt::dpoison(lo, c->arena.base + c->arena.used - lo, c->stream);
   }
 }
 
@@ -1356,6 +1365,7 @@ static void analyze_into_records(WorldHipContext *c, int n_utt, int fs, const do
     put_table(c, c->d_pk, 2 * fr + fr / 4);
     c->pk_cap = 2 * fr + fr / 4;
   }
+  devrt::dpoison(c->d_pk, sizeof(double) * c->pk_cap, c->stream);
   double *d_tpos = c->d_pk, *d_f0 = c->d_pk + fr;
   run_harvest(c, n_utt, fs, d_x, x_stride, x_length, hopt, f_stride, d_tpos, d_f0);
   RowLayout lay_sp, lay_ap;
@@ -2515,6 +2525,11 @@ int world_hip_verify_tables(WorldHipContext *c) {
   return guarded(c, [&] { noise_table_verify(c->device, c->stream); });
 }
 
+#ifdef WORLD_EMU
+// the host emulation always poisons (devrt.h): its counter, as the -DWH_HBM_POISON build exports it from devrt.cpp
+unsigned long long world_hip_debug_poisoned_bytes(void) { return __atomic_load_n(&devrt::g_poisoned_bytes, __ATOMIC_RELAXED); }
+#endif
+
 // per-kernel HIP-event timing (used by bench.py for the roofline figure)
 void world_hip_profile_enable(int on) {
 #ifndef WORLD_EMU
@@ -2947,6 +2962,7 @@ int world_hip_analyze_sharded(int n_dev, WorldHipContext *const *ctxs, int n_utt
             memcpy(h + (size_t)j * ch.max_len, x[i], sizeof(double) * x_length[i]);
             if (x_length[i] < ch.max_len) memset(h + (size_t)j * ch.max_len + x_length[i], 0, sizeof(double) * (ch.max_len - x_length[i]));
           }
+          devrt::dpoison(dx, sizeof(double) * c->xin_cap, c->stream);
           devrt::h2d(dx, h, sizeof(double) * (size_t)b * ch.max_len, c->stream);
           run_analyze_packed(c, b, fs, dx, ch.max_len, xl.data(), hopt, copt, dopt, ch.first, d_blocks[r], cols);
           devrt::event_record(staged[half], c->stream);

@@ -1,6 +1,9 @@
 // devrt.cpp -- HIP runtime plumbing for the product build (gfx950).
 #include "devrt.h"
 
+#ifdef WH_HBM_POISON
+#include <atomic>
+#endif
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,9 +51,23 @@ void check(hipError_t e, const char *what) {
   if (e != hipSuccess)
     throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
 }
+#ifdef WH_HBM_POISON
+// the checked build of devrt.h: what dpoison has filled so far, read by the tests through the one symbol only this build exports
+static std::atomic<unsigned long long> g_poisoned_bytes{0};
+void dpoison(void *dst, size_t n, hipStream_t s) {
+  if (!n) return;
+  check(hipMemsetAsync(dst, 0xFF, n, s), "hipMemsetAsync (poison)");
+  g_poisoned_bytes += n;
+}
+#endif
 void *dmalloc(size_t bytes) {
   void *p = nullptr;
   check(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc");
+#ifdef WH_HBM_POISON
+  // at once: the contexts' streams do not wait for the null stream, so the fill is finished before anyone gets the pointer
+  dpoison(p, bytes, nullptr);
+  check(hipStreamSynchronize(nullptr), "hipStreamSynchronize (poison)");
+#endif
   return p;
 }
 void dfree(void *p) { if (p) check(hipFree(p), "hipFree"); }
@@ -194,3 +211,9 @@ std::string prof_collect() {
 }
 
 }  // namespace devrt
+
+#ifdef WH_HBM_POISON
+extern "C" __attribute__((visibility("default"))) unsigned long long world_hip_debug_poisoned_bytes(void) {
+  return devrt::g_poisoned_bytes.load();
+}
+#endif

@@ -69,6 +69,14 @@ static inline void h2d(void *dst, const void *src, size_t n, hipStream_t) { memc
 static inline void d2h(void *dst, const void *src, size_t n, hipStream_t) { memcpy(dst, src, n); }
 static inline void d2d(void *dst, const void *src, size_t n, hipStream_t) { memcpy(dst, src, n); }
 static inline void dzero(void *dst, size_t n, hipStream_t) { memset(dst, 0, n); }
+// 0xFF bytes, counted (the checked builds below: -DWH_HBM_POISON; here always).  Defined here, not in the emulation's runtime
+// (tests/emu/emu_rt.cpp), so that these sources need nothing of it beyond what they always did; api.hip exports the counter.
+inline unsigned long long g_poisoned_bytes = 0;
+static inline void dpoison(void *dst, size_t n, hipStream_t) {
+  if (!n) return;
+  memset(dst, 0xFF, n);
+  __atomic_fetch_add(&g_poisoned_bytes, (unsigned long long)n, __ATOMIC_RELAXED);
+}
 static inline void sync(hipStream_t) {}
 static inline void set_device(int) {}
 static inline int current_device() { return 0; }
@@ -127,6 +135,12 @@ void h2d(void *dst, const void *src, size_t n, hipStream_t s);
 void d2h(void *dst, const void *src, size_t n, hipStream_t s);
 void d2d(void *dst, const void *src, size_t n, hipStream_t s);
 void dzero(void *dst, size_t n, hipStream_t s);
+// memory whose contents the coming call may not rely on: nothing in the product, 0xFF bytes under -DWH_HBM_POISON (below)
+#ifdef WH_HBM_POISON
+void dpoison(void *dst, size_t n, hipStream_t s);
+#else
+static inline void dpoison(void *, size_t, hipStream_t) {}
+#endif
 void sync(hipStream_t s);
 void set_device(int device);
 int current_device();
@@ -267,7 +281,20 @@ __device__ __forceinline__ int xcd_grouped(int b, int n) {
 //                    otherwise inherits the previous one's data, usually the same kernel's: plausible values), and
 //                    lds_dead(ptr, n) marks fill a region whose contents nobody may read any more.  (This build ADDS
 //                    barriers around the fills, so it is a separate build from the jitter one.)
-// The GPU suite runs EVERY kernel family on both -- the analysis workloads, and one workload per family of synthesis,
+// Global memory gives the same kind of bug more room: every stage carves its scratch from one grow-only arena that nothing
+// clears between calls, and the buffers outside it (drop-in slots, the resident signal, d_pk, d_xin) are reused across calls
+// of different sizes with slack behind the live data.  A fresh hipMalloc is usually zero pages and a repeated call finds
+// its own correct leftovers, so a counter nobody initialised or a read one element past what was written passes both.
+//   -DWH_HBM_POISON  devrt::dpoison(ptr, bytes, stream) -- an empty inline in the product -- fills with 0xFF bytes (a NaN
+//                    as double or float, -1 as int, UINT_MAX as unsigned): every dmalloc at once, and on the call's stream
+//                    the arena above its floor at every begin_stage, the whole arena at every hold_at_floor attempt, a
+//                    spectral stage's claim (not what a reuse_offsets call finds prepared: only its pure scratch), a
+//                    drop-in slot buffer's whole capacity whenever a DevBuf takes it, the resident signal's before an
+//                    upload, d_pk and d_xin before the call that fills them.  The library then exports
+//                    world_hip_debug_poisoned_bytes(), so that a misspelt macro cannot pass as a clean run.  The real-time
+//                    buffers keep state between calls by design and get the allocation's fill only; caller-owned memory
+//                    is the caller's.  The host emulations (tests/emu) do the same fills unconditionally.
+// The GPU suite runs EVERY kernel family on all three -- the analysis workloads, and one workload per family of synthesis,
 // real-time synthesis, the coders, modification, alignment, morph, resampling, mel-cepstra, MLPG, the Gaussian mixture
 // and the plumbing kernels -- and requires results bit-identical to the product build's.  The families name the kernels
 // they launch; a CPU test of the same file reads these sources and fails for a __global__ function no family names (the

@@ -358,6 +358,7 @@ struct DevBuf {
       io.cap[slot] = bytes + bytes / 8;
     }
     p = io.dev[slot];
+    devrt::dpoison(p, io.cap[slot], io.ctx->stream);   // (the last call's data, perhaps a longer call's, lies behind this one's)
   }
   ~DevBuf() { --tls_slot->next; }
   DevBuf(const DevBuf &) = delete;
@@ -422,6 +423,7 @@ template <class Launch> static void run_on_signal(DropinSlot &io, const double *
     io.d_x = static_cast<double *>(devrt::dmalloc(bytes + bytes / 8));
     io.x_cap = (bytes + bytes / 8) / sizeof(double);
   }
+  devrt::dpoison(io.d_x, io.x_cap * sizeof(double), io.ctx->stream);
   upload_bytes(io, io.d_x, x, bytes);
   launch(static_cast<const double *>(io.d_x));
   if (P.cache_x) {
