@@ -404,7 +404,7 @@ WORLD_HIP_API int world_hip_synthesis_records(WorldHipContext *ctx, int n_utt, i
 WORLD_HIP_API int world_hip_probe_machine(WorldHipContext *ctx, double *values, int n_values);
 /* The per-frame real FFT of the path in isolation (the reference's fft_plan_dft_r2c_1d / _c2r_1d +
  * fft_execute, src/world/fft.h:22-44, as re-implemented in csrc/fft.h): `batch` transforms of 2^lg_n
- * points (256 .. 16384), one workgroup each, straight from and to HBM -- the test and microbenchmark hook.
+ * points (64 .. 16384), one workgroup each, straight from and to HBM -- the test and microbenchmark hook.
  *   rfft : d_in [batch][N] -> d_spectrum [batch][N/2+1][2] (re, im), X[k] = sum x[n] e^{-2 pi i k n / N}
  *   irfft: d_spectrum -> d_out [batch][N] = N * irfft (unscaled like the reference's c2r; Im of DC / Nyquist ignored)
  * max_lr = 3 (radix-8 plan) or 4 (radix-16 plan); threads = workgroup size, 0 = one butterfly per thread;
@@ -414,6 +414,37 @@ WORLD_HIP_API int world_hip_probe_rfft(WorldHipContext *ctx, int lg_n, int max_l
                                        long long batch, const double *d_in, double *d_spectrum);
 WORLD_HIP_API int world_hip_probe_irfft(WorldHipContext *ctx, int lg_n, int max_lr, int threads, int static_plan,
                                         long long batch, const double *d_spectrum, double *d_out);
+/* Every composition of csrc/fft.h's entry points that a stage kernel runs, in isolation: `batch` transforms of 2^lg_n points,
+ * one workgroup of `threads` threads each, with the template arguments of the kernels named below.  swizzle = the LDS slot
+ * map the probe is compiled with: 0 the shipped one, 1 d4c.hip's.  Real rows are [batch][N], spectra [batch][N/2+1][2]
+ * (re, im), plain complex rows [batch][N][2].  threads = 64 .. 1024 in steps of 64 unless the mode fixes it.  Anything that
+ * is not listed fails with a message naming what is; the one-lane host emulation has modes 1 .. 6, 18 and 19 only.
+ * Swizzle 0 has modes 1 .. 12, 18 and 19; swizzle 1 has what d4c.hip runs: 1 (max_lr 3), 7 (2^11), 13 .. 19.
+ *    1  r2c, block_rfft<max_lr>, the twiddle table of the inner N/2-point transform   2^6 .. 2^14, max_lr 3 | 4
+ *       (ct_frame, hv_band_spectra, d4c_lovetrain)
+ *    2  c2r unscaled, block_irfft<max_lr> (ct_frame, sy_pulse, rt_pulse)               2^6 .. 2^14, max_lr 3 | 4
+ *    3  r2c, block_rfft_from<3>: the first stage reads a functor (sy_pulse, ct_frame)  2^6 .. 2^14, max_lr 3
+ *    4  r2c, block_rfft<4>, the table staged at N itself (codec_code_sp, ct_frame_coded) 2^6 .. 2^13, max_lr 4
+ *    5  complex forward, block_cfft_dif, default plan (decode_sp_row)                  2^6 .. 2^13, max_lr 4
+ *    6  complex forward of a row that is zero beyond element N/2, block_cfft_dif_from<3>, the table one level coarser than
+ *       the transform (minimum_phase of synthesis.hip)                                  2^6 .. 2^13, max_lr 3
+ *    7, 8, 9  modes 1, 2, 3 with the length a compile-time constant (ct_frame, d4c_lovetrain) 2^10 .. 2^12, max_lr 3
+ *   10  r2c, block_cfft_dif_static<11, 3, 256> + rfft_merge_items<5, 256> (hv_block_spectra)      2^12, 256 threads
+ *   11  c2r unscaled, irfft_pretwiddle_items_w<5, 256> with twiddles by rotation + block_cfft_dit_static<11, 3, 256>
+ *       (hv_band_events_fft)                                                                      2^12, 256 threads
+ *   12  c2r unscaled, irfft_pretwiddle_items<5, 256> + the same inverse (no caller: fft.h promises mode 2's values)
+ *   13  r2c TIMES TWO, block_cfft_dif_static<11, 3, 256> + rfft_merge_items_w<5, 256, true> with twiddles by rotation
+ *       (d4c_lovetrain's 4096-point shape)                                                        2^12, 256 threads
+ *   14  r2c by d4c_frame's route: quarter-wave table two levels coarser than the merge's, direct tables for the two inner
+ *       radix-8 stages, block_cfft_dif_static<lg-1, 3, N/16> + rfft_merge_items_rot<K, N/16>   2^11 .. 2^14, N/16 threads
+ *   15  the same TIMES TWO: rfft_merge_items_rot<K, N/16, true>
+ *   16  mode 14 with the run-time plan's stages (block_cfft_dif<3>) for the static ones (no caller: static == run-time)
+ *   17  no input read: one complex row of the twiddles e^{-2 pi i k / 2^level} d4c_frame's staging serves -- [0, N/128) level
+ *       lg-4 and [N/128, N/128 + N/1024) level lg-7 from the direct tables, the same from the plain table at N/4,
+ *       [3N/8, 3N/8 + N/16) level lg-1, [N/2, N) level lg (k < N/2), zero elsewhere
+ *   18, 19  dft8<true> / dft8_head2<true> (the latter on the first two values) on `batch` rows of 8 complex values; lg_n = 3 */
+WORLD_HIP_API int world_hip_probe_fft(WorldHipContext *ctx, int mode, int lg_n, int max_lr, int threads, int swizzle,
+                                      long long batch, const void *d_in, void *d_out);
 
 /* Multi-GPU exchange (the reference has no counterpart).  Utterances are sharded over GPUs
  * and analysed independently; a GPU's results are then packed into ONE contiguous block of records

@@ -70,6 +70,8 @@ class PortOracle(_Base):
         L.wo_d4c.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp]
         L.wo_rfft.argtypes = [C.c_int, _dp, _dp, _dp]
         L.wo_irfft_unscaled.argtypes = [C.c_int, _dp, _dp, _dp]
+        if hasattr(L, "wo_cfft"):
+            L.wo_cfft.argtypes = [C.c_int, _dp, _dp, C.c_int]
         L.wo_interp1.argtypes = [_dp, _dp, C.c_int, _dp, C.c_int, _dp]
         L.wo_decimate.argtypes = [_dp, C.c_int, C.c_int, _dp]
         L.wo_linear_smoothing.argtypes = [_dp, C.c_double, C.c_int, C.c_int, _dp]
@@ -100,6 +102,13 @@ class PortOracle(_Base):
         re = _f64(X.real); im = _f64(X.imag); out = np.zeros(n)
         self.lib.wo_irfft_unscaled(n, _p(re), _p(im), _p(out))
         return out
+
+    def cfft(self, z, sign=-1):
+        """unscaled complex transform of z (a power of two long): sign -1 forward, +1 backward"""
+        z = np.asarray(z, dtype=np.complex128)
+        re, im = _f64(z.real).copy(), _f64(z.imag).copy()
+        self.lib.wo_cfft(len(z), _p(re), _p(im), sign)
+        return re + 1j * im
 
     def interp1(self, x, y, xi):
         x, y, xi = _f64(x), _f64(y), _f64(xi)

@@ -192,6 +192,10 @@ static void cfft_double(int n, double *re, double *im, int sign) {
   free(t);
 }
 
+/* the plain complex transform in the build's own arithmetic, rounded once (tests/test_gpu_fft_routes.py: the yardstick
+ * of the product's complex transforms); sign = -1 forward, +1 backward, unscaled, in place */
+void wo_cfft(int n, double *re, double *im, int sign) { cfft_double(n, re, im, sign); }
+
 void wo_rfft(int n, const double *in, double *re, double *im) {
   wo_real *t = ralloc(n + 2 * (n / 2 + 1));
   to_real(in, n, t);

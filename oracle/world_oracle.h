@@ -28,6 +28,7 @@ double wo_randn(uint32_t s[4]);                      /* matlabfunctions.cpp:244-
 int    wo_round(double v);                           /* matlabfunctions.cpp:206-208 */
 int    wo_pow2_above(int n);                         /* common.cpp:51-54  */
 void   wo_rfft(int n, const double *in, double *re, double *im);      /* fft.cpp:49-60  */
+void   wo_cfft(int n, double *re, double *im, int sign);                /* fft.cpp:143-212: c2c, in place, unscaled */
 void   wo_irfft_unscaled(int n, const double *re, const double *im,
                          double *out);                                 /* fft.cpp:26-35  */
 void   wo_nuttall(int len, double *w);               /* common.cpp:113-121 */

@@ -145,19 +145,25 @@ def test_emulated_randomised_sweep(emu, port_oracle):
 
 def test_emulated_fft_matches_numpy():
     """csrc/fft.h (plans, slot arithmetic, merge / pre-twiddle steps) through the probe entry points of the
-    host-compiled library: index logic only -- the GPU tests (tests/test_gpu_fft.py) cover the real kernels"""
+    host-compiled library, 64 .. 16384 points: index logic only -- the GPU tests (tests/test_gpu_fft.py,
+    tests/test_gpu_fft_routes.py) cover the real kernels.  world_hip_probe_fft runs what the emulation has of the routes'
+    table: the run-time-size modes of the shipped swizzle on one lane, and d4c.hip's swizzle as the GPU runs it (the
+    lock-step library: real workgroup sizes, static plans, rotation twiddles, direct tables)."""
     import ctypes as C
+    from test_gpu_fft_routes import ROUTES, threads_of, to_complex, to_pairs
     subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
     L = C.CDLL(os.path.join(EMU_DIR, "libworld_emu.so"))
     L.world_hip_create.restype = C.c_void_p
     L.world_hip_create.argtypes = [C.c_int, C.c_void_p]
     L.world_hip_destroy.argtypes = [C.c_void_p]
+    L.world_hip_last_error.restype = C.c_char_p
     for f in (L.world_hip_probe_rfft, L.world_hip_probe_irfft):
         f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.world_hip_probe_fft.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     ctx = L.world_hip_create(0, None)
     try:
         rng = np.random.default_rng(3)
-        for lg in (8, 10, 11, 12, 13):
+        for lg in range(6, 15):
             n = 1 << lg
             for max_lr in (3, 4):
                 x = rng.standard_normal((3, n))
@@ -168,6 +174,56 @@ def test_emulated_fft_matches_numpy():
                 y = np.zeros((3, n))
                 assert L.world_hip_probe_irfft(ctx, lg, max_lr, 0, 0, 3, X.ctypes.data, y.ctypes.data) == 0
                 assert np.abs(y / n - x).max() < 1e-13
+        assert L.world_hip_probe_rfft(ctx, 5, 3, 0, 0, 3, x.ctypes.data, X.ctypes.data) != 0
+
+        ran = set()
+        for route in ROUTES:
+            if route["kind"] in ("twiddles", "dft8"):
+                continue
+            for swz in route["swz"]:
+                for lg in route["lgs"]:
+                    n, h = 1 << lg, 1 << (lg - 1)
+                    kind = "r2c" if route["kind"] == "r2c_twice" else route["kind"]
+                    if kind == "r2c":
+                        x = rng.standard_normal((3, n)); ref = np.fft.rfft(x, axis=1); rows = x; out = np.zeros((3, h + 1, 2))
+                    elif kind == "c2r":
+                        z = rng.standard_normal((3, h + 1)) + 1j * rng.standard_normal((3, h + 1))
+                        zz = z.copy(); zz[:, 0] = zz[:, 0].real; zz[:, -1] = zz[:, -1].real
+                        ref = np.fft.irfft(zz, n=n, axis=1) * n; rows = to_pairs(z); out = np.zeros((3, n))
+                    else:
+                        z = rng.standard_normal((3, n)) + 1j * rng.standard_normal((3, n))
+                        if kind == "c2c_half":
+                            z[:, h + 1:] = 0.0
+                        ref = np.fft.fft(z, axis=1); rows = to_pairs(z); out = np.zeros((3, n, 2))
+                    for max_lr in route["max_lr"]:
+                        threads = threads_of(route, lg)[-1 if route["threads"] == "N/16" else 1 if len(route["threads"]) > 1 else 0]
+                        rc = L.world_hip_probe_fft(ctx, route["mode"], lg, max_lr, threads, swz, 3, rows.ctypes.data, out.ctypes.data)
+                        if rc != 0:                                  # workgroup size a template constant: not on one lane
+                            assert swz == 0 and route["mode"] >= 7 and b"probe_fft" in L.world_hip_last_error(), (route["mode"], lg, swz)
+                            continue
+                        got = out if kind == "c2r" else to_complex(out)
+                        if route["kind"] == "r2c_twice":
+                            got = got * 0.5
+                        assert np.abs(got - ref).max() < 1e-13 * np.abs(ref).max(), (route["mode"], lg, swz, max_lr)
+                        ran.add((route["mode"], swz))
+        assert ran == {(1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0), (1, 1), (7, 1), (13, 1), (14, 1), (15, 1), (16, 1)}, sorted(ran)
+        # d4c_frame's twiddles: the direct tables are twiddle()'s values; the pruned butterfly is dft8 on padded input
+        for lg in (11, 12, 13, 14):
+            n = 1 << lg
+            out = np.zeros((1, n, 2))
+            assert L.world_hip_probe_fft(ctx, 17, lg, 3, n // 16, 1, 1, out.ctypes.data, out.ctypes.data) == 0
+            g = to_complex(out)[0]
+            na = (n >> 7) + (n >> 10)
+            assert np.array_equal(g[:na], g[n // 4:n // 4 + na])
+            assert np.abs(g[n // 2:] - np.exp(-2j * np.pi * np.arange(n // 2) / n)).max() < 1e-13
+        z = np.zeros((5, 8), dtype=np.complex128)
+        z[:, :2] = rng.standard_normal((5, 2)) + 1j * rng.standard_normal((5, 2))
+        for swz in (0, 1):
+            a, b = np.zeros((5, 8, 2)), np.zeros((5, 8, 2))
+            rows = to_pairs(z)
+            assert L.world_hip_probe_fft(ctx, 18, 3, 3, 256, swz, 5, rows.ctypes.data, a.ctypes.data) == 0
+            assert L.world_hip_probe_fft(ctx, 19, 3, 3, 256, swz, 5, rows.ctypes.data, b.ctypes.data) == 0
+            assert np.array_equal(a, b) and np.abs(to_complex(a) - np.fft.fft(z, axis=1)).max() < 1e-13
     finally:
         L.world_hip_destroy(ctx)
 

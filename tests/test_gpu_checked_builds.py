@@ -629,6 +629,33 @@ def run_plumbing(wh):
     return out
 
 
+# ---- fft.h's compositions in isolation (tests/test_gpu_fft_routes.py: ROUTES) -----------------------------------------------
+def run_fft_routes(wh):
+    """every mode of world_hip_probe_fft at 4096 points, and one more size wherever a mode's template differs by length (the
+    compile-time plans, d4c_frame's shapes, a plan with a radix-2 / radix-4 remainder): the wave-local stages that drop
+    workgroup barriers are what the jitter build is for"""
+    import torch
+    from test_gpu_fft_routes import ROUTES, threads_of
+    out = []
+    for route in ROUTES:
+        sizes = {"twiddles": (11, 12, 13, 14), "dft8": (3,)}.get(route["kind"]) or \
+            (tuple(route["lgs"]) if len(route["lgs"]) <= 4 else (6, 9, 12))
+        for swz in route["swz"]:
+            for lg in (g for g in sizes if g in route["lgs"]):
+                n = 1 << lg
+                shape = {"r2c": (3, n), "r2c_twice": (3, n), "c2r": (3, n // 2 + 1, 2)}.get(route["kind"], (3, n, 2))
+                x = _once(("fft route rows", shape), lambda: np.random.default_rng(n + len(shape)).standard_normal(shape))
+                if route["kind"] == "c2c_half":
+                    x = x.copy(); x[:, n // 2 + 1:] = 0.0
+                for max_lr in route["max_lr"]:
+                    threads = threads_of(route, lg)
+                    threads = threads[len(threads) // 2]
+                    out.append((f"mode {route['mode']} swz {swz} lg {lg} max_lr {max_lr} threads {threads}",
+                                _np(wh.probe_fft(route["mode"], _dev(x), max_lr=max_lr, threads=threads, swizzle=swz))))
+    torch.cuda.synchronize()
+    return out
+
+
 # ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
 DROPIN_SECONDS = (0.5, 0.2, 0.31)
 
@@ -707,6 +734,14 @@ FAMILIES = {
     "plumbing": (run_plumbing, ("ex_pack_rows", "ex_unpack_rows", "pcm16_to_double", "pcm_bytes_to_double", "double_to_pcm16",
                                 "fft_probe_rfft<3, 11>", "fft_probe_irfft<3, 11>", "fft_probe_rfft<3>", "fft_probe_irfft<3>",
                                 "fft_probe_rfft<4>", "fft_probe_irfft<4>"), {}),
+    "fft-routes": (run_fft_routes, tuple(f"fft_route_rfft<{a}>" for a in ("0, 3", "0, 4", "1, 3", "0, 3, 10", "0, 3, 11", "0, 3, 12", "1, 3, 11"))
+                   + tuple(f"fft_route_irfft<{a}>" for a in ("0, 3", "0, 4", "0, 3, 10", "0, 3, 11", "0, 3, 12"))
+                   + tuple(f"fft_route_rfft_from<{a}>" for a in ("0, 3", "0, 3, 10", "0, 3, 11", "0, 3, 12"))
+                   + ("fft_route_cfft<0>", "fft_route_cfft_from<0>", "fft_route_rfft_items<0, 12, 256, false>", "fft_route_rfft_items<1, 12, 256, true>",
+                      "fft_route_irfft_items<0, 12, 256, true>", "fft_route_irfft_items<0, 12, 256, false>")
+                   + tuple(f"fft_route_d4c_rfft<1, {n}, {n // 16}, {k}>" for n in (2048, 4096, 8192, 16384) for k in (0, 1, 2))
+                   + tuple(f"fft_route_d4c_twiddles<1, {n}, {n // 16}>" for n in (2048, 4096, 8192, 16384))
+                   + tuple(f"fft_route_dft8<{s}, {h}>" for s in (0, 1) for h in ("false", "true")), {}),
     "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
                                                             "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
                        + _SYNTHESIS, {}),
@@ -714,7 +749,7 @@ FAMILIES = {
 # Families whose calls carve nothing from the arena and keep no buffer of their own between calls (cached tables apart): a
 # second pass in the same context has nothing to refill, so the hbm build's counter need only rise in the first (the tables'
 # allocation).  Every other family must see it rise in both passes.
-NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing")
+NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing", "fft-routes")
 # profile labels that are not the kernel's own name (devrt::launch_blocks("label", kernel<...>, ...))
 LABELS = {"ct_frame_coded": "ct_frame"}
 # kernels that run only while a process-wide table is built: asserted on the first pass of the jitter library, which nothing

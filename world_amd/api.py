@@ -305,6 +305,8 @@ def load_library(path=LIB_PATH):
     lib.world_hip_synthesis_pulses_dropped.argtypes = [vp, _ip]
     lib.world_hip_probe_rfft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
     lib.world_hip_probe_irfft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
+    if hasattr(lib, "world_hip_probe_fft"):                          # (added under ABI 6: looked up by name)
+        lib.world_hip_probe_fft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
     lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                              C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
     lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
@@ -1417,6 +1419,34 @@ class WorldHip:
         self._check(self.lib.world_hip_probe_irfft(self._context(), lg, max_lr, threads, int(static_plan), batch, spec.data_ptr(),
                                                    out.data_ptr()),
                     "probe_irfft")
+        return out
+
+    # real rows in / spectra out, spectra in / real rows out, complex rows in and out (include/world_hip.h: world_hip_probe_fft)
+    PROBE_FFT_REAL_IN = (1, 3, 4, 7, 9, 10, 13, 14, 15, 16)
+    PROBE_FFT_REAL_OUT = (2, 8, 11, 12)
+
+    def probe_fft(self, mode, x, max_lr=3, threads=256, swizzle=0):
+        """one composition of csrc/fft.h's entry points per row of x, one workgroup each: x [batch, N] float64 ->
+        [batch, N/2+1, 2] for the r2c modes, the reverse for the c2r modes, [batch, N, 2] -> [batch, N, 2] for the
+        complex ones (mode 17 reads nothing: x gives the shape)"""
+        t = self.torch
+        assert x.dtype == t.float64 and x.is_contiguous()
+        batch = x.shape[0]
+        if mode in self.PROBE_FFT_REAL_IN:
+            assert x.dim() == 2
+            N, shape = x.shape[1], (batch, x.shape[1] // 2 + 1, 2)
+        elif mode in self.PROBE_FFT_REAL_OUT:
+            assert x.dim() == 3 and x.shape[2] == 2
+            N = 2 * (x.shape[1] - 1)
+            shape = (batch, N)
+        else:
+            assert x.dim() == 3 and x.shape[2] == 2
+            N, shape = x.shape[1], tuple(x.shape)
+        lg = N.bit_length() - 1
+        assert 1 << lg == N
+        out = t.empty(shape, dtype=t.float64, device=x.device)
+        self._check(self.lib.world_hip_probe_fft(self._context(), mode, lg, max_lr, threads, swizzle, batch, x.data_ptr(),
+                                                 out.data_ptr()), "probe_fft")
         return out
 
     # ---- multi-GPU exchange records (include/world_hip.h: world_hip_pack_results) ----

@@ -2743,7 +2743,7 @@ int world_hip_probe_machine(WorldHipContext *c, double *values, int n_values) {
 // fft.h in isolation (fft_probe.hip): `batch` real transforms of 2^lg_n points, one workgroup each
 static void run_fft_probe(WorldHipContext *c, bool inverse, int lg_n, int max_lr, int threads, int static_plan,
                           long long batch, const void *d_in, void *d_out) {
-  if (lg_n < 8 || lg_n > kTwLog2) fail("probe: 2^%d points unsupported (256 .. %d)", lg_n, kTwN);   // (16384: 147 KB of LDS)
+  if (lg_n < 6 || lg_n > kTwLog2) fail("probe: 2^%d points unsupported (64 .. %d)", lg_n, kTwN);   // (16384: 147 KB of LDS)
   if (max_lr != 3 && max_lr != 4) fail("probe: max_lr must be 3 (radix-8 plan) or 4 (radix-16 plan)");
   if (threads == 0) threads = std::max(64, (1 << lg_n) >> (max_lr + 1));      // one butterfly per thread and stage
   if (threads < 64 || threads > 1024 || threads % 64) fail("probe: bad workgroup size %d", threads);
@@ -2760,6 +2760,28 @@ int world_hip_probe_rfft(WorldHipContext *c, int lg_n, int max_lr, int threads, 
 int world_hip_probe_irfft(WorldHipContext *c, int lg_n, int max_lr, int threads, int static_plan, long long batch,
                           const double *d_spectrum, double *d_out) {
   return guarded(c, [&] { run_fft_probe(c, true, lg_n, max_lr, threads, static_plan, batch, d_spectrum, d_out); });
+}
+
+// every composition of fft.h's entry points a stage kernel runs (fft_probe.h: FftProbeMode), under either slot swizzle
+int world_hip_probe_fft(WorldHipContext *c, int mode, int lg_n, int max_lr, int threads, int swizzle, long long batch,
+                        const void *d_in, void *d_out) {
+  return guarded(c, [&] {
+    if (swizzle != 0 && swizzle != 1) fail("probe_fft: swizzle map %d unsupported (0: the shipped map, 1: d4c.hip's)", swizzle);
+    if (batch < 0 || batch > 0x7FFFFFFFll) fail("probe_fft: bad batch");
+    if (batch == 0) return;
+    if (!d_in || !d_out) fail("null buffer");
+#ifdef WORLD_EMU
+    if (swizzle == 1 && !launch_fft_routes_swz1) fail("probe_fft: this host emulation was built without fft_probe_swz1.hip");
+#endif
+    const bool ok = swizzle == 0 ? launch_fft_routes_swz0(mode, lg_n, max_lr, threads, (long)batch, d_in, d_out, c->tab, c->stream)
+                                 : launch_fft_routes_swz1(mode, lg_n, max_lr, threads, (long)batch, d_in, d_out, c->tab, c->stream);
+    if (!ok)
+      fail("probe_fft: mode %d at 2^%d points, max_lr %d, %d threads, swizzle %d is not a composition the stage kernels run.  Supported "
+           "(threads = 64 .. 1024 in steps of 64 unless fixed; include/world_hip.h): modes 1, 2 at 2^6 .. 2^14, max_lr 3 or 4; 3 at "
+           "2^6 .. 2^14, max_lr 3; 4, 5 at 2^6 .. 2^13, max_lr 4; 6 at 2^6 .. 2^13, max_lr 3; 7, 8, 9 at 2^10 .. 2^12, max_lr 3; 10 .. 13 "
+           "at 2^12, max_lr 3, 256 threads; 14 .. 17 at 2^11 .. 2^14, max_lr 3, N / 16 threads; 18, 19 at lg_n 3 (rows of 8).  Swizzle 0 has modes "
+           "1 .. 12, 18 and 19; swizzle 1 modes 1 (max_lr 3), 7 (2^11) and 13 .. 19.  Modes 7 .. 17 do not exist in the one-lane host emulation", mode, lg_n, max_lr, threads, swizzle);
+  });
 }
 
 int world_hip_pack_results(WorldHipContext *c, int n_utt, const int *n_frames, int f_stride, int bins,

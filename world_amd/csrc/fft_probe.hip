@@ -1,11 +1,14 @@
 // fft_probe.hip -- fft.h in isolation: batches of real transforms straight from and to HBM, one
 // workgroup per transform, exactly the block_rfft / block_irfft instantiations the stage kernels use
-// (radix-8 and radix-16 plans, 256 .. 8192 points).  Replaces nothing in the reference by itself:
+// (radix-8 and radix-16 plans, 64 .. 16384 points).  Replaces nothing in the reference by itself:
 // it is the measurement and test hook for the reference's fft_plan_dft_r2c_1d / fft_plan_dft_c2r_1d /
 // fft_execute (src/world/fft.h:22-44, src/fft.cpp:143-212) as re-implemented in fft.h --
 // tests/test_gpu_fft.py checks it against numpy.fft, tools/fft_microbench.py times it per N.
+// Behind them, fft_probe_routes.inc: every other composition of fft.h's entry points a stage kernel runs, here under the
+// shipped slot swizzle (fft_probe_swz1.hip: under d4c.hip's); tests/test_gpu_fft_routes.py holds each to the long-double oracle.
 #include "common.h"
 #include "fft_probe.h"
+#include "fft_probe_routes.inc"
 
 namespace world_hip {
 
