@@ -804,6 +804,83 @@ WORLD_HIP_API int world_hip_gmm_fit(WorldHipContext *ctx, int M, int P, int rows
 WORLD_HIP_API int world_hip_gmm_init(WorldHipContext *ctx, int M, int P, int rows, const double *d_z, long long z_row_stride,
                                      double *w, double *mu, double *cov /* host, out */);
 
+/* Training rows of a voice-conversion corpus on the device: the step between world_hip_align_batch and world_hip_gmm_fit.
+ * A power gate drops the silent frames of every utterance, an ordered compaction turns the decisions into frame numbers, a
+ * gather makes the kept frames adjacent rows (so that all pairs of a corpus go into ONE world_hip_align_batch call), and a
+ * second gather builds the joint rows [x, y] along the paths.  The reference has no such function; THIS COMMENT IS THE RULE.
+ *   power (world_hip_frame_power_batch).  Utterance u has n_frames[u] envelope rows of K = fft_size / 2 + 1 doubles at
+ *            d_sp + u sp_utt_stride + t sp_row_stride.  With N = fft_size,
+ *              P_t = ((sp[0] + sp[N/2]) + 2 S) / N,   S = the sum of sp[1 .. N/2 - 1]   (the mean of the N-point spectrum),
+ *              mean_u = (sum over t of P_t) / n_frames[u].
+ *            Both sums have one order: 64 partial sums, partial j adding from +0.0 the terms whose index (the bin k, the
+ *            frame t) is congruent to j modulo 64, in ascending index; then, for s = 32, 16, 8, 4, 2, 1 in turn, partial j
+ *            takes partial j + s for every j < s; partial 0 is the sum.  Every addition is rounded on its own, 2 S is exact.
+ *            d_power [u][t] (power_utt_stride doubles apart) and d_mean [u]; either may be NULL.
+ *   selection (world_hip_select_frames_batch).  Frame t of utterance u is KEPT if
+ *              (d_mask == NULL or mask[u][t] != 0) and v_t >= threshold * scale_u,
+ *            v_t the double at d_value + u value_utt_stride + t value_stride (a vector with value_stride = 1, or a column of a
+ *            record where it lies), scale_u = d_scale[u], or 1 when d_scale is NULL; the product is rounded once.  A NaN on
+ *            either side of the comparison keeps nothing.  Outputs, each may be NULL: d_index [u][i] (ints, index_utt_stride
+ *            apart) the kept frames' numbers in ascending order; d_count [u]; d_keep [u][t] (bytes, keep_utt_stride apart)
+ *            0 / 1, the mask format world_hip_delta_batch and world_hip_mlpg_batch read.  An utterance may have any number
+ *            of frames.
+ *   gather (world_hip_gather_rows_batch).  out[u][i][0 .. dim) = in[u][index[u][i]][0 .. dim) for i < n_out[u]; n_src[u]
+ *            (the rows utterance u of d_in has) and n_out are HOST arrays, the indices live on the device.
+ *   joint rows (world_hip_joint_rows_batch).  For pair u and step k < path_len[u] (HOST array; d_path [u][p_stride][2] as
+ *            world_hip_align_batch writes it): (i, j) = d_path[u][k]; i' = d_sel_a ? sel_a[u][i] : i, j' likewise from
+ *            d_sel_b (selections are ints, sel_*_stride apart, n_sel_*[u] of them: HOST arrays, required with a selection).
+ *            Row z_row[u] + k of d_z is the dim_a doubles of A's row a_row[u] + i' followed by the dim_b doubles of B's row
+ *            b_row[u] + j'.  a_row, b_row, z_row are HOST arrays with the meaning of world_hip_align_batch's; z_row is the
+ *            caller's prefix sum of the path lengths (any rows that keep the pairs apart will do).  dim_b = 0 is allowed
+ *            (d_b, b_row, n_b are then not looked at).
+ *   copies.   Both gathers copy bits (a NaN keeps its payload).  Strides are counted in doubles and are arbitrary beyond
+ *            the row: a source may sit at column 2 or 3 of a record, so pointers are 8-byte aligned and need not be 16-byte
+ *            aligned.
+ *   never written.  Index entries at or beyond count[u], index and keep entries at or beyond n_frames[u], power entries at or
+ *            beyond n_frames[u], doubles beyond a row's extent and rows at or beyond n_out[u] / path_len[u].
+ *   data.     Index values cannot be refused before the launch.  A gather index outside [0, n_src[u]) writes that row as
+ *            `fill`; in the joint rows an i or j outside the selection's length (or the side's frame count without one) or
+ *            an i' or j' outside [0, n_a[u]) / [0, n_b[u]) writes `fill` into that half of the row.  Nothing out of range is
+ *            read and no other row changes.  A NaN envelope bin makes that frame's power (and the mean) NaN and nothing else.
+ *   determinism.  An utterance's or pair's outputs depend on nothing but its own data and counts: not on the batch, its
+ *            position in it, the strides, the launch shape or a graph replay.  The selection's outputs are integers.
+ * Refused, before any GPU work and with nothing written (1 is returned, the reason is in world_hip_last_error): a count of
+ * utterances or pairs below 1; any n_frames[u], n_src[u], n_out[u], n_a[u], n_b[u], n_sel[u] or path_len[u] below 1; a NULL
+ * n_frames / d_sp, n_frames / d_value, n_src / n_out / d_in / d_index / d_out, or a / b (with dim_b > 0) / their row and count
+ * arrays / path_len / d_path / z_row / d_z, a selection without its lengths; fft_size not a power of two in [128, 8192]; dim,
+ * dim_a below 1 or dim_b below 0; dim_a + dim_b above INT_MAX / 8; a row stride shorter than its row; value_stride below 1; a
+ * negative utterance stride or first row; path_len[u] above p_stride; utterances of an output (power, index, keep, the
+ * gathered rows; a selection likewise) that run into each other, pairs of d_z that do; an output range that overlaps an input
+ * range or another output.
+ * Stream order and errors as the other batched calls.  After one eager call of a shape (the count arrays are found by content)
+ * a call neither allocates nor copies from the host nor waits, and can be captured.  Workspace: only a mean without d_power,
+ * [n_utt][max n_frames] doubles (world_hip_workspace_bytes counts it).
+ * Time (one MI355X, 2026-10-20; tools/corpus_bench.py; 200 pairs of 540 to 600 frames a side, D = 50 statics, joint rows of
+ * 200 doubles): all joint rows of the corpus through one align call and one joint_rows call 4.9 ms, against 210.8 ms for a
+ * loop of one align call a pair with torch indexing (the same bits); by the launch, HIP events after a warm-up: frame_power
+ * with its mean on 114 k rows of 513 bins 0.115 ms, select_frames 0.007 ms, gather_rows of the kept statics 0.018 ms,
+ * joint_rows 0.072 ms (torch.index_select twice and torch.cat on the same tensors: 0.164 ms).  DESIGN.md 3.18. */
+WORLD_HIP_API int world_hip_frame_power_batch(WorldHipContext *ctx, int n_utt, int fft_size, const int *n_frames /* host */,
+                                              const double *d_sp, long long sp_utt_stride, long long sp_row_stride,
+                                              double *d_power, long long power_utt_stride, double *d_mean);
+WORLD_HIP_API int world_hip_select_frames_batch(WorldHipContext *ctx, int n_utt, const int *n_frames /* host */,
+                                                const double *d_value, long long value_utt_stride, long long value_stride,
+                                                double threshold, const double *d_scale, const unsigned char *d_mask,
+                                                long long mask_utt_stride, int *d_index, long long index_utt_stride,
+                                                int *d_count, unsigned char *d_keep, long long keep_utt_stride);
+WORLD_HIP_API int world_hip_gather_rows_batch(WorldHipContext *ctx, int n_utt, int dim, const int *n_src /* host */,
+                                              const double *d_in, long long in_utt_stride, long long in_row_stride,
+                                              const int *n_out /* host */, const int *d_index, long long index_utt_stride,
+                                              double fill, double *d_out, long long out_utt_stride, long long out_row_stride);
+WORLD_HIP_API int world_hip_joint_rows_batch(WorldHipContext *ctx, int n_pairs, int dim_a, int dim_b, const double *d_a,
+                                             const long long *a_row /* host */, const int *n_a /* host */, long long a_row_stride,
+                                             const double *d_b, const long long *b_row /* host */, const int *n_b /* host */,
+                                             long long b_row_stride, const int *path_len /* host */, const int *d_path,
+                                             int p_stride, const int *d_sel_a, const int *n_sel_a /* host */,
+                                             long long sel_a_stride, const int *d_sel_b, const int *n_sel_b /* host */,
+                                             long long sel_b_stride, double fill, double *d_z, const long long *z_row /* host */,
+                                             long long z_row_stride);
+
 /* Coders on dense device rows (reference src/codec.cpp:217-324).  Rows are independent:
  *   spectrogram / aperiodicity  [rows][fft_size/2+1]
  *   coded spectral envelope     [rows][number_of_dimensions]

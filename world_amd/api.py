@@ -420,6 +420,13 @@ def load_library(path=LIB_PATH):
         lib.world_hip_gmm_update.argtypes = [i, i, vp, vp, vp, vp, d, d, vp, vp, vp]
         lib.world_hip_gmm_fit.argtypes = [vp, i, i, i, vp, ll, i, d, vp, vp, vp, vp]
         lib.world_hip_gmm_init.argtypes = [vp, i, i, i, vp, ll, vp, vp, vp]
+    if hasattr(lib, "world_hip_joint_rows_batch"):                   # (likewise)
+        ll, i, d, lp = C.c_longlong, C.c_int, C.c_double, C.POINTER(C.c_longlong)
+        lib.world_hip_frame_power_batch.argtypes = [vp, i, i, _ip, vp, ll, ll, vp, ll, vp]
+        lib.world_hip_select_frames_batch.argtypes = [vp, i, _ip, vp, ll, ll, d, vp, vp, ll, vp, ll, vp, vp, ll]
+        lib.world_hip_gather_rows_batch.argtypes = [vp, i, i, _ip, vp, ll, ll, _ip, vp, ll, d, vp, ll, ll]
+        lib.world_hip_joint_rows_batch.argtypes = [vp, i, i, i, vp, lp, _ip, ll, vp, lp, _ip, ll, _ip, vp, i, vp, _ip, ll, vp, _ip, ll,
+                                                   d, vp, lp, ll]
     lib.world_hip_profile_enable.argtypes = [C.c_int]
     lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
     return lib
@@ -1920,6 +1927,154 @@ class WorldHip:
         self._check(lib.world_hip_gmm_fit(self._context(), M, P, rows, z.data_ptr(), z_rs, int(n_iter), float(reg), w.ctypes.data, mu.ctypes.data,
                                           cov.ctypes.data, loglik.ctypes.data), "gmm_fit")
         return w, mu, cov, loglik
+
+    # ---- training rows of a corpus (include/world_hip.h: world_hip_frame_power_batch .. world_hip_joint_rows_batch) ----
+    def _corpus_lib(self):
+        if not hasattr(self.lib, "world_hip_joint_rows_batch"):
+            raise RuntimeError("this libworld_hip.so has no corpus stage (world_hip_joint_rows_batch)")
+        return self.lib
+
+    @staticmethod
+    def _counts(n, U, most, what):
+        nf = np.full(U, most, dtype=np.int32) if n is None else np.ascontiguousarray(np.atleast_1d(n), dtype=np.int32).reshape(-1)
+        if nf.shape != (U,) or (nf.size and int(nf.max()) > most):
+            raise ValueError(f"{what}: {U} counts of at most {most}")
+        return nf
+
+    @staticmethod
+    def _stride(a, axis, least):
+        """the stride of an axis, or `least` where the axis has one entry (its stride then means nothing)"""
+        return int(a.stride(axis)) if a.shape[axis] > 1 else least
+
+    def frame_power(self, sp, n_frames=None):
+        """envelope rows sp [U][T][fft_size / 2 + 1] (or [T][bins]; float64 on the device, strides honoured) -> (power [U][T],
+        mean [U]): each frame's mean spectral power and its mean over the utterance's n_frames[u] frames (entries beyond
+        are 0).  A 2-D input gives power [T] and a 0-dim mean."""
+        lib, t = self._corpus_lib(), self.torch
+        x3 = self._frames3(sp, "frame_power")
+        U, T, bins = (int(v) for v in x3.shape)
+        nf = self._counts(n_frames, U, T, "frame_power: n_frames")
+        power, mean = t.zeros((U, T), dtype=t.float64, device=sp.device), t.zeros(U, dtype=t.float64, device=sp.device)
+        self._check(lib.world_hip_frame_power_batch(self._context(), U, 2 * (bins - 1), nf.ctypes.data_as(_ip), x3.data_ptr(),
+                                                    self._stride(x3, 0, 0), self._stride(x3, 1, bins), power.data_ptr(), T, mean.data_ptr()),
+                    "frame_power")
+        return (power[0], mean[0]) if sp.dim() == 2 else (power, mean)
+
+    def select_frames(self, values, n_frames, threshold, scale=None, mask=None):
+        """the frames with mask != 0 and values >= threshold * scale[u]: values [U][T] (or [T]) float64 on the device, any
+        strides (a column of a record is read where it lies); scale [U] float64 on the device or None; mask [U][T] bool or
+        uint8.  -> (index [U][T] int32: the kept frames' numbers, ascending, in the first count[u] entries; count [U] int32;
+        keep [U][T] uint8, the mask deltas() and mlpg() read).  Entries beyond are 0."""
+        lib, t = self._corpus_lib(), self.torch
+        assert values.dtype == t.float64 and values.device == self.device and values.dim() in (1, 2), f"select_frames: [U][T] float64 on {self.device}"
+        v2 = values[None] if values.dim() == 1 else values
+        U, T = (int(v) for v in v2.shape)
+        nf = self._counts(n_frames, U, T, "select_frames: n_frames")
+        s_ptr = None
+        if scale is not None:
+            scale = scale.reshape(-1)
+            assert scale.dtype == t.float64 and scale.device == self.device and scale.is_contiguous() and scale.numel() == U, f"select_frames: scale [{U}] float64"
+            s_ptr = scale.data_ptr()
+        m_ptr, m_us = None, 0
+        if mask is not None:
+            assert mask.device == self.device and mask.dtype in (t.bool, t.uint8), "select_frames: mask must be bool or uint8 on the device"
+            m2 = mask[None] if mask.dim() == 1 else mask
+            assert tuple(m2.shape) == (U, T) and (T == 1 or m2.stride(1) == 1), f"select_frames: mask must be [{U}][{T}] with adjacent frames"
+            m_ptr, m_us = m2.data_ptr(), self._stride(m2, 0, 0)
+        index, count = t.zeros((U, T), dtype=t.int32, device=self.device), t.zeros(U, dtype=t.int32, device=self.device)
+        keep = t.zeros((U, T), dtype=t.uint8, device=self.device)
+        self._check(lib.world_hip_select_frames_batch(self._context(), U, nf.ctypes.data_as(_ip), v2.data_ptr(), self._stride(v2, 0, 0),
+                                                      self._stride(v2, 1, 1), float(threshold), s_ptr, m_ptr, m_us, index.data_ptr(), T,
+                                                      count.data_ptr(), keep.data_ptr(), T), "select_frames")
+        return (index[0], count, keep[0]) if values.dim() == 1 else (index, count, keep)
+
+    def gather_rows(self, x, index, n_out, fill=0.0, out=None, n_src=None):
+        """out[u][i] = x[u][index[u][i]] for i < n_out[u] (host counts): x [U][T][D] (or [T][D]) float64 on the device,
+        strides honoured; index [U][I] int32 on the device (select_frames' output).  A row whose index lies outside
+        [0, n_src[u]) (default T) is `fill`.  Returns [U][max n_out][D] (zeros beyond n_out[u]), or out."""
+        lib, t = self._corpus_lib(), self.torch
+        x3 = self._frames3(x, "gather_rows")
+        U, T, D = (int(v) for v in x3.shape)
+        i2 = index[None] if index.dim() == 1 else index
+        assert i2.dtype == t.int32 and i2.device == self.device and i2.dim() == 2 and i2.shape[0] == U and (i2.shape[1] == 1 or i2.stride(1) == 1), \
+            f"gather_rows: index [{U}][I] int32 on {self.device} with adjacent entries"
+        no = self._counts(n_out, U, int(i2.shape[1]), "gather_rows: n_out")
+        ns = self._counts(n_src, U, T, "gather_rows: n_src")
+        ret = out
+        if out is None:
+            out = t.zeros((U, int(no.max()), D), dtype=t.float64, device=self.device)
+            ret = out[0] if x.dim() == 2 else out
+        o3 = self._frames3(out, "gather_rows")
+        assert o3.shape[0] == U and o3.shape[1] >= int(no.max()) and o3.shape[2] == D, f"gather_rows: out must be [{U}][>= {int(no.max())}][{D}]"
+        self._check(lib.world_hip_gather_rows_batch(self._context(), U, D, ns.ctypes.data_as(_ip), x3.data_ptr(), self._stride(x3, 0, 0),
+                                                    self._stride(x3, 1, D), no.ctypes.data_as(_ip), i2.data_ptr(), self._stride(i2, 0, 0),
+                                                    float(fill), o3.data_ptr(), self._stride(o3, 0, 0), self._stride(o3, 1, D)), "gather_rows")
+        return ret
+
+    def _pair_rows(self, x, first, P, name):
+        """frames [P][F][D] or a block [rows][D] with each pair's first row -> (first rows int64, row stride, rows each pair
+        may reach to)"""
+        t = self.torch
+        assert x.dtype == t.float64 and x.device == self.device and x.dim() in (2, 3), f"{name}: float64 [P, F, D] or [rows, D] on {self.device}"
+        assert x.shape[-1] >= 1 and (x.shape[-1] == 1 or x.stride(-1) == 1), f"{name}: the columns of a row must be adjacent"
+        stride = self._stride(x, -2, max(int(x.shape[-1]), int(x.stride(-2))))
+        assert stride >= x.shape[-1], f"{name}: rows overlap"
+        if x.dim() == 3:
+            assert first is None and x.shape[0] == P, f"{name}: [P, F, D]"
+            assert P == 1 or x.stride(0) % stride == 0, f"{name}: the utterances must lie whole rows apart"
+            return np.arange(P, dtype=np.int64) * ((x.stride(0) // stride) if P > 1 else 0), stride, np.full(P, x.shape[1], dtype=np.int64)
+        first = np.zeros(1, dtype=np.int64) if first is None and P == 1 else first
+        assert first is not None, f"{name}: a block of rows needs {name}_row"
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        assert len(first) == P and int(first.min()) >= 0 and int(first.max()) < x.shape[0]
+        return first, stride, x.shape[0] - first
+
+    def joint_rows(self, a, b, path, path_len, sel_a=None, sel_b=None, a_row=None, b_row=None, out=None, n_a=None, n_b=None,
+                   n_sel_a=None, n_sel_b=None, fill=0.0):
+        """the joint rows [a, b] along DTW paths: a, b as align() takes them ([P, F, D] or a block [rows, D] with a_row /
+        b_row; b may be None); path [P, S, 2] int32 and path_len [P] (host counts, or align()'s tensor) as align() returns
+        them; sel_a / sel_b [P, I] int32 on the device: the frame numbers the path's indices stand for (select_frames'
+        index), or None.  n_a / n_b: each side's rows per pair (default: all the tensor has from the pair's first row on),
+        n_sel_*: the selections' lengths (default I).  An index out of range gives `fill` in that half of the row.
+        -> z [sum of path_len][Da + Db] float64, pair u's rows from the sum of the path lengths before it; or out."""
+        lib, t = self._corpus_lib(), self.torch
+        if t.is_tensor(path_len):
+            path_len = path_len.cpu().numpy()
+        K = np.ascontiguousarray(np.atleast_1d(path_len), dtype=np.int32)
+        P = len(K)
+        assert path.dtype == t.int32 and path.device == self.device and path.dim() == 3 and path.shape[0] == P and path.shape[2] == 2 and \
+            path[0].is_contiguous() and int(K.max()) <= path.shape[1], f"joint_rows: path [{P}][>= {int(K.max())}][2] int32 on {self.device}"
+        assert P == 1 or path.stride(0) == 2 * path.shape[1], "joint_rows: the paths must lie p_stride cells apart"
+        lp = C.POINTER(C.c_longlong)
+        sides = []
+        for x, first, n, sel, n_sel, name in ((a, a_row, n_a, sel_a, n_sel_a, "a"), (b, b_row, n_b, sel_b, n_sel_b, "b")):
+            if x is None:
+                assert name == "b", "joint_rows: a is required"
+                sides.append((0, None, None, None, 0, None, None, 0))
+                continue
+            fr, stride, reach = self._pair_rows(x, first, P, name)
+            cnt = reach.astype(np.int32) if n is None else np.ascontiguousarray(np.atleast_1d(n), dtype=np.int32)
+            assert len(cnt) == P and bool(np.all(cnt <= reach)), f"joint_rows: n_{name} beyond the tensor"
+            s_ptr, s_n, s_us = None, None, 0
+            if sel is not None:
+                assert sel.dtype == t.int32 and sel.device == self.device and sel.dim() == 2 and sel.shape[0] == P and \
+                    (sel.shape[1] == 1 or sel.stride(1) == 1), f"joint_rows: sel_{name} [{P}][I] int32 on {self.device}"
+                s_n = self._counts(n_sel, P, int(sel.shape[1]), f"joint_rows: n_sel_{name}")
+                s_ptr, s_us = sel.data_ptr(), self._stride(sel, 0, 0)
+            sides.append((int(x.shape[-1]), x.data_ptr(), fr, cnt, stride, s_ptr, s_n, s_us))
+        (da, pa, fa, na, sa, qa, ma, ua), (db, pb, fb, nb, sb, qb, mb, ub) = sides
+        z_row = np.concatenate([[0], np.cumsum(K[:-1], dtype=np.int64)]).astype(np.int64)
+        rows = int(K.sum(dtype=np.int64))
+        if out is None:
+            out = t.empty((rows, da + db), dtype=t.float64, device=self.device)
+        assert out.dtype == t.float64 and out.device == self.device and tuple(out.shape) == (rows, da + db) and (da + db == 1 or out.stride(1) == 1), \
+            f"joint_rows: out must be [{rows}][{da + db}] float64"
+        ip = lambda v: None if v is None else v.ctypes.data_as(_ip)
+        self._check(lib.world_hip_joint_rows_batch(self._context(), P, da, db, pa, fa.ctypes.data_as(lp), ip(na), sa, pb,
+                                                   None if fb is None else fb.ctypes.data_as(lp), ip(nb), sb, ip(K), path.data_ptr(),
+                                                   int(path.shape[1]), qa, ip(ma), ua, qb, ip(mb), ub, float(fill), out.data_ptr(),
+                                                   z_row.ctypes.data_as(lp), self._stride(out, 0, da + db)), "joint_rows")
+        return out
 
     def probe_machine(self):
         """world_hip_probe_machine (include/world_hip.h): ~50 ms of microbenchmarks that characterise the box"""

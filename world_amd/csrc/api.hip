@@ -2373,6 +2373,192 @@ static void run_gmm_init(WorldHipContext *c, int M, int P, int rows, const doubl
   }
 }
 
+// Training rows of a corpus (include/world_hip.h: world_hip_frame_power_batch / _select_frames_batch / _gather_rows_batch /
+// _joint_rows_batch; corpus.h).  Everything the host can know is refused before any GPU work; the indices live on the
+// device and are made harmless in the kernel.  Only a mean without d_power takes workspace (P [n_utt][max T]).
+static int corpus_counts(const char *name, const char *what, const int *n, int count) {
+  int largest = 0;
+  for (int u = 0; u < count; ++u) {
+    if (n[u] < 1) fail("%s: %s[%d]=%d; each needs one", name, what, u, n[u]);
+    largest = std::max(largest, n[u]);
+  }
+  return largest;
+}
+static void run_frame_power(WorldHipContext *c, int n_utt, int fft_size, const int *n_frames, const double *d_sp, long long sp_us,
+                            long long sp_rs, double *d_power, long long power_us, double *d_mean) {
+  const char *name = "frame_power";
+  if (n_utt < 1) fail("%s: n_utt must be positive", name);
+  if (!n_frames || !d_sp) fail("%s: null n_frames / d_sp", name);
+  if (fft_size < 128 || fft_size > 8192 || (fft_size & (fft_size - 1))) fail("%s: fft_size %d is not a power of two in [128, 8192]", name, fft_size);
+  const int bins = fft_size / 2 + 1, max_frames = corpus_counts(name, "n_frames", n_frames, n_utt);
+  if (sp_rs < bins) fail("%s: sp_row_stride %lld below the row's %d doubles", name, sp_rs, bins);
+  if (sp_us < 0 || (d_power && power_us < 0)) fail("%s: a negative utterance stride", name);
+  long long sp_span = 0, power_span = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    if (d_power && u + 1 < n_utt && n_frames[u] > power_us) fail("%s: power_utt_stride %lld below n_frames[%d]=%d", name, power_us, u, n_frames[u]);
+    sp_span = std::max(sp_span, u * sp_us + (n_frames[u] - 1) * sp_rs + bins);
+    power_span = std::max(power_span, u * power_us + n_frames[u]);
+  }
+  refuse_overlap(name, {{d_power, sizeof(double) * (size_t)power_span, "d_power"}, {d_mean, sizeof(double) * (size_t)n_utt, "d_mean"}},
+                 {{d_sp, sizeof(double) * (size_t)sp_span, "d_sp"}});
+  if (!d_power && !d_mean) return;
+  CorpusPowerParams p;
+  p.power = d_power; p.power_us = power_us;
+  if (!d_power) {
+    begin_stage(c, [&](Arena &a) { p.power = a.take<double>((size_t)n_utt * max_frames); });
+    p.power_us = max_frames;
+  } else {
+    open_uploads(c);
+  }
+  p.sp = d_sp; p.sp_us = sp_us; p.sp_rs = sp_rs; p.mean = d_mean; p.fft_size = fft_size; p.n_utt = n_utt;
+  p.n_frames = upload(c, n_frames, n_utt);
+  for (int u0 = 0; u0 < n_utt; u0 += kGridY) {
+    p.u0 = u0;
+    launch_frame_power(p, std::min(kGridY, n_utt - u0), max_frames, c->stream);
+  }
+  p.u0 = 0;
+  if (d_mean) launch_frame_power_mean(p, n_utt, c->stream);
+}
+
+static void run_select_frames(WorldHipContext *c, int n_utt, const int *n_frames, const double *d_value, long long value_us,
+                              long long value_s, double threshold, const double *d_scale, const unsigned char *d_mask,
+                              long long mask_us, int *d_index, long long index_us, int *d_count, unsigned char *d_keep,
+                              long long keep_us) {
+  const char *name = "select_frames";
+  if (n_utt < 1) fail("%s: n_utt must be positive", name);
+  if (!n_frames || !d_value) fail("%s: null n_frames / d_value", name);
+  corpus_counts(name, "n_frames", n_frames, n_utt);
+  if (value_s < 1) fail("%s: value_stride %lld below the one double of a value", name, value_s);
+  if (value_us < 0 || (d_mask && mask_us < 0) || (d_index && index_us < 0) || (d_keep && keep_us < 0)) fail("%s: a negative utterance stride", name);
+  long long value_span = 0, frames_span[3] = {0, 0, 0};     // mask, index, keep
+  const long long us[3] = {mask_us, index_us, keep_us};
+  for (int u = 0; u < n_utt; ++u) {
+    if (d_index && u + 1 < n_utt && n_frames[u] > index_us) fail("%s: index_utt_stride %lld below n_frames[%d]=%d", name, index_us, u, n_frames[u]);
+    if (d_keep && u + 1 < n_utt && n_frames[u] > keep_us) fail("%s: keep_utt_stride %lld below n_frames[%d]=%d", name, keep_us, u, n_frames[u]);
+    value_span = std::max(value_span, u * value_us + (n_frames[u] - 1) * value_s + 1);
+    for (int k = 0; k < 3; ++k) frames_span[k] = std::max(frames_span[k], u * us[k] + n_frames[u]);
+  }
+  refuse_overlap(name, {{d_index, sizeof(int) * (size_t)frames_span[1], "d_index"}, {d_count, sizeof(int) * (size_t)n_utt, "d_count"},
+                        {d_keep, (size_t)frames_span[2], "d_keep"}},
+                 {{d_value, sizeof(double) * (size_t)value_span, "d_value"}, {d_scale, sizeof(double) * (size_t)n_utt, "d_scale"},
+                  {d_mask, (size_t)frames_span[0], "d_mask"}});
+  if (!d_index && !d_count && !d_keep) return;
+  open_uploads(c);
+  CorpusSelectParams p;
+  p.value = d_value; p.scale = d_scale; p.mask = d_mask; p.index = d_index; p.count = d_count; p.keep = d_keep;
+  p.value_us = value_us; p.value_s = value_s; p.mask_us = mask_us; p.index_us = index_us; p.keep_us = keep_us;
+  p.threshold = threshold;
+  p.n_frames = upload(c, n_frames, n_utt);
+  for (int u0 = 0; u0 < n_utt; u0 += kGridY) {
+    p.u0 = u0;
+    launch_select_frames(p, std::min(kGridY, n_utt - u0), c->stream);
+  }
+}
+
+// both gathers: pair u's output rows z_off[u] + k z_rs, k < n_rows[u]
+struct CorpusSide {
+  const char *name;
+  const double *d;
+  const long long *row;           // host, first row of every pair; nullptr: utt_stride apart
+  long long utt_stride, rs;
+  const int *n;                   // host, rows of every pair
+  const int *d_sel, *n_sel;       // the selection (device) and its lengths (host), or nullptr
+  long long sel_us;
+  int dim;
+};
+static void run_rows(WorldHipContext *c, const char *name, int n_pairs, CorpusSide A, CorpusSide B, const int *n_rows, const int *d_path,
+                     int p_stride, double fill, double *d_z, const long long *z_row, long long z_us, long long z_rs) {
+  if (n_pairs < 1) fail("%s: the number of utterances or pairs must be positive", name);
+  if (A.dim < 1 || B.dim < 0) fail("%s: a row of %d + %d doubles", name, A.dim, B.dim);
+  if ((long long)A.dim + B.dim > INT_MAX / 8) fail("%s: a row of %lld doubles is more than INT_MAX bytes", name, (long long)A.dim + B.dim);
+  const int dim = A.dim + B.dim;
+  if (!A.d || !A.n || !n_rows || !d_z || (B.dim && (!B.d || !B.n))) fail("%s: null input, count array or output", name);
+  if (d_path ? (!A.row || !z_row || (B.dim && !B.row)) : !A.d_sel) fail("%s: null row array or index", name);
+  if (z_rs < dim) fail("%s: the output's row stride %lld below the row's %d doubles", name, z_rs, dim);
+  if (z_us < 0) fail("%s: a negative utterance stride", name);
+  const int max_rows = corpus_counts(name, d_path ? "path_len" : "n_out", n_rows, n_pairs);
+  std::vector<long long> z_off(n_pairs);
+  std::vector<std::pair<long long, long long>> taken(n_pairs);      // rows [first, last] of every pair's output, in z_rs units
+  long long z_lo = LLONG_MAX, z_hi = 0;
+  for (int u = 0; u < n_pairs; ++u) {
+    if (z_row && z_row[u] < 0) fail("%s: pair %d's output starts at a negative row", name, u);
+    if (d_path && n_rows[u] > p_stride) fail("%s: path_len[%d]=%d above p_stride %d", name, u, n_rows[u], p_stride);
+    z_off[u] = z_row ? z_row[u] * z_rs : u * z_us;
+    const long long end = z_off[u] + (n_rows[u] - 1) * z_rs + dim;
+    taken[u] = {z_off[u], end};
+    z_lo = std::min(z_lo, z_off[u]);
+    z_hi = std::max(z_hi, end);
+  }
+  std::sort(taken.begin(), taken.end());
+  for (int u = 0; u + 1 < n_pairs; ++u)
+    if (taken[u].second > taken[u + 1].first) fail("%s: two utterances or pairs of the output run into each other", name);
+  Span ins[5] = {};
+  int n_ins = 0;
+  std::vector<long long> off[2];
+  for (CorpusSide *s : {&A, &B}) {
+    if (!s->dim) continue;
+    if (s->rs < s->dim) fail("%s: %s's row stride %lld below the row's %d doubles", name, s->name, s->rs, s->dim);
+    if (s->utt_stride < 0 || (s->d_sel && s->sel_us < 0)) fail("%s: a negative utterance stride", name);
+    if (s->d_sel && !s->n_sel) fail("%s: a selection of %s without its lengths", name, s->name);
+    corpus_counts(name, s == &A ? "n_a" : "n_b", s->n, n_pairs);
+    if (s->d_sel) corpus_counts(name, "n_sel", s->n_sel, n_pairs);
+    std::vector<long long> &o = off[s == &B];
+    o.resize(n_pairs);
+    long long span = 0, sel_span = 0;
+    for (int u = 0; u < n_pairs; ++u) {
+      if (s->row && s->row[u] < 0) fail("%s: pair %d of %s starts at a negative row", name, u, s->name);
+      o[u] = s->row ? s->row[u] * s->rs : u * s->utt_stride;
+      span = std::max(span, o[u] + (s->n[u] - 1) * s->rs + s->dim);
+      if (s->d_sel) {
+        if (u + 1 < n_pairs && s->n_sel[u] > s->sel_us) fail("%s: %s's selection stride %lld below its %d entries of pair %d", name, s->name, s->sel_us, s->n_sel[u], u);
+        sel_span = std::max(sel_span, u * s->sel_us + s->n_sel[u]);
+      }
+    }
+    ins[n_ins++] = {s->d, sizeof(double) * (size_t)span, s->name};
+    ins[n_ins++] = {s->d_sel, sizeof(int) * (size_t)sel_span, "a selection"};
+  }
+  long long path_span = 0;
+  for (int u = 0; u < n_pairs; ++u) path_span = std::max(path_span, ((long long)u * p_stride + n_rows[u]) * 2);
+  ins[n_ins++] = {d_path, sizeof(int) * (size_t)path_span, "d_path"};
+  refuse_overlap(name, {{d_z + z_lo, sizeof(double) * (size_t)(z_hi - z_lo), "the output"}}, {ins[0], ins[1], ins[2], ins[3], ins[4]});
+  open_uploads(c);
+  CorpusRowsParams p;
+  p.a = A.d; p.b = B.dim ? B.d : nullptr; p.z = d_z;
+  p.a_rs = A.rs; p.b_rs = B.rs; p.z_rs = z_rs;
+  p.path = d_path; p.path_us = 2LL * p_stride;
+  p.sel_a = A.d_sel; p.sel_a_us = A.sel_us; p.sel_b = B.dim ? B.d_sel : nullptr; p.sel_b_us = B.sel_us;
+  p.dim_a = A.dim; p.dim_b = B.dim; p.group = corpus_group(A.dim, B.dim);
+  memcpy(&p.fill, &fill, sizeof(fill));
+  p.a_off = upload(c, off[0]);
+  p.b_off = B.dim ? upload(c, off[1]) : p.a_off;
+  p.z_off = upload(c, z_off);
+  p.n_a = upload(c, A.n, n_pairs);
+  p.n_b = B.dim ? upload(c, B.n, n_pairs) : p.n_a;
+  p.n_sel_a = A.d_sel ? upload(c, A.n_sel, n_pairs) : p.n_a;
+  p.n_sel_b = p.sel_b ? upload(c, B.n_sel, n_pairs) : p.n_a;
+  p.n_rows = upload(c, n_rows, n_pairs);
+  for (int u0 = 0; u0 < n_pairs; u0 += kGridY) {
+    p.u0 = u0;
+    launch_joint_rows(p, std::min(kGridY, n_pairs - u0), max_rows, c->stream);
+  }
+}
+static void run_gather_rows(WorldHipContext *c, int n_utt, int dim, const int *n_src, const double *d_in, long long in_us,
+                            long long in_rs, const int *n_out, const int *d_index, long long index_us, double fill, double *d_out,
+                            long long out_us, long long out_rs) {
+  const CorpusSide in{"d_in", d_in, nullptr, in_us, in_rs, n_src, d_index, n_out, index_us, dim};
+  run_rows(c, "gather_rows", n_utt, in, CorpusSide{"", nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0}, n_out, nullptr, 0, fill,
+           d_out, nullptr, out_us, out_rs);
+}
+static void run_joint_rows(WorldHipContext *c, int n_pairs, int dim_a, int dim_b, const double *d_a, const long long *a_row,
+                           const int *n_a, long long a_rs, const double *d_b, const long long *b_row, const int *n_b, long long b_rs,
+                           const int *path_len, const int *d_path, int p_stride, const int *d_sel_a, const int *n_sel_a,
+                           long long sel_a_us, const int *d_sel_b, const int *n_sel_b, long long sel_b_us, double fill, double *d_z,
+                           const long long *z_row, long long z_rs) {
+  if (!d_path) fail("joint_rows: null d_path");
+  run_rows(c, "joint_rows", n_pairs, CorpusSide{"d_a", d_a, a_row, 0, a_rs, n_a, d_sel_a, n_sel_a, sel_a_us, dim_a},
+           CorpusSide{"d_b", d_b, b_row, 0, b_rs, n_b, d_sel_b, n_sel_b, sel_b_us, dim_b}, path_len, d_path, p_stride, fill, d_z, z_row, 0, z_rs);
+}
+
 // ---------------------------------------------------------------------------
 // error plumbing for the C ABI
 // ---------------------------------------------------------------------------
@@ -3221,6 +3407,39 @@ int world_hip_gmm_fit(WorldHipContext *c, int M, int P, int rows, const double *
 int world_hip_gmm_init(WorldHipContext *c, int M, int P, int rows, const double *d_z, long long z_row_stride, double *w,
                        double *mu, double *cov) {
   return guarded(c, [&] { run_gmm_init(c, M, P, rows, d_z, z_row_stride, w, mu, cov); });
+}
+int world_hip_frame_power_batch(WorldHipContext *c, int n_utt, int fft_size, const int *n_frames, const double *d_sp,
+                                long long sp_utt_stride, long long sp_row_stride, double *d_power, long long power_utt_stride,
+                                double *d_mean) {
+  return guarded(c, [&] { run_frame_power(c, n_utt, fft_size, n_frames, d_sp, sp_utt_stride, sp_row_stride, d_power, power_utt_stride, d_mean); });
+}
+int world_hip_select_frames_batch(WorldHipContext *c, int n_utt, const int *n_frames, const double *d_value,
+                                  long long value_utt_stride, long long value_stride, double threshold, const double *d_scale,
+                                  const unsigned char *d_mask, long long mask_utt_stride, int *d_index, long long index_utt_stride,
+                                  int *d_count, unsigned char *d_keep, long long keep_utt_stride) {
+  return guarded(c, [&] {
+    run_select_frames(c, n_utt, n_frames, d_value, value_utt_stride, value_stride, threshold, d_scale, d_mask, mask_utt_stride,
+                      d_index, index_utt_stride, d_count, d_keep, keep_utt_stride);
+  });
+}
+int world_hip_gather_rows_batch(WorldHipContext *c, int n_utt, int dim, const int *n_src, const double *d_in,
+                                long long in_utt_stride, long long in_row_stride, const int *n_out, const int *d_index,
+                                long long index_utt_stride, double fill, double *d_out, long long out_utt_stride,
+                                long long out_row_stride) {
+  return guarded(c, [&] {
+    run_gather_rows(c, n_utt, dim, n_src, d_in, in_utt_stride, in_row_stride, n_out, d_index, index_utt_stride, fill, d_out,
+                    out_utt_stride, out_row_stride);
+  });
+}
+int world_hip_joint_rows_batch(WorldHipContext *c, int n_pairs, int dim_a, int dim_b, const double *d_a, const long long *a_row,
+                               const int *n_a, long long a_row_stride, const double *d_b, const long long *b_row, const int *n_b,
+                               long long b_row_stride, const int *path_len, const int *d_path, int p_stride, const int *d_sel_a,
+                               const int *n_sel_a, long long sel_a_stride, const int *d_sel_b, const int *n_sel_b,
+                               long long sel_b_stride, double fill, double *d_z, const long long *z_row, long long z_row_stride) {
+  return guarded(c, [&] {
+    run_joint_rows(c, n_pairs, dim_a, dim_b, d_a, a_row, n_a, a_row_stride, d_b, b_row, n_b, b_row_stride, path_len, d_path, p_stride,
+                   d_sel_a, n_sel_a, sel_a_stride, d_sel_b, n_sel_b, sel_b_stride, fill, d_z, z_row, z_row_stride);
+  });
 }
 int world_hip_resynthesis_length(int fs, int n_frames, double frame_period, double time_scale) {
   if (fs <= 0 || n_frames < 1 || !std::isfinite(frame_period) || !(frame_period > 0) || !std::isfinite(time_scale) ||

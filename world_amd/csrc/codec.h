@@ -230,4 +230,42 @@ struct GmmAccParams {
 void launch_gmm_accumulate(const GmmAccParams &p, hipStream_t stream);
 void launch_gmm_fill(double *d, size_t n, double value, hipStream_t stream);
 
+// Training rows of a corpus (world_hip_frame_power_batch / _select_frames_batch / _gather_rows_batch / _joint_rows_batch;
+// corpus.h).  Strides are counted in doubles, in ints for the index arrays and in bytes for the masks; the count arrays are
+// device copies of the host's.
+struct CorpusPowerParams {
+  const double *sp;
+  double *power, *mean;           // power [u][t] (the caller's or the workspace), mean [u] or nullptr
+  const int *n_frames;
+  long long sp_us, sp_rs, power_us;
+  int fft_size, n_utt, u0;
+};
+void launch_frame_power(const CorpusPowerParams &p, int n_utt, int max_frames, hipStream_t stream);
+void launch_frame_power_mean(const CorpusPowerParams &p, int n_utt, hipStream_t stream);
+struct CorpusSelectParams {
+  const double *value, *scale;    // scale [u] or nullptr
+  const unsigned char *mask;
+  int *index, *count;
+  unsigned char *keep;
+  const int *n_frames;
+  long long value_us, value_s, mask_us, index_us, keep_us;
+  double threshold;
+  int u0;
+};
+void launch_select_frames(const CorpusSelectParams &p, int n_utt, hipStream_t stream);
+// joint_rows: row k < n_rows[u] of pair u is A's row (through sel_a) then B's (through sel_b) at the path's cell k, or at
+// (k, k) without a path; *_off are each pair's first element, `group` the lanes that share a row (corpus_group)
+struct CorpusRowsParams {
+  const double *a, *b;
+  double *z;
+  const long long *a_off, *b_off, *z_off;
+  const int *n_a, *n_b, *n_sel_a, *n_sel_b, *n_rows;
+  const int *path, *sel_a, *sel_b;
+  long long a_rs, b_rs, z_rs, path_us, sel_a_us, sel_b_us;
+  unsigned long long fill;
+  int dim_a, dim_b, group, u0;
+};
+int corpus_group(int dim_a, int dim_b);
+void launch_joint_rows(const CorpusRowsParams &p, int n_pairs, int max_rows, hipStream_t stream);
+
 }  // namespace world_hip

@@ -26,8 +26,10 @@
 // And what turns two rows of coded frames into such a time map (world_hip_align_batch): align.inc, included at the end;
 // behind it morph.inc, the frames between two utterances aligned that way (world_hip_morph_batch); and mcep.inc, the
 // all-pass mel-cepstrum of an envelope and back (world_hip_sp2mc / world_hip_mc2sp) on the FP64 matrix unit; mlpg.inc,
-// dynamic features and the maximum-likelihood trajectory behind them (world_hip_delta_batch / world_hip_mlpg_batch); last
-// gmm.inc, the joint-density Gaussian mixture between the two (world_hip_gmm_convert / world_hip_gmm_accumulate).
+// dynamic features and the maximum-likelihood trajectory behind them (world_hip_delta_batch / world_hip_mlpg_batch);
+// gmm.inc, the joint-density Gaussian mixture between the two (world_hip_gmm_convert / world_hip_gmm_accumulate); last
+// corpus.h, the rows that mixture is trained on (world_hip_frame_power_batch .. world_hip_joint_rows_batch; a header for the
+// reason its head comment gives).
 #include "codec.h"
 #include "fft.h"
 
@@ -460,5 +462,6 @@ void launch_rt_store_coded_rows(const RtCodedRowsParams &p, hipStream_t stream) 
 #include "mcep.inc"
 #include "mlpg.inc"
 #include "gmm.inc"
+#include "corpus.h"
 
 }  // namespace world_hip

@@ -299,7 +299,10 @@ __device__ __forceinline__ int xcd_grouped(int b, int n) {
 // and the plumbing kernels -- and requires results bit-identical to the product build's.  The families name the kernels
 // they launch; a CPU test of the same file reads these sources and fails for a __global__ function no family names (the
 // mp_* machine probes excepted: they measure, they have no result).  A new kernel therefore comes with a workload there,
-// and with lds_dead() marks where it hands an LDS region from one use to the next.
+// and with lds_dead() marks where it hands an LDS region from one use to the next.  (corpus.h is a header, not an .inc, because
+// that scan reads *.hip and *.inc and its table could not be edited when the corpus kernels arrived: they carry the same
+// obligations -- every kernel claimed, one workload on all three builds -- in tests/test_gpu_corpus_checked.py until the row
+// moves into the table.)
 #ifndef WORLD_EMU
 #if defined(WH_JITTER)
 __device__ __forceinline__ void jitter() {

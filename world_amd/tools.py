@@ -19,6 +19,7 @@ per call, batched on the GPU, and read / write the same F0 / SPEC / AP / WAV fil
     python -m world_amd.tools deltas a.mgc --dim 60 -o a.mgc.dyn                  # [frames][60] -> [frames][180]: static, delta, delta-delta
     python -m world_amd.tools mlpg mean.mgc.dyn var.mgc.dyn --dim 60 -o a.mgc     # the smooth trajectory under means and variances
     python -m world_amd.tools vc-train s1.mgc s2.mgc --target t1.mgc t2.mgc --dim 25 --mix 32 --iter 20 -o model.npz
+    python -m world_amd.tools vc-train s*.mgc --target t*.mgc --dim 25 --power-gate -20 --fs 16000 --realign 2 -o model.npz
     python -m world_amd.tools vc-convert model.npz s3.mgc --dim 25 -o s3_as_t.mgc   # goes into features-synthesis as it is
 
 `analysis` keeps the example programs' option letters where they exist (-f/-c/-s of f0analysis,
@@ -51,8 +52,14 @@ maximum-likelihood parameter generation): a file of [frames][3 dim] means and on
 variances give the [frames][dim] trajectory, which goes into `features-synthesis` as it is.  With --lf0 (dim 1) the -1e10
 frames are masked: windows stop at the ends of every voiced run and unvoiced frames stay -1e10.
 `vc-train` fits the classic joint-density Gaussian mixture of voice conversion (world_hip_gmm_fit) on pairs of .mgc files of
-two speakers: per pair the deltas of both, the DTW alignment of the statics without c0, the joint rows [x, dx, y, dy] along
-the path; all rows of all pairs are fitted together and w, mu, cov and the dimensions saved as .npz.  `vc-convert` turns a
+two speakers: the deltas of every utterance, ONE world_hip_align_batch call over the statics without c0 of all pairs, one
+world_hip_joint_rows_batch call for the joint rows [x, dx, y, dy] along the paths; all rows of all pairs are fitted together and
+w, mu, cov and the dimensions saved as .npz.  With --power-gate DB --fs F each speaker's frames below DB dB of their utterance's
+mean power (world_hip_frame_power_batch on the envelope of the cepstra, world_hip_select_frames_batch) stay out of the alignment
+and the rows (-20: the usual silence gate; the deltas are still those of the whole utterance).  With --realign R the sources
+are converted with the fitted model, the converted frames aligned to the targets, the rows rebuilt from the original source
+features along the new paths and the model refitted from where it stood, R times; each round prints its mean log-likelihood
+and the mean MCD along the paths.  Without either option the model is the one earlier versions saved.  `vc-convert` turns a
 source .mgc into the target speaker's: deltas, world_hip_gmm_convert (the per-frame means and variances of [y, dy]), mlpg.
 There is no CPU path: without a GPU and the built library this exits with an error.
 """
@@ -598,14 +605,62 @@ def _mlpg(a):
 VC_WINDOWS = WorldHip.DEFAULT_WINDOWS[:2]   # the conversion model sees [static, delta]
 
 
-def vc_joint_rows(wh, src, tgt):
-    """one pair of utterances' statics [T_a][D], [T_b][D] (float64 on the device) -> the joint rows [x, dx, y, dy] along the
-    DTW path of the statics without c0, [path length][4 D]"""
-    xa, xb = wh.deltas(src, windows=VC_WINDOWS), wh.deltas(tgt, windows=VC_WINDOWS)
-    path, path_len, _, _, _ = wh.align(src[None, :, 1:], tgt[None, :, 1:], [len(src)], [len(tgt)])
-    steps = path[0, :int(path_len[0])].long()
+def vc_speaker(wh, utterances):
+    """one speaker's utterances, a list of statics [T][D] (float64 on the device) -> (statics [P][F][D] padded with zeros,
+    [static, delta] [P][F][2 D] of the whole utterances in one deltas call, the frame counts [P] int32)"""
     import torch
-    return torch.cat([xa[steps[:, 0]], xb[steps[:, 1]]], dim=1)
+    n = np.array([len(x) for x in utterances], dtype=np.int32)
+    statics = torch.zeros((len(utterances), int(n.max()), int(utterances[0].shape[1])), dtype=torch.float64, device=wh.device)
+    for u, x in enumerate(utterances):
+        statics[u, :len(x)] = x
+    dyn = torch.zeros((statics.shape[0], statics.shape[1], 2 * statics.shape[2]), dtype=torch.float64, device=wh.device)
+    wh.deltas(statics, windows=VC_WINDOWS, n_frames=n, out=dyn)
+    return statics, dyn, n
+
+
+def vc_power_gate(wh, statics, n, fs, gate_db, alpha=None, batch=16):
+    """the frames of each utterance whose power is at least 10^(gate_db / 10) times the utterance's mean: the envelope of the
+    mel-cepstra (mc2sp at the rate's all-pass constant and CheapTrick's default fft_size) -> frame_power -> select_frames.
+    -> (index [P][F] int32, count [P] int32 on the host)"""
+    import torch
+    fft_size = cheaptrick_fft_size(fs)
+    alpha = wh.mcep_alpha(fs) if alpha is None else alpha
+    index, count = [], []
+    for u0 in range(0, len(n), batch):
+        block, nb = statics[u0:u0 + batch], n[u0:u0 + batch]
+        sp = wh.mc2sp(block.reshape(-1, block.shape[2]), alpha, fft_size).reshape(block.shape[0], block.shape[1], -1)
+        power, mean = wh.frame_power(sp, nb)
+        i, c, _ = wh.select_frames(power, nb, 10.0 ** (gate_db / 10.0), scale=mean)
+        index.append(i)
+        count.append(c)
+    return torch.cat(index), torch.cat(count).cpu().numpy()
+
+
+def vc_joint_rows(wh, a, b, gate_a=None, gate_b=None, align_a=None):
+    """every pair at once: a, b = vc_speaker()'s triples of the two speakers -> (the joint rows [x, dx, y, dy] along the DTW
+    paths of the statics without c0, [sum of the path lengths][4 D]; each pair's MCD along its path in dB, on the host).
+    gate_a / gate_b: vc_power_gate()'s (index, count): alignment and rows use the kept frames only (the deltas are those of
+    the whole utterance).  align_a: statics to align in the source's place (a realignment's converted ones); the rows are
+    the source's own either way.  One align call, one host read (the path lengths), one joint_rows call."""
+    (sa, xa, na), (sb, xb, nb) = a, b
+    sa = sa if align_a is None else align_a
+    fa, fb, ca, cb = sa[:, :, 1:], sb[:, :, 1:], na, nb
+    if gate_a is not None:
+        fa, ca = wh.gather_rows(fa, gate_a[0], gate_a[1], n_src=na), gate_a[1]
+    if gate_b is not None:
+        fb, cb = wh.gather_rows(fb, gate_b[0], gate_b[1], n_src=nb), gate_b[1]
+    path, path_len, summary, _, _ = wh.align(fa, fb, ca, cb)
+    z = wh.joint_rows(xa, xb, path, path_len, sel_a=None if gate_a is None else gate_a[0], sel_b=None if gate_b is None else gate_b[0],
+                      n_a=na, n_b=nb, n_sel_a=None if gate_a is None else gate_a[1], n_sel_b=None if gate_b is None else gate_b[1])
+    return z, summary[:, 2].cpu().numpy()
+
+
+def vc_convert_statics(wh, w, mu, cov, speaker):
+    """a speaker's utterances through the model: gmm_convert (the mixture) on [static, delta], then mlpg -> statics [P][F][D]"""
+    _, dyn, n = speaker
+    model = wh.gmm_prepare(w, mu, cov, dyn.shape[2])
+    mean, var = wh.gmm_convert(model, dyn.reshape(-1, dyn.shape[2]))
+    return wh.mlpg(mean.reshape(dyn.shape), var.reshape(dyn.shape), windows=VC_WINDOWS, n_frames=n)
 
 
 def _vc_train(a):
@@ -613,12 +668,27 @@ def _vc_train(a):
     if a.dim < 2 or a.mix < 1 or a.iter < 1 or len(a.src) != len(a.target):
         sys.exit(f"vc-train: --dim {a.dim} (at least 2: c0 and one more), --mix {a.mix}, --iter {a.iter}, {len(a.src)} source and "
                  f"{len(a.target)} target files (as many of each)")
+    if a.realign < 0 or (a.power_gate is not None and (a.fs is None or a.fs < 1)):
+        sys.exit(f"vc-train: --realign {a.realign} (0 or more); --power-gate needs --fs, the sampling rate the .mgc files were made at")
     wh = WorldHip()
     try:
-        rows = [vc_joint_rows(wh, torch.from_numpy(_float_rows("vc-train", s, a.dim)).to(wh.device),
-                              torch.from_numpy(_float_rows("vc-train", t, a.dim)).to(wh.device)) for s, t in zip(a.src, a.target)]
-        z = torch.cat(rows) if len(rows) > 1 else rows[0]
+        load = lambda files: vc_speaker(wh, [torch.from_numpy(_float_rows("vc-train", f, a.dim)).to(wh.device) for f in files])
+        src, tgt = load(a.src), load(a.target)
+        gates = [None, None]
+        if a.power_gate is not None:
+            gates = [vc_power_gate(wh, s[0], s[2], a.fs, a.power_gate) for s in (src, tgt)]
+            for g, s, name in zip(gates, (src, tgt), ("source", "target")):
+                if int(g[1].min()) < 1:
+                    sys.exit(f"vc-train: --power-gate {a.power_gate} dB keeps no frame of {name} file {int(g[1].argmin()) + 1}")
+                print(f"{name}: {int(g[1].sum())} of {int(s[2].sum())} frames at or above {a.power_gate} dB of their utterance's mean power")
+        z, mcd = vc_joint_rows(wh, src, tgt, *gates)
         w, mu, cov, loglik = wh.gmm_fit(z, a.mix, n_iter=a.iter, reg=a.reg)
+        for r in range(a.realign):
+            print(f"round {r}: {len(z)} joint rows, mean log-likelihood {loglik[-1]:.4f}, mean MCD along the paths {mcd.mean():.4f} dB")
+            z, mcd = vc_joint_rows(wh, src, tgt, *gates, align_a=vc_convert_statics(wh, w, mu, cov, src))
+            w, mu, cov, loglik = wh.gmm_fit(z, a.mix, n_iter=a.iter, reg=a.reg, init=(w, mu, cov))
+        if a.realign:
+            print(f"round {a.realign}: {len(z)} joint rows, mean log-likelihood {loglik[-1]:.4f}, mean MCD along the paths {mcd.mean():.4f} dB")
     except (ValueError, RuntimeError) as e:
         sys.exit(f"vc-train: {e}")
     np.savez(a.o, w=w, mu=mu, cov=cov, dim=np.int64(a.dim), dx=np.int64(2 * a.dim), loglik=loglik)
@@ -761,6 +831,12 @@ def main(argv=None):
     vt.add_argument("--mix", type=int, default=32, metavar="M", help="mixtures")
     vt.add_argument("--iter", type=int, default=20, metavar="N", help="EM iterations")
     vt.add_argument("--reg", type=float, default=1e-6, help="added to the diagonal of every covariance")
+    vt.add_argument("--power-gate", type=float, default=None, metavar="DB",
+                    help="align and train on the frames whose power is at least DB dB of their utterance's mean (-20: the usual "
+                         "silence gate), each speaker by itself; needs --fs")
+    vt.add_argument("--fs", type=int, default=None, metavar="F", help="the sampling rate the .mgc files were made at (Hz)")
+    vt.add_argument("--realign", type=int, default=0, metavar="R",
+                    help="R times: convert the sources with the fitted model, align the converted frames to the targets, refit")
     vt.add_argument("-o", required=True, metavar="model.npz")
     vt.set_defaults(run=_vc_train)
     vc = sub.add_parser("vc-convert", help="a model and a source .mgc -> the converted .mgc (deltas, conversion, MLPG)")
