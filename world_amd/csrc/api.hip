@@ -519,6 +519,7 @@ static void claim_prepared(WorldHipContext *c, WorldHipContext::PrepToken &mine,
 static void carve_cheaptrick(Arena &a, CtParams &p) {
   // the frame kernel keeps everything between x and the spectrogram in LDS: no per-frame scratch
   p.offsets = a.take<unsigned>((size_t)p.b.n_utt * p.b.f_stride);
+  p.frec = a.take<CtFrameRec>((size_t)p.b.n_utt * p.b.f_stride);       // written by the offsets' launch
 }
 static void carve_d4c(Arena &a, D4cParams &p) {
   CtParams below;
@@ -529,6 +530,7 @@ static void carve_d4c(Arena &a, D4cParams &p) {
   p.offsets1 = a.take<unsigned>(fr);
   p.draws2 = a.take<unsigned>(fr);
   p.draws1 = a.take<unsigned>(p.b.n_utt);
+  p.frec = a.take<D4cFrameRec>(fr);                                    // written by offsets1's launch
   p.coarse = a.take<double>(fr * 16);
   const size_t slot = d4c_park_slot_doubles(p.lg_d4c);
   p.park_ws = slot ? a.take<double>(slot * p.park_slots) : nullptr;
@@ -557,7 +559,7 @@ static void spectral_workspace(WorldHipContext *c, CtParams *ct, D4cParams *d4c,
     t.fft = d4c->fft_out; t.f0 = d4c->f0; t.tpos = d4c->tpos; t.opt = d4c->threshold;
     t.lo = reinterpret_cast<char *>(d4c->ap0) - c->arena.base; t.hi = c->arena.used;      // (ap0: D4C's first array)
     claim_prepared(c, c->prep_d4c, c->prep_ct, t, d4c->skip_prepare != 0, "D4C");
-    // from ap0: CheapTrick's part below it survives a D4C call, as the layout intends.  With skip_prepare ap0 .. draws1 are
+    // from ap0: CheapTrick's part below it survives a D4C call, as the layout intends.  With skip_prepare ap0 .. frec are
     // what the earlier call prepared; coarse and park_ws behind them are scratch that every call writes before it reads.
     char *lo = reinterpret_cast<char *>(d4c->skip_prepare ? d4c->coarse : d4c->ap0);
     devrt::dpoison(lo, c->arena.base + c->arena.used - lo, c->stream);
@@ -572,6 +574,10 @@ static void refuse_shape_limit(int what, int fs, int fft_size) {      // a call'
   const std::string lim = shape_limit(what, fs, fft_size);
   if (!lim.empty()) fail("%s", lim.c_str());
 }
+// WORLD_HIP_INKERNEL_CONSTS: the frame kernels and Harvest's filter bank evaluate their workgroup-uniform constants
+// themselves instead of reading them from the records their producers leave (stage_params.h: CtFrameRec, D4cFrameRec;
+// harvest.h: quirk) -- the comparison route of tests/test_gpu_frame_consts.py, read per call like WORLD_HIP_REFINE_FRAMES
+static bool inkernel_consts() { return getenv("WORLD_HIP_INKERNEL_CONSTS") != nullptr; }
 static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride,
                                  const int *x_length, const int *n_frames, int f_stride, const double *d_tpos,
                                  const double *d_f0, const CheapTrickOption *opt, double *d_sp, const RowLayout &lay,
@@ -595,6 +601,10 @@ static CtParams setup_cheaptrick(WorldHipContext *c, int n_utt, int fs, const do
   p.tab = c->tab;
   p.q1 = opt->q1;
   p.lg_fft = lg;
+  p.frec = nullptr;                                                    // (carve_cheaptrick)
+  p.frame_consts = inkernel_consts() ? 0 : 1;
+  p.frame_threads = ct_frame_threads(lg);
+  p.lift0 = (1.0 - 2.0 * opt->q1) + 2.0 * opt->q1;                     // ct_frame's k = 0 lifter: the kernel's own expression
   if (lay.frame_lo < 0 || lay.frame_hi < lay.frame_lo) fail("bad frame range [%d, %d)", lay.frame_lo, lay.frame_hi);
   p.frame_lo = lay.frame_lo; p.frame_hi = lay.frame_hi; p.skip_prepare = lay.skip_prepare ? 1 : 0;
   return p;
@@ -689,6 +699,15 @@ static D4cParams setup_d4c(WorldHipContext *c, int n_utt, int fs, const double *
   // d4c_frame's band transforms rely on the slice being at most 512 packed elements (3000 N / fs < 511.1 for every fs >= 15.8 kHz)
   if (wl / 2 + 1 > 512) fail("D4C: band window of %d samples at fs=%d exceeds the 1023 the frame kernel is built for", wl, fs);
   for (int b = 0; b < 8; ++b) p.band_center[b] = static_cast<int>(3000.0 * (b + 1) * fft_d4c / fs);      // d4c.cpp:207-208
+  // the launch's other constants, with the kernels' own expressions (d4c_love_frame, d4c_frame: their REC = false route)
+  p.frec = nullptr;                                                    // (carve_d4c)
+  p.frame_consts = inkernel_consts() ? 0 : 1;
+  p.love_threads = d4c_love_threads(p.lg_love);
+  p.frame_threads = d4c_frame_threads(p.lg_d4c);
+  p.love_b[0] = static_cast<int>(ceil(100.0 * fft_love / fs));
+  p.love_b[1] = static_cast<int>(ceil(4000.0 * fft_love / fs));
+  p.love_b[2] = static_cast<int>(ceil(7900.0 * fft_love / fs));
+  p.band_bnd = mround(fft_d4c * 8.0 / wl);
   if (lay.frame_lo < 0 || lay.frame_hi < lay.frame_lo) fail("bad frame range [%d, %d)", lay.frame_lo, lay.frame_hi);
   p.frame_lo = lay.frame_lo; p.frame_hi = lay.frame_hi;
   p.skip_prepare = lay.skip_prepare ? kD4cSkipScan | kD4cSkipLoveTrain : 0;
@@ -883,7 +902,7 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   begin_stage(c, [&](Arena &a) {
     p.nyq = a.take<double>(B * p.nyq_slices * 4);
     p.mean_part = a.take<double>(B * p.mean_parts);
-    p.quirk = a.take<double>(B * p.nch * 4);
+    p.quirk = a.take<double>(B * p.nch * kQuirkDoubles);
     p.fwd = a.take<double>(B * p.m_stride);
     p.y = a.take<double>(B * p.y_stride);
     p.events = a.take<double>(E * p.nch * 4 * p.ev_cap);
@@ -917,6 +936,7 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
                    ? reinterpret_cast<const double2 *>(p.win_lane + (size_t)hb.win_tab_len * WAVE * 2) : nullptr;
   // the candidate-major hv_refine serves the table route; this runs the frame-major kernel there instead (same bits)
   p.refine_frames = getenv("WORLD_HIP_REFINE_FRAMES") != nullptr;
+  p.inkernel_consts = inkernel_consts() ? 1 : 0;
   p.tpos = d_tpos; p.f0 = d_f0;
   launch_harvest(p, max_x, max_y, max_fb, max_fr, c->stream);
 #ifdef WORLD_EMU
@@ -1318,7 +1338,7 @@ static void run_spectral_stages(WorldHipContext *c, int n_utt, int fs, const dou
   // both stages' first offset scans depend on F0 alone: one launch serves both (two 1-workgroup kernels per job were two
   // of the narrow launches the twelve-jobs-in-flight mode pays 10-25 us apiece for)
   if (!cp.skip_prepare && !dp.skip_prepare) {
-    launch_spectral_prepare(cp, dp, c->stream);
+    launch_spectral_prepare(cp, dp, std::max(max_ct, max_d4c), c->stream);
     cp.skip_prepare = 1; dp.skip_prepare |= kD4cSkipScan;
   }
   launch_cheaptrick(cp, max_ct, c->stream);

@@ -32,7 +32,8 @@ __host__ __device__ __forceinline__ int ct_seg_cap(int N) {
 // ---------------------------------------------------------------------------
 __global__ void ct_prepare(CtParams p) {
   DYN_LDS(lds);
-  ct_offsets_utt(p, blockIdx.x, reinterpret_cast<double *>(lds));
+  if (blockIdx.y == 0) ct_offsets_utt(p, blockIdx.x, reinterpret_cast<double *>(lds));
+  else ct_records_utt(p, blockIdx.x, blockIdx.y - 1);                  // the grid's tail: the frames' constants (prepare.h)
 }
 
 // ---------------------------------------------------------------------------
@@ -40,15 +41,7 @@ __global__ void ct_prepare(CtParams p) {
 // radix-16 butterflies for 256 threads; smaller butterflies keep more threads busy per stage.
 constexpr int kCtMaxLr = 3;
 
-// LinearSmoothing's geometry for one frame (common.cpp:27-50): boundary bins and segment length
-struct CtSmooth { double width; int bnd, seg_len; };
-__device__ __forceinline__ CtSmooth ct_smooth_shape(double cf0, int N, int fs) {
-  CtSmooth s;
-  s.width = cf0 * 2.0 / 3.0;
-  s.bnd = static_cast<int>(s.width * N / fs) + 1;
-  s.seg_len = N / 2 + 2 * s.bnd + 1;
-  return s;
-}
+// (LinearSmoothing's geometry for one frame, ct_smooth_shape, lives in prepare.h with the frame's other constants)
 
 // ---- LinearSmoothing's prefix sum (common.cpp:85-86), SERIAL and in FP64 order -------------------------------------
 // `hi - lo` of the smoothing cancels up to 12 digits where the envelope sits at the noise floor, so any other summation
@@ -158,7 +151,9 @@ __device__ __forceinline__ void ct_wave_prefix_sum(double *seg, int seg_len) {
 // CODED: the instantiation that writes coded rows (CtParams::code_ndim > 0).  A kernel of its own: the coder's radix-16
 // transform raised the DENSE kernel's registers from 95 to 128 when both lived in one body -- four wavefronts per SIMD
 // instead of five, ct_frame +8 % in a batch (A/B, round 6).
-template <int PER, int LGN, int TB, bool CODED = false>
+// REC: the frame's uniform constants come from its record (CtParams::frec, written by the offset scan); false: every
+// thread evaluates them (prepare.h: ct_frame_consts -- the route WORLD_HIP_INKERNEL_CONSTS selects).
+template <int PER, int LGN, int TB, bool CODED = false, bool REC = true>
 // (the 4096-point frame owns 59 KB of LDS: two workgroups per CU whatever the registers, so it may have 256 of them --
 // its 48 window values per thread spilled at the 128 of four workgroups per CU)
 __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 2 : 4) ct_frame(CtParams p) {   // (threads, waves per SIMD)
@@ -181,26 +176,34 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
   const size_t fi = (size_t)u * p.b.f_stride + f;
   const double *x = p.b.x + (size_t)u * p.b.x_stride;
   const int x_len = p.b.x_len[u];
-  const double pos = p.tpos[fi];
-  const double cf0 = ct_effective_f0(p.f0[fi], p.f0_floor, fs);
   const uint32_t *noise = p.noise + p.offsets[fi];
   const int tid = wg_thread<TB>(), nt = wg_size<TB>();
+  // the frame's constants: fields of the record are read where they are first used (a workgroup-uniform address: scalar
+  // loads, nothing held in registers across the transforms)
+  CtFrameRec own;
+  const CtFrameRec *rec = &own;
+  if constexpr (REC) rec = p.frec + fi;
+  else own = ct_frame_consts(ct_effective_f0(p.f0[fi], p.f0_floor, fs), p.tpos[fi], fs, N, nt);
+  auto fld = [](auto *field) __attribute__((always_inline)) {            // a field of the record (scalar load) or of `own`
+    if constexpr (REC) return uniform_const_load(field); else return *field;
+  };
+  const double cf0 = fld(&rec->cf0);
   // (Round 5 tried fetching the NEXT round's draws -- the frame 1280 workgroups on, same XCD -- a dword per line while this
   // frame computes, and d4c_frame its own second and third windows' ahead of time: no change in either kernel, A/B in one call.
   // The window phases are bound by instruction issue among five resident workgroups, not by the cold stream.)
 
   WH_STAMP(0, 1);
   // ---- GetWindowedWaveform (cheaptrick.cpp:87-142) -------------------------
-  const int hw = mround(1.5 * fs / cf0);
+  const int hw = fld(&rec->hw);
   const int wlen = 2 * hw + 1;
-  const int origin = mround(pos * fs + 0.001);
+  const int origin = fld(&rec->origin);
   // One pass, one block reduction: with w the raw window, a = x w and n the dither, the
   // reference's normalised window is c w (c = 1/sqrt(sum w^2)), its waveform v = c a + n, and
   // the DC-balanced result v - c w (sum v / sum c w) -- all linear in four sums.  A thread keeps
   // the three values of each of its samples in registers; the frame's draws (sample order) come
   // from the noise stream.  cos(pi position f0) advances by a fixed angle from one of the thread's
   // samples to the next (they are nt apart): one sincospi pair per thread, then rotations.
-  const double win_scale = 1.0 / 1.5 / fs * cf0;        // position * f0 = (i - hw) / 1.5 / fs * f0
+  const double win_scale = fld(&rec->win_scale);              // position * f0 = (i - hw) / 1.5 / fs * f0
   {
     double wv[PER], av[PER], nv[PER];
     double s_ww = 0.0, s_a = 0.0, s_n = 0.0, s_w = 0.0;
@@ -219,9 +222,9 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
       }
 #pragma unroll
       for (int q = 0; q < PER; ++q) { xv[q] = keep(xv[q]); nz[q] = keep_word(nz[q]); }   // fetched here, not down in the branches
-      double rc, rs, dc, ds;
+      double rc, rs;
       sincospi(win_scale * (tid - hw), &rs, &rc);
-      sincospi(win_scale * nt, &ds, &dc);
+      const double dc = fld(&rec->step_c), ds = fld(&rec->step_s);    // sincospi(win_scale * nt)
 #pragma unroll
       for (int q = 0; q < PER; ++q) {
         const int i = tid + q * nt;
@@ -254,7 +257,7 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
   WH_STAMP(0, 3);
   // DCCorrection (common.cpp:56-75); replica staged in Z (dead now), then added
   {
-    const int upper = 2 + static_cast<int>(cf0 * N / fs);
+    const int upper = fld(&rec->upper);
     const int nrep = upper - 1;
     const double dx = -static_cast<double>(fs) / N;
     for (int i = tid; i < nrep; i += nt) {
@@ -269,7 +272,8 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
   WH_STAMP(0, 4);
   // ---- LinearSmoothing (common.cpp:27-111), width = 2/3 f0: the mirrored, scaled segment whose prefix sum the
   // reference walks serially, in LDS
-  const CtSmooth sm = ct_smooth_shape(cf0, N, fs);
+  CtSmooth sm;
+  sm.width = fld(&rec->width); sm.bnd = fld(&rec->bnd); sm.seg_len = half + 2 * sm.bnd + 1;     // ct_smooth_shape
   const double inv_n = 1.0 / N;
   block_map<4, double>(sm.seg_len,
     [&](int i) {
@@ -318,7 +322,7 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
   __syncthreads();
   WH_STAMP(0, 6);
   {
-    const double origin_axis = -(sm.bnd - 0.5) * fs / N;
+    const double origin_axis = fld(&rec->origin_axis);
     const double step = static_cast<double>(fs) / N;
     // hi - lo cancels up to 12 digits where the envelope sits at the noise floor:
     // the interpolation weights and the final quotient keep the reference's exact operations
@@ -339,7 +343,8 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
   WH_STAMP(0, 7);
   // ---- SmoothingWithRecovery (cheaptrick.cpp:22-57) -------------------------
   // the symmetric extension of the log spectrum is read by the first FFT stage directly from P.
-  const double q1 = p.q1, f0_over_fs = cf0 / fs;
+  const double q1 = p.q1, f0_over_fs = fld(&rec->f0_over_fs);
+  const double lift0 = REC ? p.lift0 : (1.0 - 2.0 * q1) + 2.0 * q1;
   auto mirrored = [&](int i) { return i <= half ? P[i] : P[N - i]; };
   block_rfft_from<kCtMaxLr, LGN>(Z, lgn, tw, [&](int n) { cplx v; v.re = mirrored(2 * n); v.im = mirrored(2 * n + 1); return v; },
                   [&](int k, double re, double im) {
@@ -349,7 +354,7 @@ __global__ void __launch_bounds__(TB > 0 ? TB : 256, TB > 256 ? 1 : LGN == 12 ? 
     double sl, cl;
     if (k == 0) {
       sl = 1.0;
-      cl = (1.0 - 2.0 * q1) + 2.0 * q1;
+      cl = lift0;
     } else {
       const double a = static_cast<double>(k) * f0_over_fs;
       const double sp = sinpi(a);
@@ -398,33 +403,46 @@ size_t ct_frame_lds_bytes(int lg_fft) {
   return sizeof(double) * (size_t)(ct_seg_cap(N) + nb + 1 + ((nb + 1) & 1) + 64 + N / 8 + 2);
 }
 
+// threads of a ct_frame workgroup (launch_cheaptrick's choices; the emulator's blocks are one thread)
+int ct_frame_threads(int lg_fft) {
+#ifdef WORLD_EMU
+  (void)lg_fft;
+  return 1;
+#else
+  return lg_fft == 13 ? 512 : (lg_fft == 11 || lg_fft == 12) ? 256 : 128;
+#endif
+}
 size_t ct_max_draws_per_frame(int fft_size) { return (size_t)fft_size + fft_size / 2 + 1; }   // window < fft_size, + bins
 
 void launch_cheaptrick(const CtParams &p, int max_frames_all, hipStream_t stream) {
-  if (!p.skip_prepare) WH_BLOCKS(ct_prepare, dim3(p.b.n_utt), 1024, 64 * sizeof(double), stream, p);    // 1024 threads: a 10 s utterance is two scans
+  if (!p.skip_prepare) WH_BLOCKS(ct_prepare, dim3(p.b.n_utt, 1 + rec_chunks(max_frames_all)), 1024, 64 * sizeof(double), stream, p);    // 1024 threads: a 10 s utterance is two scans
   const int max_frames = imin(max_frames_all, p.frame_hi) - p.frame_lo;          // frames of the range
   if (max_frames <= 0) return;
   const dim3 grid(max_frames, p.b.n_utt);
   const size_t lds = ct_frame_lds_bytes(p.lg_fft);
+  auto launch = [&](auto rec) {
+    constexpr bool R = decltype(rec)::value;
 #ifdef WORLD_EMU
-  if (p.code_ndim > 0) devrt::launch_blocks("ct_frame_coded", ct_frame<8192, 0, 0, true>, grid, 256, lds, stream, p);
-  else devrt::launch_blocks("ct_frame", ct_frame<8192, 0, 0>, grid, 256, lds, stream, p);
+    if (p.code_ndim > 0) devrt::launch_blocks("ct_frame_coded", ct_frame<8192, 0, 0, true, R>, grid, 256, lds, stream, p);
+    else devrt::launch_blocks("ct_frame", ct_frame<8192, 0, 0, false, R>, grid, 256, lds, stream, p);
 #else
-  // Workgroup size follows the transform: fft_size 1024 (fs <= 24 kHz) runs with 128 threads (64 butterflies per
-  // radix-8 stage; measured 1.33 ms for 64 x 1001 frames against 1.60 with 256 threads and 1.49 with 64), 2048 and
-  // 4096 with 256.  The three sizes the sampling rates of speech lead to get compile-time plans.
-  if (p.code_ndim > 0) {
-    if (p.lg_fft == 10) devrt::launch_blocks("ct_frame_coded", ct_frame<8, 10, 128, true>, grid, 128, lds, stream, p);
-    else if (p.lg_fft == 11) devrt::launch_blocks("ct_frame_coded", ct_frame<8, 11, 256, true>, grid, 256, lds, stream, p);
-    else if (p.lg_fft == 12) devrt::launch_blocks("ct_frame_coded", ct_frame<16, 12, 256, true>, grid, 256, lds, stream, p);
-    else if (p.lg_fft == 13) devrt::launch_blocks("ct_frame_coded", ct_frame<16, 0, 512, true>, grid, 512, lds, stream, p);
-    else devrt::launch_blocks("ct_frame_coded", ct_frame<8, 0, 128, true>, grid, 128, lds, stream, p);
-  } else if (p.lg_fft == 10) devrt::launch_blocks("ct_frame", ct_frame<8, 10, 128>, grid, 128, lds, stream, p);
-  else if (p.lg_fft == 11) devrt::launch_blocks("ct_frame", ct_frame<8, 11, 256>, grid, 256, lds, stream, p);
-  else if (p.lg_fft == 12) devrt::launch_blocks("ct_frame", ct_frame<16, 12, 256>, grid, 256, lds, stream, p);
-  else if (p.lg_fft == 13) devrt::launch_blocks("ct_frame", ct_frame<16, 0, 512>, grid, 512, lds, stream, p);
-  else devrt::launch_blocks("ct_frame", ct_frame<8, 0, 128>, grid, 128, lds, stream, p);
+    // Workgroup size follows the transform (ct_frame_threads): fft_size 1024 (fs <= 24 kHz) runs with 128 threads (64
+    // butterflies per radix-8 stage; measured 1.33 ms for 64 x 1001 frames against 1.60 with 256 threads and 1.49 with 64),
+    // 2048 and 4096 with 256.  The three sizes the sampling rates of speech lead to get compile-time plans.
+    if (p.code_ndim > 0) {
+      if (p.lg_fft == 10) devrt::launch_blocks("ct_frame_coded", ct_frame<8, 10, 128, true, R>, grid, 128, lds, stream, p);
+      else if (p.lg_fft == 11) devrt::launch_blocks("ct_frame_coded", ct_frame<8, 11, 256, true, R>, grid, 256, lds, stream, p);
+      else if (p.lg_fft == 12) devrt::launch_blocks("ct_frame_coded", ct_frame<16, 12, 256, true, R>, grid, 256, lds, stream, p);
+      else if (p.lg_fft == 13) devrt::launch_blocks("ct_frame_coded", ct_frame<16, 0, 512, true, R>, grid, 512, lds, stream, p);
+      else devrt::launch_blocks("ct_frame_coded", ct_frame<8, 0, 128, true, R>, grid, 128, lds, stream, p);
+    } else if (p.lg_fft == 10) devrt::launch_blocks("ct_frame", ct_frame<8, 10, 128, false, R>, grid, 128, lds, stream, p);
+    else if (p.lg_fft == 11) devrt::launch_blocks("ct_frame", ct_frame<8, 11, 256, false, R>, grid, 256, lds, stream, p);
+    else if (p.lg_fft == 12) devrt::launch_blocks("ct_frame", ct_frame<16, 12, 256, false, R>, grid, 256, lds, stream, p);
+    else if (p.lg_fft == 13) devrt::launch_blocks("ct_frame", ct_frame<16, 0, 512, false, R>, grid, 512, lds, stream, p);
+    else devrt::launch_blocks("ct_frame", ct_frame<8, 0, 128, false, R>, grid, 128, lds, stream, p);
 #endif
+  };
+  if (p.frame_consts) launch(std::true_type()); else launch(std::false_type());
 }
 
 }  // namespace world_hip

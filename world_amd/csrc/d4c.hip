@@ -37,6 +37,7 @@
 #ifndef WH_SWZ
 #define WH_SWZ 1
 #endif
+#include <type_traits>
 #include "stage_params.h"
 #include "prepare.h"
 #include "trace.h"
@@ -50,12 +51,17 @@ constexpr int kHanning = 1, kBlackman = 2;
 // ---------------------------------------------------------------------------
 __global__ void d4c_prepare1(D4cParams p) {
   DYN_LDS(lds);
-  d4c_offsets1_utt(p, blockIdx.x, reinterpret_cast<double *>(lds));
+  if (blockIdx.y == 0) d4c_offsets1_utt(p, blockIdx.x, reinterpret_cast<double *>(lds));
+  else d4c_records_utt(p, blockIdx.x, blockIdx.y - 1);                 // the grid's tail: the frames' constants (prepare.h)
 }
-// CheapTrick's scan and D4C's first in one launch (grid (n_utt, 2)): both follow from F0 alone (prepare.h)
+// CheapTrick's scan and D4C's first in one launch (grid (n_utt, 2, 1 + record chunks)): both follow from F0 alone (prepare.h),
+// and so do the frames' constants, which the workgroups behind z = 0 write
 __global__ void spectral_prepare(CtParams cp, D4cParams dp) {
   DYN_LDS(lds);
-  if (blockIdx.y == 0) ct_offsets_utt(cp, blockIdx.x, reinterpret_cast<double *>(lds));
+  if (blockIdx.z > 0) {
+    if (blockIdx.y == 0) ct_records_utt(cp, blockIdx.x, blockIdx.z - 1);
+    else d4c_records_utt(dp, blockIdx.x, blockIdx.z - 1);
+  } else if (blockIdx.y == 0) ct_offsets_utt(cp, blockIdx.x, reinterpret_cast<double *>(lds));
   else d4c_offsets1_utt(dp, blockIdx.x, reinterpret_cast<double *>(lds));
 }
 
@@ -398,24 +404,26 @@ struct D4cWin {            // GetWindowedWaveform's parameters (d4c.cpp:52-84)
   int x_len, hw, wlen, origin, kind;
   double scale;
 };
-__device__ __forceinline__ D4cWin d4c_win(const double *x, int x_len, int fs, double f0, double pos, int kind, double ratio,
+// hw, origin, scale: d4c_win_half / d4c_win_origin / d4c_win_scale (prepare.h), from the frame's record or evaluated here
+__device__ __forceinline__ D4cWin d4c_win(const double *x, int x_len, int hw, int origin, double scale, int kind,
                                           const uint32_t *noise) {
   D4cWin w;
   w.x = x; w.x_len = x_len; w.noise = noise; w.kind = kind;
-  w.hw = mround(ratio * fs / f0 / 2.0);
+  w.hw = hw;
   w.wlen = 2 * w.hw + 1;
-  w.origin = mround(pos * fs + 0.001);
-  w.scale = 2.0 / ratio / fs * f0;
+  w.origin = origin;
+  w.scale = scale;
   return w;
 }
 // The window of a thread's samples i0, i0 + step, i0 + 2 step, ... by rotation: cos(pi scale (i - hw)) advances by
 // a fixed angle per sample, so one sincospi pair per thread and pass replaces one cospi per sample (the window
 // evaluations were a fifth of the frame kernel's instructions).  At most N / T = 16 rotations on the GPU.
 struct D4cWinRot { double c, s, dc, ds; };
-__device__ __forceinline__ D4cWinRot d4c_win_rot(const D4cWin &w, int i0, int step) {
+// step_s, step_c: sincospi(w.scale * step) -- the same in every thread (the frame's record); the start angle is the thread's own
+__device__ __forceinline__ D4cWinRot d4c_win_rot(const D4cWin &w, int i0, double step_s, double step_c) {
   D4cWinRot r;
   sincospi(w.scale * (i0 - w.hw), &r.s, &r.c);
-  sincospi(w.scale * step, &r.ds, &r.dc);
+  r.ds = step_s; r.dc = step_c;
   return r;
 }
 __device__ __forceinline__ double d4c_win_next(const D4cWin &w, D4cWinRot &r) {   // value at the current sample, then advance
@@ -449,7 +457,9 @@ __device__ __forceinline__ double d4c_window_to_lds(const D4cWin &w, const D4cWi
 // ---------------------------------------------------------------------------
 // D4CLoveTrain (d4c.cpp:227-285): is the frame voiced enough to analyse?  LGN: log2 of the transform when the
 // instantiation fixes it (compile-time plan), 0 = p.lg_love.
-template <int LGN>
+// REC: the frame's uniform constants come from its record and the launch's from the host (D4cParams::frec, love_b); false: every
+// thread evaluates them (the route WORLD_HIP_INKERNEL_CONSTS selects).
+template <int LGN, bool REC>
 __device__ __forceinline__ void d4c_love_frame(const D4cParams &p, char *lds) {
   const int u = blockIdx.y, f = blockIdx.x;
   if (f >= p.b.n_frames[u]) return;
@@ -461,13 +471,19 @@ __device__ __forceinline__ void d4c_love_frame(const D4cParams &p, char *lds) {
   double *Zr = reinterpret_cast<double *>(lds);
   double *scratch = Zr + M;
   const TwLds tw = stage_twiddles(scratch + 64, lgn - 1, p.tab.tw);    // inner complex transform's table
-  const double cf0 = f0 > 40.0 ? f0 : 40.0;                            // d4c.cpp:263,279
-  const D4cWin w = d4c_win(p.b.x + (size_t)u * p.b.x_stride, p.b.x_len[u], fs, cf0, p.tpos[fi], kBlackman, 3.0,
-                           p.noise + p.offsets1[fi]);
-  const D4cWinRot rot0 = d4c_win_rot(w, threadIdx.x, blockDim.x);
-  const int b0 = static_cast<int>(ceil(100.0 * M / fs));
-  const int b1 = static_cast<int>(ceil(4000.0 * M / fs));
-  const int b2 = static_cast<int>(ceil(7900.0 * M / fs));
+  D4cFrameRec own;
+  const D4cFrameRec *rec = &own;
+  if constexpr (REC) rec = p.frec + fi;
+  else d4c_love_consts(own, f0, p.tpos[fi], fs, blockDim.x);
+  auto fld = [](auto *field) __attribute__((always_inline)) {            // a field of the record (scalar load) or of `own`
+    if constexpr (REC) return uniform_const_load(field); else return *field;
+  };
+  const D4cWin w = d4c_win(p.b.x + (size_t)u * p.b.x_stride, p.b.x_len[u], fld(&rec->love_hw), fld(&rec->love_origin), fld(&rec->love_scale),
+                           kBlackman, p.noise + p.offsets1[fi]);
+  const D4cWinRot rot0 = d4c_win_rot(w, threadIdx.x, fld(&rec->love_step_s), fld(&rec->love_step_c));
+  const int b0 = REC ? p.love_b[0] : static_cast<int>(ceil(100.0 * M / fs));
+  const int b1 = REC ? p.love_b[1] : static_cast<int>(ceil(4000.0 * M / fs));
+  const int b2 = REC ? p.love_b[2] : static_cast<int>(ceil(7900.0 * M / fs));
   double lo = 0.0, hi = 0.0;     // cumulative power (b0, b1] and (b0, b2]   (d4c.cpp:241-249)
   auto band_power = [&](int k, double re, double im) __attribute__((always_inline)) {
     if (k > b0 && k <= b2) {
@@ -524,13 +540,14 @@ __device__ __forceinline__ void d4c_love_frame(const D4cParams &p, char *lds) {
     // statistic keeps the frame out of the second pass.  Their positions in the stream are a prefix sum over the
     // utterance's frames, which every d4c_frame workgroup forms for itself (round 4: a 1-workgroup scan kernel per job).
     const double bf0 = kFloorF0D4C > f0 ? kFloorF0D4C : f0;
-    p.draws2[fi] = ap0 <= p.threshold ? 0u : 3u * (unsigned)(2 * mround(4.0 * fs / bf0 / 2.0) + 1);
+    const int body_hw = REC ? fld(&rec->hw) : d4c_win_half(4.0, fs, bf0);
+    p.draws2[fi] = ap0 <= p.threshold ? 0u : 3u * (unsigned)(2 * body_hw + 1);
   }
 }
-template <int LGN>
+template <int LGN, bool REC = true>
 __global__ void __launch_bounds__(256) d4c_lovetrain(D4cParams p) {
   DYN_LDS(lds);
-  d4c_love_frame<LGN>(p, lds);
+  d4c_love_frame<LGN, REC>(p, lds);
 }
 
 // Resident waves per SIMD the register allocation aims at: 3 (three 256-thread workgroups per CU, 168 VGPRs;
@@ -568,7 +585,8 @@ __host__ __device__ constexpr size_t d4c_frame_direct_tw_offset(int lg) {
   const size_t park = lg > 13 ? 0 : N / 2 + 2;          // (the 16384-point shape parks in global memory: d4c_frame)
   return sizeof(double) * (N + 64 + ((size_t)1 << (lg - D4C_TW_LEVEL - 2)) + 2 + park + 16 * (N / 1024 > 1 ? N / 1024 : 1));
 }
-template <int NMAX, int T>
+// REC: as d4c_love_frame
+template <int NMAX, int T, bool REC = true>
 __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   constexpr int kItems = D4cShape<NMAX, T>::kItems, kBins = D4cShape<NMAX, T>::kBins, kLo = D4cShape<NMAX, T>::kLo;
   constexpr bool kRot = T * 16 == NMAX;                                // twiddles by constant rotation (fft.h)
@@ -578,12 +596,12 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   int tid = wg_thread<T>();
   constexpr int nt = T;                                                // launch_d4c launches exactly T threads
   // Everything the workgroup needs from global memory before its first window is REQUESTED here, ahead of the two early
-  // exits and of the table staging: the frame's F0 and LoveTrain statistic, its position, the utterance's length and
+  // exits and of the table staging: the frame's F0 and LoveTrain statistic, the utterance's length and
   // first-pass draw count, and the thread's share of the earlier frames' draw counts.  Asked for where each is first used
   // they were six dependent trips to L2 (n_frames -> F0 -> statistic -> tables -> counts, two at a time -> position):
   // ~9 of the frame's 157 thousand cycles in a loaded CU (tools/trace_batch.py).
   const int nf_u = p.b.n_frames[u];
-  const double f0_in = p.f0[fi], ap0_in = p.ap0[fi], pos = p.tpos[fi];
+  const double f0_in = p.f0[fi], ap0_in = p.ap0[fi];
   const int x_len = p.b.x_len[u];
   const unsigned draws1_u = p.draws1[u];
   constexpr int kCntAhead = 8;                                         // counts per thread in flight: 8 T frames = 10 s at 48 kHz
@@ -642,7 +660,15 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   };
 
   const double *x = p.b.x + (size_t)u * p.b.x_stride;
-  const double cf0 = kFloorF0D4C > f0 ? kFloorF0D4C : f0;
+  // the frame's constants: fields of the record are read where they are first used (a workgroup-uniform address: scalar
+  // loads -- a field held across the transforms would cost more than reading it again)
+  D4cFrameRec own;
+  const D4cFrameRec *rec = &own;
+  if constexpr (REC) rec = p.frec + fi;
+  else d4c_body_consts(own, f0, p.tpos[fi], fs, N, nt);
+  auto fld = [](auto *field) __attribute__((always_inline)) {            // a field of the record (scalar load) or of `own`
+    if constexpr (REC) return uniform_const_load(field); else return *field;
+  };
   // Where the frame's draws sit in the reference's one randn() stream: behind the first pass's (draws1) and behind those
   // of every earlier frame of the utterance that LoveTrain let through -- <= 8 KB of counts summed by the workgroup itself.
   unsigned stream_at;
@@ -664,7 +690,7 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
     // before everybody has arrived there -- past these reads)
   }
   const uint32_t *noise = p.noise + stream_at;
-  const int wdraws = 2 * mround(4.0 * fs / cf0 / 2.0) + 1;
+  const int wdraws = 2 * fld(&rec->hw) + 1;
   // `park` (N/2 + 2 doubles: the centroid sum, then the static group delay) lives in LDS beside the transform -- except
   // for the 16384-point shape (96 kHz < fs <= 192 kHz), whose transform buffer alone takes 128 of the CU's 160 KB: there
   // it is the workgroup's slot of a global staging area (launch_d4c hands out p.park_slots of them per launch; a slot is
@@ -676,17 +702,15 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
 
   // DCCorrection (common.cpp:56-75) on register bins: the few low bins it mirrors go through LDS
   auto dc_correct = [&](double (&S)[kBins], auto for_own) __attribute__((always_inline)) {
-    const int upper = 2 + static_cast<int>(cf0 * N / fs), nrep = upper - 1;
-    const double inv_dx = -static_cast<double>(N) / fs;
+    const int upper = fld(&rec->upper), nrep = upper - 1;
     __syncthreads();
     for_own([&](int slot, int k) { if (k <= upper) Zr[k] = S[slot]; });
     __syncthreads();
     // interp1Q at k fs / N on the axis cf0 - j fs / N: position cf0 N / fs - k -- the SAME fraction for every bin, and
     // the knot index a constant minus k (the per-bin subtract / scale / convert / clamp of the general routine was a
     // quarter of this pass's instructions; the weights agree to the rounding of the position, ~1e-13)
-    const double pos0 = (0.0 - cf0) * inv_dx;
-    const int b0 = static_cast<int>(pos0);
-    const double fr0 = pos0 - b0;
+    const int b0 = fld(&rec->b0);                                  // (d4c_body_consts: pos0 = cf0 N / fs, its integer part and fraction)
+    const double fr0 = fld(&rec->fr0);
     for_own([&](int slot, int k) {
       if (k < nrep) {
         const int b = b0 - k;                                // 1 <= b <= upper - 1 for k < nrep = upper - 1 ... b0 = upper - 2
@@ -699,8 +723,9 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   // LinearSmoothing (common.cpp:27-111): register bins -> mirrored segment in LDS -> block prefix sum -> register bins;
   // the input and the output may be owned differently
   // pre: a barrier first (whoever read Zr last is not behind one yet)
-  auto smooth = [&](const double (&in)[kBins], auto for_in, double width, double (&out)[kBins], auto for_out, const bool pre = true) __attribute__((always_inline)) {
-    const int bnd = static_cast<int>(width * N / fs) + 1;
+  // sc: the width's constants (d4c_smooth_consts; rec->sm[0]: width cf0, [1]: cf0 / 2)
+  auto smooth = [&](const double (&in)[kBins], auto for_in, const D4cSmoothConsts *sc, double (&out)[kBins], auto for_out, const bool pre = true) __attribute__((always_inline)) {
+    const int bnd = fld(&sc->bnd);
     const int seg_len = H + 2 * bnd + 1;
     if (pre) __syncthreads();
     for_in([&](int slot, int k) {
@@ -710,16 +735,14 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
       if (k < H && k >= H - bnd) Zr[2 * H + bnd - k] = v;
     });
     block_scan_incl_double<T>(Zr, seg_len, scratch);
-    const double origin_axis = -(bnd - 0.5) * fs / N;
-    const double inv_step = static_cast<double>(N) / fs, inv_width = 1.0 / width;
+    const double inv_width = fld(&sc->inv_width);
     // interp1Q of the prefix sums at k fs / N -+ width / 2: on the segment's axis that is position k + c_lo and k + c_hi
     // with c_lo = bnd - 0.5 - r / 2, c_hi = c_lo + r (r = width N / fs) -- the fractions are the same for EVERY bin and
     // the knot indices are k plus a constant.  The general routine recomputed position, index, fraction and an end clamp
     // per bin and edge (24 VALU instructions per bin; 6 here); the weights agree to the rounding of the position
     // (~1e-13), and k + floor(c_hi) + 1 <= H + 1.5 r + 2 < seg_len - 1: no clamp can ever apply.
-    const double c_lo = (0.0 - width / 2.0 - origin_axis) * inv_step, c_hi = (width / 2.0 - origin_axis) * inv_step;
-    const int i_lo = static_cast<int>(c_lo), i_hi = static_cast<int>(c_hi);
-    const double f_lo = c_lo - i_lo, f_hi = c_hi - i_hi;
+    const int i_lo = fld(&sc->i_lo), i_hi = fld(&sc->i_hi);
+    const double f_lo = fld(&sc->f_lo), f_hi = fld(&sc->f_hi);
     const double *z_lo = Zr + i_lo, *z_hi = Zr + i_hi;
     for_out([&](int slot, int k) {
       const double l0 = z_lo[k], l1 = z_lo[k + 1], h0 = z_hi[k], h1 = z_hi[k + 1];
@@ -732,7 +755,8 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   // The frame's three windows -- two Blackman for the centroid, one Hanning for the power spectrum -- share their
   // length and their angle per sample (ratio 4, the same F0: d4c.cpp:97,101,155), so the cosine every one of them
   // is built from starts and advances identically: one sincospi pair per frame.
-  const D4cWinRot rot0 = d4c_win_rot(d4c_win(x, x_len, fs, cf0, pos, kHanning, 4.0, noise), tid, nt);
+  const D4cWinRot rot0 = d4c_win_rot(d4c_win(x, x_len, fld(&rec->hw), fld(&rec->origin[2]), fld(&rec->scale), kHanning, noise), tid,
+                                     fld(&rec->step_s), fld(&rec->step_c));
 
   // One window (d4c.cpp:52-84): the thread's samples below N/2 -- i = tid + j T, j < kLo -- balanced and in registers
   // (0 beyond the window); returns the balance coefficient.  Samples at and above N/2 exist only for windows longer
@@ -821,8 +845,7 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   // own pairs): nothing but the window's samples waits in registers through the transforms.
 #pragma unroll 1
   for (int c = 0; c < 2; ++c) {
-    const D4cWin w = d4c_win(x, x_len, fs, cf0, c == 0 ? pos - 0.25 / cf0 : pos + 0.25 / cf0, kBlackman, 4.0,
-                             noise + (size_t)c * wdraws);
+    const D4cWin w = d4c_win(x, x_len, fld(&rec->hw), fld(&rec->origin[c]), fld(&rec->scale), kBlackman, noise + (size_t)c * wdraws);
     D4C_FRESH_TID();
     double ulo[kLo];
     const double coef = balanced(w, ulo);
@@ -890,7 +913,7 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   // ---- GetSmoothedPowerSpectrum (d4c.cpp:149-166) ----------------------------
   double B[kBins];
   {
-    const D4cWin w = d4c_win(x, x_len, fs, cf0, pos, kHanning, 4.0, noise + (size_t)2 * wdraws);
+    const D4cWin w = d4c_win(x, x_len, fld(&rec->hw), fld(&rec->origin[2]), fld(&rec->scale), kHanning, noise + (size_t)2 * wdraws);
     double ulo[kLo];
     const double coef = balanced(w, ulo);
 #pragma unroll
@@ -912,11 +935,10 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
     // mirrored bins sit in lanes of the first wavefront (upper < 64: F0 below ~715 Hz at 48 kHz) the two neighbours of
     // the interpolation come by lane index -- no staging of the low bins in Z, and none of the pass's three barriers
     // (the waves that have nothing to correct walk on to the smoothing's first barrier).  Same operands, same order.
-    if (2 + static_cast<int>(cf0 * N / fs) < WAVE) {
-      const int upper = 2 + static_cast<int>(cf0 * N / fs), nrep = upper - 1;
-      const double pos0 = (0.0 - cf0) * (-static_cast<double>(N) / fs);
-      const int b0 = static_cast<int>(pos0);
-      const double fr0 = pos0 - b0;
+    if (fld(&rec->upper) < WAVE) {
+      const int upper = fld(&rec->upper), nrep = upper - 1;
+      const int b0 = fld(&rec->b0);
+      const double fr0 = fld(&rec->fr0);
       if (wave_in_block() == 0) {
         const int b = b0 - lane_id();                         // 1 <= b <= upper - 2 for the lanes that are corrected
         const double y0 = __shfl(Bn[0], b & (WAVE - 1), WAVE), y1 = __shfl(Bn[0], (b + 1 <= upper ? b + 1 : upper) & (WAVE - 1), WAVE);
@@ -925,7 +947,7 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
     } else
     dc_correct(Bn, for_nat);
     // (the transform's readers are behind the merge's closing barrier -- and dc_correct's own, if it ran: no barrier in front)
-    smooth(Bn, for_nat, cf0, B, for_pair, false);
+    smooth(Bn, for_nat, &rec->sm[0], B, for_pair, false);
   }
   WH_STAMP(32, 12);
   lds_dead(Zr, N);                                         // (the smoothing segment is dead: DCCorrection below stages its own bins)
@@ -935,10 +957,9 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
   // the centroid (the thread's own pairs) with its DCCorrection (d4c.cpp:141-142) on the way: the bins the correction
   // mirrors are in `park` already, in natural order -- no staging in Z, no barriers (round 4: three)
   {
-    const int upper = 2 + static_cast<int>(cf0 * N / fs), nrep = upper - 1;
-    const double pos0 = (0.0 - cf0) * (-static_cast<double>(N) / fs);
-    const int b0 = static_cast<int>(pos0);
-    const double fr0 = pos0 - b0;
+    const int upper = fld(&rec->upper), nrep = upper - 1;
+    const int b0 = fld(&rec->b0);
+    const double fr0 = fld(&rec->fr0);
     for_pair([&](int slot, int k) {
       double v = park[k];
       if (k < nrep) {
@@ -954,17 +975,17 @@ __global__ void __launch_bounds__(T, D4C_MIN_WAVES) d4c_frame(D4cParams p) {
 #pragma unroll
   for (int e = 0; e < kBins; ++e) A[e] = fast_div(A[e], B[e]);        // the smoothed power spectrum is positive and normal
   D4C_FRESH_TID();
-  smooth(A, for_pair, cf0 / 2.0, A, for_pair);
+  smooth(A, for_pair, &rec->sm[1], A, for_pair);
   WH_STAMP(32, 14);
   D4C_FRESH_TID();
-  smooth(A, for_pair, cf0, B, for_pair);
+  smooth(A, for_pair, &rec->sm[0], B, for_pair);
   // The group delay takes the centroid sum's place in `park` (natural bin order, N/2 + 1 doubles): the band transforms
   // below read their slices from there -- no staging pass, and nothing bin-indexed in registers through the hottest loop.
   for_pair([&](int slot, int k) { park[k] = A[slot] - B[slot]; });
   WH_STAMP(32, 15);
 
   // ---- GetCoarseAperiodicity (d4c.cpp:194-225) per 3 kHz band ------------------
-  const int bnd = mround(N * 8.0 / p.wl);
+  const int bnd = REC ? p.band_bnd : mround(N * 8.0 / p.wl);
   const int hwl = p.wl / 2, wl = 2 * hwl + 1;
   const int nz = hwl + 1;                               // packed complex input elements that are not zero
   int mine = 0;
@@ -1163,26 +1184,32 @@ size_t d4c_frame_lds_bytes(int lg) {
 // doubles of one workgroup's slot of D4cParams::park_ws (0: the shape parks in LDS)
 size_t d4c_park_slot_doubles(int lg) { return lg > 13 ? ((size_t)1 << (lg - 1)) + 2 : 0; }
 int d4c_frame_threads(int lg) { return (1 << lg) / 16; }   // one radix-8 butterfly per thread and stage
+int d4c_love_threads(int lg) { return lg <= 11 ? 128 : 256; }
 // worst case per frame: LoveTrain window at 40 Hz + 3 body windows at 47 Hz
 size_t d4c_max_draws_per_frame(int fs) {
   return (size_t)(2 * mround(3.0 * fs / 40.0 / 2.0) + 1) + 3 * (size_t)(2 * mround(4.0 * fs / kFloorF0D4C / 2.0) + 1);
 }
 
-void launch_spectral_prepare(const CtParams &cp, const D4cParams &dp, hipStream_t stream) {
-  WH_BLOCKS(spectral_prepare, dim3(cp.b.n_utt, 2), 256, 64 * sizeof(double), stream, cp, dp);     // (four wavefronts: what finds room beside other jobs' frame kernels)
+void launch_spectral_prepare(const CtParams &cp, const D4cParams &dp, int max_frames, hipStream_t stream) {
+  WH_BLOCKS(spectral_prepare, dim3(cp.b.n_utt, 2, 1 + rec_chunks(max_frames)), 256, 64 * sizeof(double), stream, cp, dp);     // (four wavefronts: what finds room beside other jobs' frame kernels)
 }
 
 void launch_d4c(const D4cParams &p, int max_frames, hipStream_t stream) {
-  if (!(p.skip_prepare & kD4cSkipScan)) WH_BLOCKS(d4c_prepare1, dim3(p.b.n_utt), 1024, 64 * sizeof(double), stream, p);
+  if (!(p.skip_prepare & kD4cSkipScan)) WH_BLOCKS(d4c_prepare1, dim3(p.b.n_utt, 1 + rec_chunks(max_frames)), 1024, 64 * sizeof(double), stream, p);
   if (!(p.skip_prepare & kD4cSkipLoveTrain) && max_frames > 0) {
     // workgroup sizes follow the transform size (threads beyond N/16 idle through every radix-8 stage): for the
     // 2048-point internal FFT of fs <= 24 kHz, 64 x 1001 frames: lovetrain 0.53 -> 0.42 ms, groupdelay 3.77 -> 2.52,
     // band 0.97 -> 0.65
     const dim3 love_grid(max_frames, p.b.n_utt);
     const size_t love_lds = d4c_love_lds_bytes(p.lg_love);
-    if (p.lg_love == 11) devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<11>, love_grid, 128, love_lds, stream, p);
-    else if (p.lg_love == 12) devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<12>, love_grid, 256, love_lds, stream, p);
-    else devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<0>, love_grid, p.lg_love <= 11 ? 128 : 256, love_lds, stream, p);
+    const int love_nt = d4c_love_threads(p.lg_love);
+    auto love = [&](auto rec) {
+      constexpr bool R = decltype(rec)::value;
+      if (p.lg_love == 11) devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<11, R>, love_grid, love_nt, love_lds, stream, p);
+      else if (p.lg_love == 12) devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<12, R>, love_grid, love_nt, love_lds, stream, p);
+      else devrt::launch_blocks("d4c_lovetrain", d4c_lovetrain<0, R>, love_grid, love_nt, love_lds, stream, p);
+    };
+    if (p.frame_consts) love(std::true_type()); else love(std::false_type());
   }
   // one radix-8 butterfly per thread: 128 / 256 / 512 threads for the 2048- / 4096- / 8192-point internal FFT
   // (fs <= 24 kHz / <= 48 kHz / <= 96 kHz); the register arrays are sized per shape
@@ -1197,10 +1224,14 @@ void launch_d4c(const D4cParams &p, int max_frames, hipStream_t stream) {
     q.frame_lo = p.frame_lo + lo;
     q.frame_hi = imin(q.frame_lo + per_launch, p.frame_lo + range_frames);
     const dim3 grid(q.frame_hi - q.frame_lo, p.b.n_utt);
-    if (p.lg_d4c == 11) devrt::launch_blocks("d4c_frame", d4c_frame<2048, 128>, grid, 128, lds, stream, q);
-    else if (p.lg_d4c == 12) devrt::launch_blocks("d4c_frame", d4c_frame<4096, 256>, grid, 256, lds, stream, q);
-    else if (p.lg_d4c == 13) devrt::launch_blocks("d4c_frame", d4c_frame<8192, 512>, grid, 512, lds, stream, q);
-    else devrt::launch_blocks("d4c_frame", d4c_frame<16384, 1024>, grid, 1024, lds, stream, q);
+    auto frame = [&](auto rec) {
+      constexpr bool R = decltype(rec)::value;
+      if (p.lg_d4c == 11) devrt::launch_blocks("d4c_frame", d4c_frame<2048, 128, R>, grid, 128, lds, stream, q);
+      else if (p.lg_d4c == 12) devrt::launch_blocks("d4c_frame", d4c_frame<4096, 256, R>, grid, 256, lds, stream, q);
+      else if (p.lg_d4c == 13) devrt::launch_blocks("d4c_frame", d4c_frame<8192, 512, R>, grid, 512, lds, stream, q);
+      else devrt::launch_blocks("d4c_frame", d4c_frame<16384, 1024, R>, grid, 1024, lds, stream, q);
+    };
+    if (p.frame_consts) frame(std::true_type()); else frame(std::false_type());
   }
   WH_BLOCKS(d4c_finish, dim3(range_frames, p.b.n_utt), 256, 8 * sizeof(double), stream, p);
 }

@@ -5,6 +5,8 @@
 
 namespace world_hip {
 
+constexpr int kQuirkDoubles = 8;
+constexpr int kBandFftThreads = 256;   // threads of an hv_band_events_fft workgroup (launch_harvest)
 struct HarvestParams {
   BatchView b;
   // ---- options (HarvestOption, reference src/world/harvest.h:16-20) ----
@@ -40,7 +42,10 @@ struct HarvestParams {
   int nyq_slices;          // slices of 4096 samples per utterance slot
   double *mean_part;       // [n_utt][mean_parts] partial sums of the decimated signal: per span of the backward sweep (ratio 1: per slice)
   int mean_parts;
-  double *quirk;           // [n_utt][nch][4] per-band constants of the mirror-store term (bandfilter.h)
+  double *quirk;           // [n_utt][nch][kQuirkDoubles] per-band constants of the mirror-store term (bandfilter.h): [0..4) its
+                           // coefficients and angle per sample w, [4..8) sincospi(256 w), sincospi(fft_seg w) -- the phase steps of
+                           // hv_band_events_fft from sample to sample and block to block, uniform over a (band, utterance)
+  int inkernel_consts;     // 1: hv_band_events_fft evaluates those two pairs itself (WORLD_HIP_INKERNEL_CONSTS)
   const double *win_tab;   // [hw][6] = sin/cos(pi d), sin/cos(pi WAVE d), 2 / window length, pi d; d = 2/(2hw+1): refinement window steps
   const double *win_lane;  // [hw][WAVE][2] = (sin, cos)(pi (lane - hw - 1) d): a lane's first window sample at a whole-sample frame centre
   const double2 *win_full; // [hw^2 + i] = (main window, its central difference)[i] of half length hw centred on a sample; nullptr:

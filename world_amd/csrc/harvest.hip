@@ -115,8 +115,14 @@ __device__ __forceinline__ void band_quirk_constants(const HarvestParams &p, int
   const double w = part[3];
   double h0, h1r, h1i;
   nyquist_pair(p.band_taps + p.band_off[band], 2 * p.band_half[band] + 1, w, scratch, &h0, &h1r, &h1i);
-  if (threadIdx.x == 0)
-    mirror_store_constants(y0, y1r, y1i, h0, h1r, h1i, w, p.quirk + ((size_t)u * p.nch + band) * 4);
+  if (threadIdx.x == 0) {
+    double *q = p.quirk + ((size_t)u * p.nch + band) * kQuirkDoubles;
+    mirror_store_constants(y0, y1r, y1i, h0, h1r, h1i, w, q);
+    // hv_band_events_fft's phase steps (they depend on w, fft_seg and the workgroup size alone): once here, not in every
+    // thread of every (band, chunk) workgroup
+    sincospi(kBandFftThreads * w, &q[4], &q[5]);
+    sincospi(p.fft_seg * w, &q[6], &q[7]);
+  }
 }
 __global__ void hv_band_quirk(HarvestParams p) {
   DYN_LDS(lds);
@@ -139,7 +145,7 @@ __global__ void __launch_bounds__(kBpThreads) hv_band_events(HarvestParams p) {
   job.nseg = p.nseg;
   job.seg_events = p.seg_events + ((size_t)(ue * p.nch + band) * 4) * p.nseg * kSegCap;   // seg_cap == kSegCap on this path
   job.seg_count = p.seg_count + ((size_t)(ue * p.nch + band) * 4) * p.nseg;
-  job.quirk = p.quirk + ((size_t)u * p.nch + band) * 4;
+  job.quirk = p.quirk + ((size_t)u * p.nch + band) * kQuirkDoubles;
   job.quirk_delay = job.shift;                     // the term is a function of the undelayed index
   band_events_segment(job, seg);
 }
@@ -220,7 +226,10 @@ __global__ void __launch_bounds__(256) hv_block_spectra(HarvestParams p) {
 #ifndef HV_FFT_MIN_WAVES
 #define HV_FFT_MIN_WAVES 4      // 128 registers (two in scratch) and 35 KB of LDS: four workgroups per CU -- 3.79 -> 3.47 ms per 128 utterances against three
 #endif
-__global__ void __launch_bounds__(256, HV_FFT_MIN_WAVES) hv_band_events_fft(HarvestParams p) {
+// REC: the phase steps come with the band's other constants (band_quirk_constants); false: every thread evaluates them
+// (the route WORLD_HIP_INKERNEL_CONSTS selects)
+template <bool REC>
+__global__ void __launch_bounds__(kBandFftThreads, HV_FFT_MIN_WAVES) hv_band_events_fft(HarvestParams p) {
   DYN_LDS(lds);
   const int band = blockIdx.x, chunk = blockIdx.y, ue = blockIdx.z, u = ue + p.ev_u0, tid = threadIdx.x, nt = blockDim.x;
   const int n = p.y_len[u];
@@ -244,7 +253,7 @@ __global__ void __launch_bounds__(256, HV_FFT_MIN_WAVES) hv_band_events_fft(Harv
   const int at0 = p.fft_pre + shift;
   // the reference's mirror-store term (bandfilter.h), a function of the undelayed index t0 + k + shift:
   //   (-1)^n (qc cos(pi w n) + qs sin(pi w n) + q0),  n = t0 + (s - at0) + shift for block sample s.
-  const double *qc4 = p.quirk + ((size_t)u * p.nch + band) * 4;
+  const double *qc4 = p.quirk + ((size_t)u * p.nch + band) * kQuirkDoubles;
   const double qc = qc4[0], qs = qc4[1], q0 = qc4[2], w = qc4[3];
   double *ev = p.seg_events + (list * p.nseg + chunk) * p.seg_cap;
   const size_t fam_stride = (size_t)p.nseg * p.seg_cap;
@@ -268,8 +277,12 @@ __global__ void __launch_bounds__(256, HV_FFT_MIN_WAVES) hv_band_events_fft(Harv
   // cos / sin of the term's phase at the thread's first sample of the first block; from block to block and from sample
   // to sample they advance by rotation (a sincospi per block sat in the loop with the filter spectrum's 40 registers live)
   double sr, cr, sb, cb, sn0, cs0;
-  sincospi(nt * w, &sr, &cr);
-  sincospi(p.fft_seg * w, &sb, &cb);
+  if constexpr (!REC) {
+    sincospi(nt * w, &sr, &cr);
+    sincospi(p.fft_seg * w, &sb, &cb);
+  } else {
+    sr = qc4[4]; cr = qc4[5]; sb = qc4[6]; cb = qc4[7];   // band_quirk_constants: the same two calls, once per (band, utterance)
+  }
   sincospi((blk0 * p.fft_seg + tid + shift) * w, &sn0, &cs0);
   constexpr int NT = 256, kItems = (kBandFft / 4 + 1 + NT - 1) / NT;   // 256 threads: launch_harvest
   constexpr int hh = kBandFft / 2, qq = hh / 2;
@@ -1142,7 +1155,10 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
     HarvestParams g = p;
     g.ev_u0 = u0;
     const int G = imin(p.ev_group, B - u0);
-    if (p.fft_seg > 0) WH_BLOCKS(hv_band_events_fft, dim3(p.nch, p.nseg, G), 256, lds, stream, g);
+    if (p.fft_seg > 0 && p.inkernel_consts)
+      devrt::launch_blocks("hv_band_events_fft", hv_band_events_fft<false>, dim3(p.nch, p.nseg, G), kBandFftThreads, lds, stream, g);
+    else if (p.fft_seg > 0)
+      devrt::launch_blocks("hv_band_events_fft", hv_band_events_fft<true>, dim3(p.nch, p.nseg, G), kBandFftThreads, lds, stream, g);
     else WH_BLOCKS(hv_band_events, dim3(p.nseg, p.nch, G), kBpThreads, hv_band_lds_bytes(p.max_half), stream, g);
     // one chunk per utterance: the kernel above appended straight into the final lists (seg_events == events)
     if (!(p.fft_seg > 0 && p.nseg == 1)) WH_BLOCKS(hv_compact_events, dim3(p.nch * 4, G), 256, compact_lds_bytes(p.nseg), stream, g);
