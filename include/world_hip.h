@@ -445,6 +445,17 @@ WORLD_HIP_API int world_hip_probe_irfft(WorldHipContext *ctx, int lg_n, int max_
  *   18, 19  dft8<true> / dft8_head2<true> (the latter on the first two values) on `batch` rows of 8 complex values; lg_n = 3 */
 WORLD_HIP_API int world_hip_probe_fft(WorldHipContext *ctx, int mode, int lg_n, int max_lr, int threads, int swizzle,
                                       long long batch, const void *d_in, void *d_out);
+/* D4C's band selection in isolation (csrc/d4c.hip: the radix select that stands for the reference's std::sort in
+ * GetCoarseAperiodicity, src/d4c.cpp:194-225): `rows` workgroups of `threads` threads (128, 256, 512 or 1024: d4c_frame's), each
+ * over one row of d_keys [rows][threads][10] -- thread t's ten slots as d4c_frame hands them over: finite doubles with the
+ * sign bit clear; slots 0 .. 7 owned, slot 8 non-zero on thread 0 only, slot 9 zero (the probe loads what it is given).
+ *   mode 0  block_excluding_largest<threads>(key, K, ..) as the band loop calls it
+ *   mode 1  the general routine block_smallest_sum<threads>(key, 10, 10 threads, 10 threads - K, ..) directly
+ * d_out [rows][3]: the sum of all slots but the K largest, the sum of all slots (both formed as d4c_frame's tail forms them:
+ * the wavefronts' shares added in wavefront order), and the route taken -- 0 one pass, 1 two passes, 2 the general routine
+ * (always 2 in mode 1).  1 <= K <= 10 threads (K = 10 threads, no key left: the probe itself writes the 0).  A refusal names the argument and writes nothing. */
+WORLD_HIP_API int world_hip_probe_select(WorldHipContext *ctx, int mode, int threads, int K, long long rows,
+                                         const double *d_keys, double *d_out);
 
 /* Multi-GPU exchange (the reference has no counterpart).  Utterances are sharded over GPUs
  * and analysed independently; a GPU's results are then packed into ONE contiguous block of records

@@ -656,6 +656,25 @@ def run_fft_routes(wh):
     return out
 
 
+# ---- D4C's band selection in isolation (tests/test_d4c_select_cpu.py) ---------------------------------------------------------
+def run_d4c_select(wh):
+    """the designed rows of test_d4c_select_cpu.py -- every route, every entry of the general routine, the ties, the positions
+    of the threshold and the top key -- and its real-valued rows, at all four workgroup sizes, through block_excluding_largest
+    (mode 0) and through the general routine directly (mode 1).  The select places its barriers by hand and its histograms
+    alias a buffer the probe marks dead, as d4c_frame does: a missing barrier on a fallback route changes these bits"""
+    import torch
+    import test_d4c_select_cpu as cpu
+    out = []
+    for nt in cpu.NTS:
+        work = [(b.name, b.K, cpu.realise(b.P, cpu.SCALES["2^-80"])) for b in cpu.batches_routes(nt) + cpu.batches_general(nt) + cpu.batches_positions(nt)]
+        for name, K, keys in work + list(cpu.real_rows(nt)):
+            d_keys = _dev(keys)
+            for mode in (0, 1):
+                out.append((f"NT {nt} {name} mode {mode}", _np(wh.probe_select(d_keys, K, mode=mode))))
+    torch.cuda.synchronize()
+    return out
+
+
 # ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
 DROPIN_SECONDS = (0.5, 0.2, 0.31)
 
@@ -742,6 +761,7 @@ FAMILIES = {
                    + tuple(f"fft_route_d4c_rfft<1, {n}, {n // 16}, {k}>" for n in (2048, 4096, 8192, 16384) for k in (0, 1, 2))
                    + tuple(f"fft_route_d4c_twiddles<1, {n}, {n // 16}>" for n in (2048, 4096, 8192, 16384))
                    + tuple(f"fft_route_dft8<{s}, {h}>" for s in (0, 1) for h in ("false", "true")), {}),
+    "d4c-select": (run_d4c_select, tuple(f"d4c_select_probe<{nt}>" for nt in (128, 256, 512, 1024)), {}),
     "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
                                                             "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
                        + _SYNTHESIS, {}),
@@ -749,7 +769,7 @@ FAMILIES = {
 # Families whose calls carve nothing from the arena and keep no buffer of their own between calls (cached tables apart): a
 # second pass in the same context has nothing to refill, so the hbm build's counter need only rise in the first (the tables'
 # allocation).  Every other family must see it rise in both passes.
-NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing", "fft-routes")
+NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing", "fft-routes", "d4c-select")
 # profile labels that are not the kernel's own name (devrt::launch_blocks("label", kernel<...>, ...))
 LABELS = {"ct_frame_coded": "ct_frame"}
 # kernels that run only while a process-wide table is built: asserted on the first pass of the jitter library, which nothing

@@ -307,6 +307,8 @@ def load_library(path=LIB_PATH):
     lib.world_hip_probe_irfft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
     if hasattr(lib, "world_hip_probe_fft"):                          # (added under ABI 6: looked up by name)
         lib.world_hip_probe_fft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
+    if hasattr(lib, "world_hip_probe_select"):                       # (added under ABI 6: looked up by name)
+        lib.world_hip_probe_select.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
     lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                              C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
     lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
@@ -1454,6 +1456,16 @@ class WorldHip:
         out = t.empty(shape, dtype=t.float64, device=x.device)
         self._check(self.lib.world_hip_probe_fft(self._context(), mode, lg, max_lr, threads, swizzle, batch, x.data_ptr(),
                                                  out.data_ptr()), "probe_fft")
+        return out
+
+    def probe_select(self, keys, K, mode=0):
+        """D4C's band selection alone (include/world_hip.h: world_hip_probe_select): keys [rows, threads, 10] float64 ->
+        [rows, 3] = the sum of all slots but the K largest, the sum of all, the route (0 one pass, 1 two, 2 general)"""
+        t = self.torch
+        assert keys.dtype == t.float64 and keys.is_contiguous() and keys.dim() == 3 and keys.shape[2] == 10
+        out = t.empty((keys.shape[0], 3), dtype=t.float64, device=keys.device)
+        self._check(self.lib.world_hip_probe_select(self._context(), mode, keys.shape[1], K, keys.shape[0], keys.data_ptr(),
+                                                    out.data_ptr()), "probe_select")
         return out
 
     # ---- multi-GPU exchange records (include/world_hip.h: world_hip_pack_results) ----

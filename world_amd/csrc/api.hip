@@ -29,6 +29,7 @@
 #include "dio.h"
 #include "exchange.h"
 #include "fft_probe.h"
+#include "d4c_select_probe.h"
 #include "gmm_host.h"
 #include "machine_probe.h"
 #include "mcep_host.h"
@@ -2987,6 +2988,20 @@ int world_hip_probe_fft(WorldHipContext *c, int mode, int lg_n, int max_lr, int 
            "2^6 .. 2^14, max_lr 3; 4, 5 at 2^6 .. 2^13, max_lr 4; 6 at 2^6 .. 2^13, max_lr 3; 7, 8, 9 at 2^10 .. 2^12, max_lr 3; 10 .. 13 "
            "at 2^12, max_lr 3, 256 threads; 14 .. 17 at 2^11 .. 2^14, max_lr 3, N / 16 threads; 18, 19 at lg_n 3 (rows of 8).  Swizzle 0 has modes "
            "1 .. 12, 18 and 19; swizzle 1 modes 1 (max_lr 3), 7 (2^11) and 13 .. 19.  Modes 7 .. 17 do not exist in the one-lane host emulation", mode, lg_n, max_lr, threads, swizzle);
+  });
+}
+
+// d4c_frame's band selection in isolation (d4c.hip: d4c_select_probe), one workgroup per row of keys
+int world_hip_probe_select(WorldHipContext *c, int mode, int threads, int K, long long rows, const double *d_keys, double *d_out) {
+  return guarded(c, [&] {
+    if (mode != 0 && mode != 1) fail("probe_select: mode %d unsupported (0: block_excluding_largest, 1: block_smallest_sum)", mode);
+    if (threads != 128 && threads != 256 && threads != 512 && threads != 1024)
+      fail("probe_select: threads = %d is not one of d4c_frame's workgroup sizes (128, 256, 512, 1024)", threads);
+    if (K < 1 || K > 10 * threads) fail("probe_select: K = %d outside 1 .. %d (the keys of a row)", K, 10 * threads);
+    if (rows < 0 || rows > 0x7FFFFFFFll) fail("probe_select: bad rows");
+    if (!d_keys || !d_out) fail("probe_select: null buffer (%s)", !d_keys ? "keys" : "out");
+    if (rows == 0) return;
+    if (!launch_d4c_select_probe(mode, threads, K, (long)rows, d_keys, d_out, c->stream)) fail("probe_select: threads = %d has no kernel", threads);
   });
 }
 

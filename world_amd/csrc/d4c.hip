@@ -41,6 +41,7 @@
 #include "stage_params.h"
 #include "prepare.h"
 #include "trace.h"
+#include "d4c_select_probe.h"
 WH_TRACE_DEFINE(d4c)
 WH_BARTRACE_DEFINE(d4c)
 
@@ -73,7 +74,8 @@ __global__ void spectral_prepare(CtParams cp, D4cParams dp) {
 // single key -- typically after two passes.  Barriers: two for min/max, ONE per pass (the
 // first kSelHists histograms are zeroed up front), two for the final sums.
 constexpr int kSelHists = 3;
-// key[q], q < mine: bit patterns of this thread's elements (n elements block-wide).
+// key[q], q < mine: bit patterns of this thread's elements (n elements block-wide).  1 <= m <= n: the threshold is the m-th
+// smallest key (m = 0 has none: *partial is then meaningless, *total still the sum; d4c_select_probe answers that edge itself).
 // hist: kSelHists x 256 ints of LDS.
 template <int NT = 0, int kSelKeys>
 __device__ __forceinline__ void block_smallest_sum(const unsigned long long (&key)[kSelKeys], int mine, int n, int m,
@@ -269,13 +271,15 @@ __device__ __forceinline__ void sel_zero_bins(int *hist, int tid, int nt) {
 
 // key[0 .. kKeys-2): owned by every thread; key[kKeys-2]: thread 0 only (the merge's unpaired bin), 0 elsewhere;
 // key[kKeys-1]: 0.  hist: 1344 ints of LDS.  K: how many of the largest keys are EXCLUDED from *partial.
+// route (optional): how the band was decided -- 0 one pass, 1 two passes, 2 the general routine (the WH_TRACE counters' split).
 // Returns true when *partial / *total are the BLOCK's sums (the general routine ran), false when they are the calling
 // wavefront's share of them: the caller adds the wavefronts' shares up whenever it next crosses a barrier anyway (the
 // block sum here -- LDS, barrier, LDS -- was a quarter of the routine's time in a CU whose LDS pipe is busy with other
 // workgroups' transforms: every dependent trip through it costs ~750 cycles there).
 template <int NT, int kKeys>
 __device__ __forceinline__ bool block_excluding_largest(const unsigned long long (&key)[kKeys], int K, int *hist, double *scratch,
-                                                        double *partial, double *total, bool trace_me = false, int threads = NT) {
+                                                        double *partial, double *total, bool trace_me = false, int threads = NT,
+                                                        int *route = nullptr) {
   (void)trace_me;
   constexpr int kFull = kKeys - 2;
   static_assert(NT % WAVE == 0 && NT / WAVE <= 16, "whole wavefronts");
@@ -342,6 +346,7 @@ __device__ __forceinline__ bool block_excluding_largest(const unsigned long long
   // development aid: how the bands of a launch were decided (tools/trace.py): [100] one pass, [101] two, [102] general routine
   if (tid == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&wh_trace[!fast ? 102 : (t_low_two ? 101 : 100)]), 1ull);
 #endif
+  if (route) *route = !fast ? 2 : (t_low_two ? 1 : 0);                    // (d4c_select_probe alone asks: null in d4c_frame)
   if (!fast) {
     __syncthreads();                                                      // nobody is still reading the bins
     // the general routine: every slot counts as a key (the zeros are the smallest and add nothing)
@@ -1172,6 +1177,64 @@ __global__ void d4c_finish(D4cParams p) {
     const double v = ap_value(i);
     if (p.out_f32) row32[i] = static_cast<float>(v); else row[i] = v;
   }
+}
+
+// ---------------------------------------------------------------------------
+// The band selection alone (world_hip_probe_select; tests/test_d4c_select_cpu.py, _gpu.py): one workgroup of NT threads per
+// row of [NT][10] keys, loaded as d4c_frame hands them over, in d4c_frame's LDS layout -- the histograms at the head of a
+// transform buffer of 16 NT doubles that is dead by then, the 64 doubles of scratch behind it -- and the block's two sums
+// formed as d4c_frame's tail forms them: each wavefront's share parked, then added in wavefront order from zero.
+// mode 0: block_excluding_largest as the band loop calls it; 1: the general routine as block_excluding_largest calls it.
+// out [rows][3]: partial, total, route (0 one pass, 1 two passes, 2 the general routine).  Replaces nothing in the reference.
+template <int NT>
+__global__ void __launch_bounds__(NT) d4c_select_probe(const double *keys, double *out, int K, int mode) {
+  constexpr int kKeys = 10, N = 16 * NT, kWaves = NT / WAVE;
+  static_assert(D4cShape<N, NT>::kBins == kKeys, "d4c_frame's keys per thread");
+  DYN_LDS(lds);
+  double *Zr = reinterpret_cast<double *>(lds);
+  double *scratch = Zr + N;
+  double *band_sums = scratch + 64;                                    // [partial, total][wavefront]
+  int *hist = reinterpret_cast<int *>(Zr);
+  const int tid = wg_thread<NT>();
+  const double *mine = keys + ((size_t)blockIdx.x * NT + tid) * kKeys;
+  unsigned long long key[kKeys];
+#pragma unroll
+  for (int e = 0; e < kKeys; ++e) key[e] = (unsigned long long)__double_as_longlong(mine[e]);
+  lds_dead(Zr, N);                                                     // (as in front of the band loop's call)
+  double part, tot;
+  int route = 2;
+  bool whole = true;
+  if (mode == 0) whole = block_excluding_largest<NT>(key, K, hist, scratch, &part, &tot, false, NT, &route);
+  else block_smallest_sum<NT>(key, kKeys, NT * kKeys, NT * kKeys - K, hist, scratch, &part, &tot, false);
+  // K = every slot: the select's threshold is the m-th smallest key and needs m >= 1 (d4c_frame excludes 257 keys of 8193 at
+  // the most); the sum of no key at all is the caller's to write
+  if (K == NT * kKeys) part = 0.0;
+  if (lane_id() == 0) {
+    const int wv = wave_in_block();
+    band_sums[wv] = whole && wv > 0 ? 0.0 : part;
+    band_sums[kWaves + wv] = whole && wv > 0 ? 0.0 : tot;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    const double *w = band_sums + tid * kWaves;
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) t += w[k];                         // wavefront order, from zero
+    out[(size_t)blockIdx.x * 3 + tid] = t;
+  }
+  if (tid == 2) out[(size_t)blockIdx.x * 3 + 2] = (double)route;
+}
+static size_t d4c_select_probe_lds_bytes(int threads) { return sizeof(double) * ((size_t)16 * threads + 64 + 2 * (threads / WAVE)); }
+// false: not one of d4c_frame's four workgroup sizes
+bool launch_d4c_select_probe(int mode, int threads, int K, long rows, const double *d_keys, double *d_out, hipStream_t stream) {
+  const dim3 grid((unsigned)rows);
+  const size_t lds = d4c_select_probe_lds_bytes(threads);
+  if (threads == 128) WH_BLOCKS(d4c_select_probe<128>, grid, 128, lds, stream, d_keys, d_out, K, mode);
+  else if (threads == 256) WH_BLOCKS(d4c_select_probe<256>, grid, 256, lds, stream, d_keys, d_out, K, mode);
+  else if (threads == 512) WH_BLOCKS(d4c_select_probe<512>, grid, 512, lds, stream, d_keys, d_out, K, mode);
+  else if (threads == 1024) WH_BLOCKS(d4c_select_probe<1024>, grid, 1024, lds, stream, d_keys, d_out, K, mode);
+  else return false;
+  return true;
 }
 
 // ---------------------------------------------------------------------------
