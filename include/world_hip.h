@@ -456,6 +456,34 @@ WORLD_HIP_API int world_hip_probe_fft(WorldHipContext *ctx, int mode, int lg_n, 
  * (always 2 in mode 1).  1 <= K <= 10 threads (K = 10 threads, no key left: the probe itself writes the 0).  A refusal names the argument and writes nothing. */
 WORLD_HIP_API int world_hip_probe_select(WorldHipContext *ctx, int mode, int threads, int K, long long rows,
                                          const double *d_keys, double *d_out);
+/* Harvest's back half in isolation (csrc/harvest.hip: hv_prune -- RemoveUnreliableCandidates and SearchF0Base, src/harvest.cpp:
+ * 652-705 -- then csrc/harvest_contour.hip: FixStep1 .. 4, SmoothF0Contour and the hop subsampling, :710-1113, :1246-1251) on
+ * refined candidates the caller made up, where Harvest proper takes them from hv_refine: the same kernels, launch shapes
+ * (the one-utterance shapes and WORLD_HIP_HINT_SHARED_DEVICE included), HarvestParams fields and workspace carve as a Harvest
+ * call of n_utt utterances whose longest has max nfb 1 ms frames.
+ *   nfb, nc (host, [n_utt])  1 ms frames per utterance (>= 1) and candidates per frame: utterance u uses slots 0 .. 7 nc[u] - 1
+ *   maxc                     slots per frame, a multiple of 7 in 7 .. 252 (Harvest's own is 105 at the default F0 range)
+ *   fb_stride, sec_cap       the batch's row lengths, given so that both sides state them: (max nfb + 7) & ~7 and max nfb / 2 + 4
+ *   d_cand, d_score          [n_utt][fb_stride][maxc] refined candidates (0 = none) and their scores
+ * Out, rows 0 .. nfb[u] - 1 of utterance u only (what lies past them is not touched):
+ *   d_pruned_cand, d_pruned_score [n_utt][fb_stride][maxc]  after RemoveUnreliableCandidates; slots 7 nc[u] .. maxc - 1 hold
+ *                            workspace bytes, and nothing is written for an utterance with nc[u] = 0
+ *   d_step2, d_step3, d_step4, d_basic_f0 [n_utt][fb_stride]  the contour after FixStep2, FixStep3, FixStep4 and the smoother
+ *   d_sec_n [n_utt][2], d_sec [n_utt][6][sec_cap]  the section table as the last launch leaves it: sec_n[0] voiced sections of
+ *                            the step-4 contour, their first and last frames in rows 0 and 1 (rows 2 .. 5 and sec_n[1] are
+ *                            scratch of the passes before)
+ *   d_tpos, d_f0 [n_utt][f_stride]  frames at frame_period ms: (int)((nfb[u] - 1) / frame_period) + 1 of them
+ * Overwritten before the last launch ends and therefore not reported: the base pick (SearchF0Base's contour: FixStep4 writes
+ * its own over it -- it shows through step 2 wherever FixStep1 and 2 pass a frame), the number of sections ExtendSub kept
+ * (sec_n[1], cleared by the section pass of step 4), the sections of steps 2 and 3 and their extended slices (the smoother's
+ * scratch).  Extend's nearest candidate: two candidates whose distances from the previous pick are equal after clearing the
+ * low 8 mantissa bits count as equally near, and the later slot wins (the reference: the nearer, the later of exact equals).
+ * A refusal names the argument and writes nothing. */
+WORLD_HIP_API int world_hip_probe_harvest_contour(WorldHipContext *ctx, int n_utt, const int *nfb, const int *nc, int maxc,
+                                                  int fb_stride, const double *d_cand, const double *d_score, double frame_period,
+                                                  int f_stride, double *d_pruned_cand, double *d_pruned_score, double *d_step2,
+                                                  double *d_step3, double *d_step4, int sec_cap, int *d_sec_n, int *d_sec,
+                                                  double *d_basic_f0, double *d_tpos, double *d_f0);
 
 /* Multi-GPU exchange (the reference has no counterpart).  Utterances are sharded over GPUs
  * and analysed independently; a GPU's results are then packed into ONE contiguous block of records

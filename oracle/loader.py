@@ -6,6 +6,8 @@ Two interchangeable back ends with one Python surface:
 * ``WideOracle``  -- oracle/libworld_oracle_wide.so, the same source with its value
   arithmetic in long double (-DWO_WIDE): the more precise answer the accuracy
   tests measure both the GPU and the reference against.
+* ``RefContour``  -- oracle/_ref/libworld_ref_contour.so, the reference's contour stage of Harvest
+  on made-up candidates (oracle/harvest_contour_ref.cpp).
 * ``RefOracle``   -- oracle/_ref/libworld_ref*.so, the UNMODIFIED reference
   compiled in place from /root/reference by oracle/Makefile (present whenever
   it was built in the container; the .so travels to the GPU box).
@@ -51,6 +53,12 @@ class _Base:
         return int(2.0 ** (1.0 + int(math.log(3.0 * fs / f0_floor + 1) / 0.69314718055994529)))
 
 
+# world_oracle.h: WO_HC_*, in order
+HC_COUNTERS = ("sections", "rejected", "kept", "compacted", "merge_disjoint", "merge_contained", "merge_s1_gt", "merge_s1_eq",
+               "merge_s1_lt", "merge_out_of_order", "bridged", "extend_stopped", "extend_full_reach", "extend_tie",
+               "extend_at_range", "extend_hit_after_3")
+
+
 class PortOracle(_Base):
     kind = "port"
 
@@ -63,6 +71,9 @@ class PortOracle(_Base):
         L.wo_frame_count.restype = C.c_int
         L.wo_frame_count.argtypes = [C.c_int, C.c_int, C.c_double]
         L.wo_harvest.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp]
+        if hasattr(L, "wo_harvest_contour"):
+            L.wo_harvest_contour.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_double] + [_dp] * 8 + [C.POINTER(C.c_int)]
+            L.wo_harvest_smooth.argtypes = [_dp, C.c_int, _dp]
         L.wo_dio.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                              C.c_int, C.c_double, _dp, _dp]
         L.wo_stonemask.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]
@@ -133,6 +144,28 @@ class PortOracle(_Base):
         tp = np.zeros(nf); f0 = np.zeros(nf)
         self.lib.wo_harvest(_p(x), len(x), fs, f0_floor, f0_ceil, frame_period, _p(tp), _p(f0))
         return tp, f0
+
+    def harvest_contour(self, cand, score, frame_period=5.0):
+        """Harvest from the refined candidates on: cand, score [nf, nslot] at 1 ms -> a dict of pruned_cand, pruned_score
+        [nf, nslot], step2, step3, step4, smooth [nf], tpos, f0 at frame_period and counters, {name: times the branch was
+        taken} (HC_COUNTERS: world_oracle.h's WO_HC_*)"""
+        cand, score = _f64(cand), _f64(score)
+        nf, nslot = cand.shape
+        assert score.shape == cand.shape and nf >= 1
+        n = int((nf - 1) / frame_period) + 1
+        o = dict(pruned_cand=np.zeros((nf, nslot)), pruned_score=np.zeros((nf, nslot)), step2=np.zeros(nf), step3=np.zeros(nf),
+                 step4=np.zeros(nf), smooth=np.zeros(nf), tpos=np.zeros(n), f0=np.zeros(n))
+        count = (C.c_int * len(HC_COUNTERS))()
+        got = self.lib.wo_harvest_contour(_p(cand), _p(score), nf, nslot, frame_period, *(_p(o[k]) for k in (
+            "pruned_cand", "pruned_score", "step2", "step3", "step4", "smooth", "tpos", "f0")), count)
+        assert got == n
+        o["counters"] = dict(zip(HC_COUNTERS, count))
+        return o
+
+    def smooth_f0(self, f0):
+        f0 = _f64(f0); out = np.zeros(len(f0))
+        self.lib.wo_harvest_smooth(_p(f0), len(f0), _p(out))
+        return out
 
     def dio(self, x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_period=5.0,
             speed=1, allowed_range=0.1):
@@ -235,6 +268,45 @@ class RefOracle(WorldCABI):
             raise FileNotFoundError(path)
         self.flags = "-O3 -march=x86-64-v3" if name.endswith("_o3.so") else "-O1 (reference makefile:6)"
         super().__init__(path, hip_runtime=False)
+
+
+class RefContour:
+    """oracle/_ref/libworld_ref_contour.so: the reference's own RemoveUnreliableCandidates, FixStep1 .. 4, FixF0Contour and
+    SmoothF0Contour on made-up candidates (oracle/harvest_contour_ref.cpp includes the reference's harvest.cpp in place)"""
+    kind = "reference"
+    path = os.path.join(HERE, "_ref", "libworld_ref_contour.so")
+
+    @classmethod
+    def available(cls):
+        return os.path.exists(cls.path)
+
+    def __init__(self):
+        if not self.available():
+            raise FileNotFoundError(self.path)
+        self.lib = C.CDLL(self.path)
+        self.lib.ref_harvest_contour.argtypes = [_dp, _dp, C.c_int, C.c_int] + [_dp] * 7
+        self.lib.ref_harvest_contour.restype = None
+        self.lib.ref_smooth_f0.argtypes = [_dp, C.c_int, _dp]
+        self.lib.ref_smooth_f0.restype = None
+
+    def harvest_contour(self, cand, score):
+        """as PortOracle.harvest_contour, without the frames at frame_period (Harvest() subsamples inline), and with
+        FixF0Contour called whole held to its stages called one by one"""
+        cand, score = _f64(cand), _f64(score)
+        nf, nslot = cand.shape
+        assert score.shape == cand.shape and nf >= 1
+        o = dict(pruned_cand=np.zeros((nf, nslot)), pruned_score=np.zeros((nf, nslot)), step2=np.zeros(nf), step3=np.zeros(nf),
+                 step4=np.zeros(nf), whole=np.zeros(nf), smooth=np.zeros(nf))
+        self.lib.ref_harvest_contour(_p(cand), _p(score), nf, nslot, *(_p(o[k]) for k in (
+            "pruned_cand", "pruned_score", "step2", "step3", "step4", "whole", "smooth")))
+        assert o["whole"].tobytes() == o["step4"].tobytes(), "FixF0Contour is not its stages in a row"
+        del o["whole"]
+        return o
+
+    def smooth_f0(self, f0):
+        f0 = _f64(f0); out = np.zeros(len(f0))
+        self.lib.ref_smooth_f0(_p(f0), len(f0), _p(out))
+        return out
 
 
 def ref_available():

@@ -638,6 +638,11 @@ static int voiced_runs(const double *f0, int nf, int *bl) {
   return nb;
 }
 
+/* Branch counters of the contour stage (world_oracle.h: WO_HC_*), filled only while wo_harvest_contour runs with a
+ * counter array: a test asserts with them that a made-up map reaches the branch it was made for. */
+static int *hc_count = NULL;
+#define HC_COUNT(i) do { if (hc_count) hc_count[i]++; } while (0)
+
 /* harvest.cpp:791-820 */
 static int extend_run(int origin, int last, int shift, double **cands, int nc,
                       double allowed, double *ext) {
@@ -648,8 +653,16 @@ static int extend_run(int origin, int last, int shift, double **cands, int nc,
     int t = origin + shift * i + shift;
     double e;
     ext[t] = nearest_candidate(cur, cands[t], nc, allowed, &e);
+    if (hc_count && ext[t] != 0.0) {                 /* another value exactly as near: the last slot decided */
+      int tie = 0;
+      for (int j = 0; j < nc; ++j) tie |= cands[t][j] != ext[t] && cands[t][j] != 0.0 && fabs(cur - cands[t][j]) / cur == e;
+      if (tie) HC_COUNT(WO_HC_EXTEND_TIE);
+      if (e == allowed) HC_COUNT(WO_HC_EXTEND_AT_RANGE);
+    }
+    if (hc_count && miss == 3 && ext[t] != 0.0) HC_COUNT(WO_HC_EXTEND_HIT_AFTER_3);
     if (ext[t] == 0.0) { miss++; } else { cur = ext[t]; miss = 0; moved = t; }
-    if (miss == 4) break;
+    if (miss == 4) { HC_COUNT(WO_HC_EXTEND_STOPPED); break; }
+    if (i == dist) HC_COUNT(WO_HC_EXTEND_FULL_REACH);
   }
   return moved;
 }
@@ -668,6 +681,7 @@ static void harvest_step3(const double *in, int nf, int nc, double **cands, doub
   int *bl = ialloc(nf);
   int nb = voiced_runs(in, nf, bl);
   int ns = nb / 2;
+  if (hc_count) hc_count[WO_HC_SECTIONS] += ns;
   double **ch = (double **)malloc(sizeof(double *) * (ns ? ns : 1));
   for (int s = 0; s < ns; ++s) {
     ch[s] = dalloc(nf);
@@ -692,9 +706,13 @@ static void harvest_step3(const double *in, int nf, int nc, double **cands, doub
       double *tp = ch[kept]; ch[kept] = ch[s]; ch[s] = tp;
       int t = bl[2 * kept]; bl[2 * kept] = bl[2 * s]; bl[2 * s] = t;
       t = bl[2 * kept + 1]; bl[2 * kept + 1] = bl[2 * s + 1]; bl[2 * s + 1] = t;
+      if (kept != s) HC_COUNT(WO_HC_COMPACTED);
       kept++;
+    } else {
+      HC_COUNT(WO_HC_REJECTED);
     }
   }
+  if (hc_count) hc_count[WO_HC_KEPT] += kept;
   if (kept != 0) {
     /* MergeF0() (937-963), including its in-place use of bl[0], bl[1] */
     int *order = ialloc(kept);
@@ -710,19 +728,22 @@ static void harvest_step3(const double *in, int nf, int nc, double **cands, doub
     for (int i = 0; i < nf; ++i) out[i] = ch[0][i];
     for (int i = 1; i < kept; ++i) {
       int o = order[i];
+      if (o == 0) HC_COUNT(WO_HC_MERGE_OUT_OF_ORDER);
       if (bl[o * 2] - bl[1] > 0) {
+        HC_COUNT(WO_HC_MERGE_DISJOINT);
         for (int j = bl[o * 2]; j <= bl[o * 2 + 1]; ++j) out[j] = ch[o][j];
         bl[0] = bl[o * 2];
         bl[1] = bl[o * 2 + 1];
       } else {
         int st1 = bl[0], ed1 = bl[1], st2 = bl[o * 2], ed2 = bl[o * 2 + 1];
         const double *f2 = ch[o];
-        if (st1 <= st2 && ed1 >= ed2) { bl[1] = ed1; continue; }
+        if (st1 <= st2 && ed1 >= ed2) { HC_COUNT(WO_HC_MERGE_CONTAINED); bl[1] = ed1; continue; }
         double s1 = 0.0, s2 = 0.0;
         for (int k = st2; k <= ed1; ++k) {
           s1 += best_score_of(out[k], cands[k], scores[k], nc);
           s2 += best_score_of(f2[k], cands[k], scores[k], nc);
         }
+        HC_COUNT(s1 > s2 ? WO_HC_MERGE_S1_GT : s1 == s2 ? WO_HC_MERGE_S1_EQ : WO_HC_MERGE_S1_LT);
         if (s1 > s2) for (int k = ed1; k <= ed2; ++k) out[k] = f2[k];
         else for (int k = st2; k <= ed2; ++k) out[k] = f2[k];
         bl[1] = ed2;
@@ -735,7 +756,9 @@ static void harvest_step3(const double *in, int nf, int nc, double **cands, doub
 }
 
 /* harvest.cpp:693-1044 */
-static void harvest_fix_contour(double **cands, double **scores, int nf, int nc, double *best) {
+/* step2, step3: when not NULL, the contour after FixStep2 and after FixStep3 (wo_harvest_contour) */
+static void harvest_fix_contour(double **cands, double **scores, int nf, int nc, double *best,
+                                double *step2, double *step3) {
   double *a = dalloc(nf), *b = dalloc(nf);
   int *bl = ialloc(nf);
   /* SearchF0Base: first maximum wins */
@@ -759,13 +782,16 @@ static void harvest_fix_contour(double **cands, double **scores, int nf, int nc,
     for (int j = bl[2 * s]; j <= bl[2 * s + 1]; ++j) a[j] = 0.0;
   }
   /* step 3 */
+  if (step2) memcpy(step2, a, sizeof(double) * nf);
   harvest_step3(a, nf, nc, cands, scores, 0.18, b);
+  if (step3) memcpy(step3, b, sizeof(double) * nf);
   /* step 4 (1000-1022) */
   memcpy(best, b, sizeof(double) * nf);
   nb = voiced_runs(b, nf, bl);
   for (int s = 0; s < nb / 2 - 1; ++s) {
     int dist = bl[(s + 1) * 2] - bl[s * 2 + 1] - 1;
     if (dist >= 9) continue;
+    HC_COUNT(WO_HC_BRIDGED);
     double t0 = b[bl[s * 2 + 1]] + 1;
     double t1 = b[bl[(s + 1) * 2]] - 1;
     double coef = (t1 - t0) / (dist + 1.0);
@@ -781,26 +807,27 @@ static void harvest_smooth(const double *f0, int nf, double *out) {
   const double a[2] = {1.7347257688092754, -0.76600660094326412};
   const int lag = 300;
   int m = nf + 2 * lag;
-  double *c = dalloc(m), *chan = dalloc(m), *tmp = dalloc(m), *res = dalloc(m);
+  double *c = dalloc(m), *chan = dalloc(m);
+  wo_real *tmp = (wo_real *)calloc(m, sizeof(wo_real)), *res = (wo_real *)calloc(m, sizeof(wo_real));
   int *bl = ialloc(m);
   for (int i = 0; i < nf; ++i) c[lag + i] = f0[i];
   int nb = voiced_runs(c, m, bl);
   for (int s = 0; s < nb / 2; ++s) {
     int st = bl[2 * s], ed = bl[2 * s + 1];
     for (int i = 0; i < m; ++i) chan[i] = (i < st) ? c[st] : (i > ed ? c[ed] : c[i]);
-    double w0 = 0.0, w1 = 0.0;
+    wo_real w0 = 0.0, w1 = 0.0;
     for (int i = 0; i < m; ++i) {
-      double wt = chan[i] + a[0] * w0 + a[1] * w1;
+      wo_real wt = chan[i] + a[0] * w0 + a[1] * w1;
       tmp[m - i - 1] = b[0] * wt + b[1] * w0 + b[0] * w1;
       w1 = w0; w0 = wt;
     }
     w0 = w1 = 0.0;
     for (int i = 0; i < m; ++i) {
-      double wt = tmp[i] + a[0] * w0 + a[1] * w1;
+      wo_real wt = tmp[i] + a[0] * w0 + a[1] * w1;
       res[m - i - 1] = b[0] * wt + b[1] * w0 + b[0] * w1;
       w1 = w0; w0 = wt;
     }
-    for (int j = st; j <= ed; ++j) out[j - lag] = res[j];
+    for (int j = st; j <= ed; ++j) out[j - lag] = (double)res[j];
   }
   free(c); free(chan); free(tmp); free(res); free(bl);
 }
@@ -850,7 +877,7 @@ static void harvest_body(const double *x, int n, int fs, int frame_period, doubl
   if (dump) { char fn[512]; snprintf(fn, sizeof fn, "%s_prune.bin", dump); FILE *f = fopen(fn, "wb");
     for (int i = 0; i < nf; ++i) fwrite(cands[i], sizeof(double), maxc, f); fclose(f); }
   double *best = dalloc(nf);
-  harvest_fix_contour(cands, scores, nf, nc, best);
+  harvest_fix_contour(cands, scores, nf, nc, best, NULL, NULL);
   if (dump) { char fn[512]; snprintf(fn, sizeof fn, "%s_best.bin", dump); FILE *f = fopen(fn, "wb");
     fwrite(best, sizeof(double), nf, f); fclose(f); }
   harvest_smooth(best, nf, f0);
@@ -878,6 +905,47 @@ void wo_harvest(const double *x, int x_length, int fs, double f0_floor, double f
     f0[i] = bf0[imin(bn - 1, wo_round(tpos[i] * 1000.0))];
   }
   free(bf0); free(bt);
+}
+
+/* Harvest's back half alone, on candidates the caller made up (tests/harvest_contour_cases.py): cand, score [nf][nslot]
+ * refined candidates at 1 ms.  Out: pruned_cand, pruned_score [nf][nslot] (RemoveUnreliableCandidates), step2, step3,
+ * step4 [nf] (FixF0Contour's stages), smooth [nf] (SmoothF0Contour; its value arithmetic in wo_real), tpos, f0
+ * [(int)((nf - 1) / frame_period) + 1] (Harvest()'s hop subsampling of a signal that ends on frame nf - 1); counters, when
+ * not NULL, [WO_HC_COUNTERS]: how often each branch of step 3 and 4 was taken.  Returns the length of tpos and f0. */
+int wo_harvest_contour(const double *cand, const double *score, int nf, int nslot, double frame_period,
+                       double *pruned_cand, double *pruned_score, double *step2, double *step3, double *step4,
+                       double *smooth, double *tpos, double *f0, int *counters) {
+  hc_count = counters;
+  if (counters) memset(counters, 0, sizeof(int) * WO_HC_COUNTERS);
+  double **cands = (double **)malloc(sizeof(double *) * nf), **scores = (double **)malloc(sizeof(double *) * nf);
+  for (int i = 0; i < nf; ++i) {
+    cands[i] = dalloc(nslot ? nslot : 1); scores[i] = dalloc(nslot ? nslot : 1);
+    memcpy(cands[i], cand + (size_t)i * nslot, sizeof(double) * nslot);
+    memcpy(scores[i], score + (size_t)i * nslot, sizeof(double) * nslot);
+  }
+  harvest_prune(nf, nslot, cands, scores);
+  for (int i = 0; i < nf; ++i) {
+    memcpy(pruned_cand + (size_t)i * nslot, cands[i], sizeof(double) * nslot);
+    memcpy(pruned_score + (size_t)i * nslot, scores[i], sizeof(double) * nslot);
+  }
+  harvest_fix_contour(cands, scores, nf, nslot, step4, step2, step3);
+  for (int i = 0; i < nf; ++i) smooth[i] = 0.0;
+  harvest_smooth(step4, nf, smooth);
+  int n = (int)((nf - 1) / frame_period) + 1;
+  for (int i = 0; i < n; ++i) {
+    tpos[i] = i * frame_period / 1000.0;
+    f0[i] = frame_period == 1.0 ? smooth[i] : smooth[imin(nf - 1, wo_round(tpos[i] * 1000.0))];
+  }
+  for (int i = 0; i < nf; ++i) { free(cands[i]); free(scores[i]); }
+  free(cands); free(scores);
+  hc_count = NULL;
+  return n;
+}
+
+/* SmoothF0Contour alone (harvest.cpp:1079-1113): frames outside the voiced sections of f0 are 0 */
+void wo_harvest_smooth(const double *f0, int nf, double *out) {
+  for (int i = 0; i < nf; ++i) out[i] = 0.0;
+  harvest_smooth(f0, nf, out);
 }
 
 /* ------------------------------------------------------------------ */

@@ -46,6 +46,24 @@ void   wo_linear_smoothing(const double *in, double width, int fs,
 int  wo_frame_count(int fs, int x_length, double frame_period);       /* harvest.cpp:1219, dio.cpp:639 */
 void wo_harvest(const double *x, int x_length, int fs, double f0_floor,
                 double f0_ceil, double frame_period, double *tpos, double *f0);
+/* Harvest from the refined candidates on (harvest.cpp:652-1113, 1246-1251): cand, score [nf][nslot] at 1 ms -> the pruned
+ * candidates and scores, the contour after FixStep2, 3, 4 and the smoother [nf], and the frames at frame_period (returns
+ * their number, (int)((nf - 1) / frame_period) + 1) */
+int  wo_harvest_contour(const double *cand, const double *score, int nf, int nslot, double frame_period,
+                        double *pruned_cand, double *pruned_score, double *step2, double *step3, double *step4,
+                        double *smooth, double *tpos, double *f0, int *counters);
+void wo_harvest_smooth(const double *f0, int nf, double *out);         /* harvest.cpp:1079-1113 (value arithmetic in wo_real) */
+/* wo_harvest_contour's counters (NULL: none): branches of FixStep3 and FixStep4 taken on this map */
+enum { WO_HC_SECTIONS,            /* voiced sections entering step 3 */
+       WO_HC_REJECTED, WO_HC_KEPT, WO_HC_COMPACTED,   /* ExtendSub: dropped, kept, kept behind a dropped one (moved down) */
+       WO_HC_MERGE_DISJOINT, WO_HC_MERGE_CONTAINED, WO_HC_MERGE_S1_GT, WO_HC_MERGE_S1_EQ, WO_HC_MERGE_S1_LT,
+       WO_HC_MERGE_OUT_OF_ORDER,  /* channel 0 met again at its sorted position */
+       WO_HC_BRIDGED,             /* FixStep4: gaps filled */
+       WO_HC_EXTEND_STOPPED, WO_HC_EXTEND_FULL_REACH,  /* ExtendF0: ended by four misses / by its reach */
+       WO_HC_EXTEND_TIE,          /* another value exactly as near as the one picked */
+       WO_HC_EXTEND_AT_RANGE,     /* picked exactly at the allowed range */
+       WO_HC_EXTEND_HIT_AFTER_3,  /* a hit after three misses */
+       WO_HC_COUNTERS };
 void wo_dio(const double *x, int x_length, int fs, double f0_floor,
             double f0_ceil, double channels_in_octave, double frame_period,
             int speed, double allowed_range, double *tpos, double *f0);

@@ -675,6 +675,29 @@ def run_d4c_select(wh):
     return out
 
 
+# ---- Harvest's contour stage in isolation (tests/harvest_contour_cases.py) ----------------------------------------------------
+def run_harvest_contour(wh):
+    """made-up candidate maps through world_hip_probe_harvest_contour: the wide-slot map (252 slots: four per tracking lane, the
+    ring of two), the many-section map (hc_merge out of HBM beside hc_merge in LDS, the smoother out of HBM) and a ragged batch
+    (nc = 0, 2, 14; 1 .. 2600 frames).  The walks of hc_extend park their picks in a slice other wavefronts sum afterwards, and
+    hc_merge and hc_smooth reuse the section table and the slices of the passes before: a missing barrier, a read of LDS or of
+    workspace nobody wrote changes these bits"""
+    import torch
+    import backends
+    import harvest_contour_cases as cases
+
+    class OnWh(backends.OnGpu, cases.Backend):
+        pass
+    be, out = OnWh(wh), []
+    for name in ("extend 252", "many sections", "ragged 5.0"):
+        g = cases.group(name)
+        for u, o in zip(g.utts, be.run(g)):
+            out += [(f"{name} {u.name} {k}", np.array(o[k])) for k in cases.OUT_ROWS + ("pruned_cand", "pruned_score", "tpos", "f0")]
+            out.append((f"{name} {u.name} sections", np.array(o["sec"][:2, :o["sec_n"][0]], dtype=np.float64)))
+    torch.cuda.synchronize()
+    return out
+
+
 # ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
 DROPIN_SECONDS = (0.5, 0.2, 0.31)
 
@@ -762,10 +785,12 @@ FAMILIES = {
                    + tuple(f"fft_route_d4c_twiddles<1, {n}, {n // 16}>" for n in (2048, 4096, 8192, 16384))
                    + tuple(f"fft_route_dft8<{s}, {h}>" for s in (0, 1) for h in ("false", "true")), {}),
     "d4c-select": (run_d4c_select, tuple(f"d4c_select_probe<{nt}>" for nt in (128, 256, 512, 1024)), {}),
+    "harvest-contour": (run_harvest_contour, ("hv_prune",) + _CONTOUR, {}),
     "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
                                                             "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
                        + _SYNTHESIS, {}),
 }
+# (harvest-contour is not among them: the probe carves Harvest's back-half workspace at every call.)
 # Families whose calls carve nothing from the arena and keep no buffer of their own between calls (cached tables apart): a
 # second pass in the same context has nothing to refill, so the hbm build's counter need only rise in the first (the tables'
 # allocation).  Every other family must see it rise in both passes.

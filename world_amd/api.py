@@ -309,6 +309,9 @@ def load_library(path=LIB_PATH):
         lib.world_hip_probe_fft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
     if hasattr(lib, "world_hip_probe_select"):                       # (added under ABI 6: looked up by name)
         lib.world_hip_probe_select.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
+    if hasattr(lib, "world_hip_probe_harvest_contour"):              # (added under ABI 6: looked up by name)
+        lib.world_hip_probe_harvest_contour.argtypes = [vp, C.c_int, _ip, _ip, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int,
+                                                        vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                              C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
     lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
@@ -1466,6 +1469,33 @@ class WorldHip:
         out = t.empty((keys.shape[0], 3), dtype=t.float64, device=keys.device)
         self._check(self.lib.world_hip_probe_select(self._context(), mode, keys.shape[1], K, keys.shape[0], keys.data_ptr(),
                                                     out.data_ptr()), "probe_select")
+        return out
+
+    def probe_harvest_contour(self, cand, score, nfb, nc, frame_period=5.0):
+        """Harvest's back half alone (include/world_hip.h: world_hip_probe_harvest_contour): cand, score [n_utt, fb_stride, maxc]
+        float64 refined candidates and scores, nfb and nc sequences of n_utt ints, fb_stride = (max(nfb) + 7) & ~7 -> a dict
+        of tensors: pruned_cand, pruned_score (as cand), step2, step3, step4, basic_f0 [n_utt, fb_stride], sec_n [n_utt, 2],
+        sec [n_utt, 6, max(nfb) // 2 + 4] (int32), tpos, f0 [n_utt, frames] and n_frames (a list).  What the call does not
+        write -- rows past nfb[u], frames past n_frames[u] -- is NaN (-1 in the int tensors)."""
+        t = self.torch
+        assert cand.dtype == score.dtype == t.float64 and cand.is_contiguous() and score.is_contiguous()
+        assert cand.dim() == 3 and cand.shape == score.shape and len(nfb) == len(nc) == cand.shape[0]
+        n, stride, maxc = cand.shape
+        nfb, nc = [int(v) for v in nfb], [int(v) for v in nc]
+        frames = [int((f - 1) / frame_period) + 1 for f in nfb]
+        sec_cap, f_stride = max(nfb) // 2 + 4, max(max(frames), 1)
+        nan = lambda *shape: t.full(shape, float("nan"), dtype=t.float64, device=cand.device)
+        out = dict(pruned_cand=nan(n, stride, maxc), pruned_score=nan(n, stride, maxc), step2=nan(n, stride), step3=nan(n, stride),
+                   step4=nan(n, stride), sec_n=t.full((n, 2), -1, dtype=t.int32, device=cand.device),
+                   sec=t.full((n, 6, sec_cap), -1, dtype=t.int32, device=cand.device), basic_f0=nan(n, stride),
+                   tpos=nan(n, f_stride), f0=nan(n, f_stride))
+        ints = lambda v: (C.c_int * n)(*v)
+        self._check(self.lib.world_hip_probe_harvest_contour(
+            self._context(), n, ints(nfb), ints(nc), maxc, stride, cand.data_ptr(), score.data_ptr(), frame_period, f_stride,
+            out["pruned_cand"].data_ptr(), out["pruned_score"].data_ptr(), out["step2"].data_ptr(), out["step3"].data_ptr(),
+            out["step4"].data_ptr(), sec_cap, out["sec_n"].data_ptr(), out["sec"].data_ptr(), out["basic_f0"].data_ptr(),
+            out["tpos"].data_ptr(), out["f0"].data_ptr()), "probe_harvest_contour")
+        out["n_frames"] = frames
         return out
 
     # ---- multi-GPU exchange records (include/world_hip.h: world_hip_pack_results) ----

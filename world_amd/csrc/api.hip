@@ -828,6 +828,29 @@ static void prepare_bands(WorldHipContext *c, int fs, double f0_floor, double f0
   hb.win_tab_len = hw_max + 1;
 }
 
+// Harvest's back half -- hv_prune and the contour kernels (launch_harvest_tail) -- as run_harvest and
+// world_hip_probe_harvest_contour both set it up: the HarvestParams fields those kernels read beside maxc, nc and nfb, and the
+// part of the workspace they work in (the end of run_harvest's carve).
+static void plan_harvest_tail(const WorldHipContext *c, HarvestParams &p, int n_utt, int max_fb) {
+  p.fb_stride = (max_fb + 7) & ~7;
+  p.sec_cap = hv_section_rows(max_fb);
+  p.lone_job = n_utt == 1 && !(c->hint & WORLD_HIP_HINT_SHARED_DEVICE);
+  p.ext_cap = max_fb + 304 * hv_sliced_sections(max_fb) + 8;
+}
+static void carve_harvest_tail(Arena &a, HarvestParams &p, size_t B) {
+  const size_t cand_elems = B * p.fb_stride * p.maxc;
+  p.cand_a = a.take<double>(cand_elems); p.score_a = a.take<double>(cand_elems);
+  p.cand_b = a.take<double>(cand_elems); p.score_b = a.take<double>(cand_elems);
+  p.nc = a.take<int>(B);
+  p.c0 = a.take<double>(B * p.fb_stride);
+  p.c2 = a.take<double>(B * p.fb_stride); p.c3 = a.take<double>(B * p.fb_stride);
+  p.basic_f0 = a.take<double>(B * p.fb_stride);
+  p.sec = a.take<int>(B * 6 * p.sec_cap);
+  p.sec_n = a.take<int>(B * 2);
+  p.sec_sum = a.take<double>(B * p.sec_cap);
+  p.ext = a.take<double>(B * p.ext_cap);
+}
+
 static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x, int x_stride,
                         const int *x_length, const HarvestOption *opt, int f_stride, double *d_tpos,
                         double *d_f0) {
@@ -858,13 +881,10 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
     max_fb = std::max(max_fb, nfb[u]); max_fr = std::max(max_fr, nfr[u]);
   }
   p.y_stride = (max_y + 7) & ~7;
-  p.fb_stride = (max_fb + 7) & ~7;
+  plan_harvest_tail(c, p, n_utt, max_fb);
   p.m_stride = (max_x + 2 * p.lag + 2 * kDecPad + 7) & ~7;
   p.ev_cap = max_y / 2 + 2;
   p.refine_cap = 2 * static_cast<int>(1.5 * p.afs / opt->f0_floor + 1.0) + 4;
-  p.sec_cap = max_fb / 7 + 4;
-  p.lone_job = n_utt == 1 && !(c->hint & WORLD_HIP_HINT_SHARED_DEVICE);
-  p.ext_cap = max_fb + 304 * p.sec_cap + 8;
   p.max_half = hb.max_half;
   p.tab = c->tab;
   p.fft_seg = hb.fft_seg;
@@ -896,7 +916,6 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   p.ev_group = std::min(n_utt, ev_group_env);
   p.ev_u0 = 0;
   const size_t E = p.ev_group;
-  const size_t cand_elems = B * p.fb_stride * p.maxc;
   p.nyq_slices = (max_y + 4095) / 4096;                                // kMeanSlice of harvest.hip
   // launch_harvest's grids: spans of the decimation sweeps (harvest.hip), or the 4096-sample slices at ratio 1
   p.mean_parts = p.ratio == 1 ? p.nyq_slices : (max_x + 2 * p.lag + 2 * kDecPad + kDecSpan - 1) / kDecSpan;
@@ -916,16 +935,7 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
     }
     p.blk_spec = a.take<double2>(B * p.nblk * kBandFftBins);
     p.raw = a.take<double>(B * p.nch * p.fb_stride);
-    p.cand_a = a.take<double>(cand_elems); p.score_a = a.take<double>(cand_elems);
-    p.cand_b = a.take<double>(cand_elems); p.score_b = a.take<double>(cand_elems);
-    p.nc = a.take<int>(B);
-    p.c0 = a.take<double>(B * p.fb_stride);
-    p.c2 = a.take<double>(B * p.fb_stride); p.c3 = a.take<double>(B * p.fb_stride);
-    p.basic_f0 = a.take<double>(B * p.fb_stride);
-    p.sec = a.take<int>(B * 6 * p.sec_cap);
-    p.sec_n = a.take<int>(B * 2);
-    p.sec_sum = a.take<double>(B * p.sec_cap);
-    p.ext = a.take<double>(B * p.ext_cap);
+    carve_harvest_tail(a, p, B);
   });
   p.b = batch_view(c, n_utt, fs, d_x, x_stride, x_length, nfr.data(), f_stride);
   p.y_len = upload(c, yl);
@@ -3002,6 +3012,76 @@ int world_hip_probe_select(WorldHipContext *c, int mode, int threads, int K, lon
     if (!d_keys || !d_out) fail("probe_select: null buffer (%s)", !d_keys ? "keys" : "out");
     if (rows == 0) return;
     if (!launch_d4c_select_probe(mode, threads, K, (long)rows, d_keys, d_out, c->stream)) fail("probe_select: threads = %d has no kernel", threads);
+  });
+}
+
+// Harvest's back half in isolation (harvest.hip: launch_harvest_tail -- hv_prune and the contour kernels, as launch_harvest
+// ends), on candidates the caller made up: run_harvest's plan and carve of that half (plan_harvest_tail, carve_harvest_tail),
+// the caller's candidates copied where hv_refine leaves its own, the workspace's rows copied out behind the last launch.
+int world_hip_probe_harvest_contour(WorldHipContext *c, int n_utt, const int *nfb, const int *nc, int maxc, int fb_stride,
+                                    const double *d_cand, const double *d_score, double frame_period, int f_stride,
+                                    double *d_pruned_cand, double *d_pruned_score, double *d_step2, double *d_step3,
+                                    double *d_step4, int sec_cap, int *d_sec_n, int *d_sec, double *d_basic_f0,
+                                    double *d_tpos, double *d_f0) {
+  return guarded(c, [&] {
+    const char *const me = "probe_harvest_contour";
+    if (n_utt <= 0 || n_utt > kGridY) fail("%s: n_utt = %d outside 1 .. %d", me, n_utt, kGridY);
+    if (!nfb || !nc) fail("%s: null buffer (%s)", me, !nfb ? "nfb" : "nc");
+    if (maxc < 7 || maxc > 256 || maxc % 7) fail("%s: maxc = %d is not a multiple of 7 in 7 .. 252 (256 slots is what the tracking kernel handles)", me, maxc);
+    if (!(frame_period > 0)) fail("%s: frame_period must be positive", me);
+    const struct { const void *p; const char *name; } bufs[] = {
+        {d_cand, "cand"}, {d_score, "score"}, {d_pruned_cand, "pruned_cand"}, {d_pruned_score, "pruned_score"}, {d_step2, "step2"},
+        {d_step3, "step3"}, {d_step4, "step4"}, {d_sec_n, "sec_n"}, {d_sec, "sec"}, {d_basic_f0, "basic_f0"}, {d_tpos, "tpos"}, {d_f0, "f0"}};
+    for (const auto &b : bufs)
+      if (!b.p) fail("%s: null buffer (%s)", me, b.name);
+    HarvestParams p{};
+    p.maxc = maxc; p.frame_period = frame_period;
+    std::vector<int> fb(nfb, nfb + n_utt), cn(nc, nc + n_utt), nfr(n_utt);
+    int max_fb = 0, max_fr = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (fb[u] < 1) fail("%s: nfb[%d] = %d: an utterance has at least one frame", me, u, fb[u]);
+      if (cn[u] < 0 || cn[u] * 7 > maxc) fail("%s: nc[%d] = %d: 7 nc slots do not fit maxc = %d", me, u, cn[u], maxc);
+      // Harvest()'s frame count (harvest.cpp:1219) of a signal that ends on 1 ms frame nfb - 1
+      nfr[u] = static_cast<int>((fb[u] - 1) / frame_period) + 1;
+      if (nfr[u] > f_stride) fail("%s: f_stride %d too small for %d frames", me, f_stride, nfr[u]);
+      max_fb = std::max(max_fb, fb[u]); max_fr = std::max(max_fr, nfr[u]);
+    }
+    plan_harvest_tail(c, p, n_utt, max_fb);
+    if (fb_stride != p.fb_stride) fail("%s: fb_stride = %d, the batch's is %d (max nfb rounded up to 8)", me, fb_stride, p.fb_stride);
+    if (sec_cap != p.sec_cap) fail("%s: sec_cap = %d, the batch's is %d (max nfb / 2 + 4)", me, sec_cap, p.sec_cap);
+    const size_t B = n_utt, row = p.fb_stride, cand_bytes = sizeof(double) * B * row * maxc;
+    refuse_overlap(me,
+                   {{d_pruned_cand, cand_bytes, "pruned_cand"}, {d_pruned_score, cand_bytes, "pruned_score"},
+                    {d_step2, sizeof(double) * B * row, "step2"}, {d_step3, sizeof(double) * B * row, "step3"},
+                    {d_step4, sizeof(double) * B * row, "step4"}, {d_basic_f0, sizeof(double) * B * row, "basic_f0"},
+                    {d_sec_n, sizeof(int) * B * 2, "sec_n"}, {d_sec, sizeof(int) * B * 6 * p.sec_cap, "sec"},
+                    {d_tpos, sizeof(double) * B * f_stride, "tpos"}, {d_f0, sizeof(double) * B * f_stride, "f0"}},
+                   {{d_cand, cand_bytes, "cand"}, {d_score, cand_bytes, "score"}});
+    begin_stage(c, [&](Arena &a) { carve_harvest_tail(a, p, B); });
+    p.b.n_utt = n_utt; p.b.f_stride = f_stride;
+    p.b.n_frames = upload(c, nfr);
+    p.nfb = upload(c, fb);
+    devrt::d2d(p.nc, upload(c, cn), sizeof(int) * B, c->stream);                  // (hv_detect's output in the product)
+    for (size_t u = 0; u < B; ++u) {                                              // rows past nfb[u] stay the workspace's
+      const size_t at = u * row * maxc, n = sizeof(double) * fb[u] * maxc;
+      devrt::d2d(p.cand_b + at, d_cand + at, n, c->stream);
+      devrt::d2d(p.score_b + at, d_score + at, n, c->stream);
+    }
+    p.tpos = d_tpos; p.f0 = d_f0;
+    launch_harvest_tail(p, max_fb, max_fr, c->stream);
+    for (size_t u = 0; u < B; ++u) {                                              // the rows of the utterance, no others
+      const size_t at = u * row * maxc, n = sizeof(double) * fb[u] * maxc, f = u * row, nf = sizeof(double) * fb[u];
+      if (cn[u]) {                                                                // (nc = 0: hv_prune has nothing to write)
+        devrt::d2d(d_pruned_cand + at, p.cand_a + at, n, c->stream);
+        devrt::d2d(d_pruned_score + at, p.score_a + at, n, c->stream);
+      }
+      devrt::d2d(d_step2 + f, p.c2 + f, nf, c->stream);
+      devrt::d2d(d_step3 + f, p.c3 + f, nf, c->stream);
+      devrt::d2d(d_step4 + f, p.c0 + f, nf, c->stream);
+      devrt::d2d(d_basic_f0 + f, p.basic_f0 + f, nf, c->stream);
+    }
+    devrt::d2d(d_sec_n, p.sec_n, sizeof(int) * B * 2, c->stream);
+    devrt::d2d(d_sec, p.sec, sizeof(int) * B * 6 * p.sec_cap, c->stream);
   });
 }
 

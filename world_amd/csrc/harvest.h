@@ -21,7 +21,8 @@ struct HarvestParams {
   int fb_stride;           // 1 ms ("basic") frames per utterance slot
   int ev_cap;              // capacity of one event list
   int refine_cap;          // LDS doubles per refinement window
-  int sec_cap;             // voiced sections per utterance slot
+  int sec_cap;             // rows of the section table per utterance slot: the most voiced runs a contour of the longest utterance
+                           // can have (hv_section_rows); only hv_sliced_sections of them ever carry a slice of `ext`
   int lone_job;            // host only: this job has the device to itself (one utterance, no WORLD_HIP_HINT_SHARED_DEVICE):
                            // the one-workgroup-per-utterance contour kernels take 1024 threads instead of 256
   int ext_cap;             // doubles of extended-section storage per utterance
@@ -81,12 +82,20 @@ struct HarvestParams {
   double *f0;              // [n_utt][f_stride]
 };
 
+// Voiced sections of an utterance of max_fb 1 ms frames.  Step 2 leaves runs of at least seven frames and step 4 runs at least
+// nine unvoiced frames apart (two more at the forced ends): at most max_fb / 7 + 4 sections walk, merge, are smoothed and own a
+// slice of `ext`.  Step 3's contour between the two is another matter -- Extend writes a frame wherever it finds a candidate
+// and goes on over up to three misses, so its runs can be one frame long and one frame apart -- and FixStep4 must see every
+// one of them to bridge the gaps: the section TABLE has a row for every second frame.
+inline int hv_sliced_sections(int max_fb) { return max_fb / 7 + 4; }
+inline int hv_section_rows(int max_fb) { return max_fb / 2 + 4; }
 constexpr int kBandFftLg = 12, kBandFft = 1 << kBandFftLg, kBandFftBins = kBandFft / 2 + 1;
 int hv_fft_segment(int max_half);          // outputs per block of the FFT path, 0 = filters too long for it
 void launch_band_spectra(const double *d_taps, const int *d_off, const int *d_half, int nch, double2 *d_spec,
                          const Tables &tab, hipStream_t stream);
 void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int max_fb, int max_frames,
                     hipStream_t stream);
+void launch_harvest_tail(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);     // hv_prune + the contour
 void launch_harvest_contour(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);
 
 }  // namespace world_hip

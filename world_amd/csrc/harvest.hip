@@ -1170,6 +1170,13 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
     WH_WAVES(hv_refine, max_fb, B, 1, sizeof(double) * (3 * p.refine_cap + 6 * static_cast<int>(p.afs / 1000.0) + 2), stream, p);
   else
     WH_WAVES(hv_refine_frames, max_fb, B, 1, 3 * sizeof(double) * p.refine_cap, stream, p);
+  launch_harvest_tail(p, max_fb, max_frames, stream);
+}
+
+// The back half, refined candidates (cand_b / score_b, nc) -> F0: the launches launch_harvest ends with, and all that
+// world_hip_probe_harvest_contour runs (api.hip: the same HarvestParams fields and workspace, made-up candidates).
+void launch_harvest_tail(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream) {
+  const int B = p.b.n_utt;
   WH_BLOCKS(hv_prune, dim3((max_fb + kPruneFrames - 1) / kPruneFrames, B), 256,
             sizeof(double) * (size_t)(2 * kPruneFrames + 2) * p.maxc, stream, p);          // + the base pick (c0)
   launch_harvest_contour(p, max_fb, max_frames, stream);

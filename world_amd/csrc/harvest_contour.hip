@@ -317,8 +317,9 @@ __device__ __forceinline__ void hc_extend_section(const HarvestParams &p, int k,
 #ifndef WORLD_EMU
           {
             // One reduction carries distance AND slot: the slot rides in the low mantissa byte of the distance
-            // (255 - slot, so that the later slot of two equal distances is the smaller key).  Distances that agree to
-            // 2^-44 count as equal -- two candidates equally near the previous pick to thirteen digits.  DPP +
+            // (255 - slot, so that the later slot of two equal distances is the smaller key).  THE RULE: distances that are
+            // equal after clearing their low 8 mantissa bits count as equal and the later slot wins -- two candidates equally
+            // near the previous pick to thirteen digits (tests/harvest_contour_cases.py: near ties).  DPP +
             // readlane, no LDS round trips on the frame-to-frame chain; the winner's exact distance is recomputed.
             static_assert(kMaxSlots <= 256, "the slot index rides in one byte");
             const long long kb = (__double_as_longlong(best_d) & ~0xFFll) | (long long)(0xFF - (best_i & 0xFF));
@@ -877,16 +878,18 @@ void launch_harvest_contour(const HarvestParams &p, int max_fb, int max_frames, 
   // a job that has the device to itself: sixteen wavefronts per utterance for the two one-workgroup kernels (VERDICT r05
   // item 7: the shapes sized for the in-flight mode had cost a lone job 0.04 ms)
   WH_BLOCKS(hc_step12_sections, dim3(B), p.lone_job ? 1024 : 256, (64 + kStepLds) * sizeof(double), stream, p, a2);
-  WH_BLOCKS(hc_extend, dim3(imin(p.sec_cap, kExtendBlocks), B), kExtendThreads, 64 * sizeof(double), stream, p);
+  // (the sections that walk, merge and are smoothed: harvest.h -- the table itself, p.sec_cap rows, is longer for step 4's sake)
+  const int sliced = imin(p.sec_cap, hv_sliced_sections(max_fb));
+  WH_BLOCKS(hc_extend, dim3(imin(sliced, kExtendBlocks), B), kExtendThreads, 64 * sizeof(double), stream, p);
   // WORLD_HIP_MERGE_LDS_SECTIONS lowers the number of section records hc_merge keeps in LDS (tests use it to send an
   // ordinary utterance down the route of one with thousands of sections)
   static const int merge_limit = [] { const char *e = getenv("WORLD_HIP_MERGE_LDS_SECTIONS"); return e ? imax(0, imin(kMergeLdsSections, atoi(e))) : kMergeLdsSections; }();
-  const int merge_cap = imin(p.sec_cap, merge_limit);
+  const int merge_cap = imin(sliced, merge_limit);
   // (+ FixStep4 and the two section passes around it; then hc_smooth writes basic_f0's voiced frames)
   WH_BLOCKS(hc_merge, dim3(B), p.lone_job ? kMergeThreadsLone : kMergeThreads, hc_merge_lds_bytes(merge_cap), stream, p, merge_cap);
   // one wavefront per block: each reserves LDS for the longest section the batch can hold
   const int smooth_lds = imin(kSmoothLdsMax, max_fb + 3 * kSmoothTail + kSmoothSlack);
-  WH_BLOCKS(hc_smooth, dim3(imin(p.sec_cap, kSmoothBlocks), B), WAVE, smooth_lds * sizeof(double), stream, p, smooth_lds);
+  WH_BLOCKS(hc_smooth, dim3(imin(sliced, kSmoothBlocks), B), WAVE, smooth_lds * sizeof(double), stream, p, smooth_lds);
   WH_THREADS(hc_output, max_frames, B, 1, stream, p);
 }
 
