@@ -484,6 +484,32 @@ WORLD_HIP_API int world_hip_probe_harvest_contour(WorldHipContext *ctx, int n_ut
                                                   int f_stride, double *d_pruned_cand, double *d_pruned_score, double *d_step2,
                                                   double *d_step3, double *d_step4, int sec_cap, int *d_sec_n, int *d_sec,
                                                   double *d_basic_f0, double *d_tpos, double *d_f0);
+/* Harvest's middle in isolation (csrc/harvest.hip: hv_compact_events, hv_raw_candidates -- GetF0CandidateContour, src/harvest.cpp:
+ * 240-293, on the intervals of ZeroCrossingEngine's fine edges, :188-190 -- and hv_detect, DetectOfficialF0Candidates, :348-412)
+ * on zero-crossing lists the caller made up, where Harvest proper takes them from the filter bank: the same kernels, grids and
+ * LDS sizes, and the lists of ONE group of ev_group utterances in the workspace at a time, as a Harvest call walks them.
+ *   nfb (host, [n_utt])      1 ms frames per utterance (>= 1); frame f sits at f / 1000 s
+ *   afs, f0_floor, f0_ceil   analysis rate (events are in samples of it) and the gate's limits
+ *   nch, band_f0 (host, [nch])  12 .. 365 bands and their positive boundary F0s; maxc = round(nch / 10) * 7, Harvest's own
+ *   fb_stride                (max nfb + 7) & ~7, given so that both sides state it
+ *   nseg, seg_cap, ev_cap    segment lists per (utterance, band, family), the capacity of one, the capacity of a final list.
+ *                            nseg = 1: the segment lists ARE the final lists (seg_cap = ev_cap) and no compaction runs
+ *   ev_group                 utterances whose lists are in the workspace at once (Harvest's own: WORLD_HIP_EVENT_GROUP, 40)
+ *   stages                   1 compaction, 2 raw candidates (behind the compaction where nseg > 1), 4 detection
+ *   d_seg_events [n_utt][nch * 4][nseg][seg_cap], d_seg_count [n_utt][nch * 4][nseg]  ascending fine edges per family (falling,
+ *                            rising, peaks, dips) and their numbers, 0 .. seg_cap (read back and checked: a refusal otherwise)
+ * Out (device); what is not named is not touched:
+ *   d_events [n_utt][nch * 4][ev_cap], d_ev_count [n_utt][nch * 4]  stage 1 with nseg > 1: the first ev_count events of every list
+ *   d_raw [n_utt][nch][fb_stride]  stage 2: frames 0 .. nfb[u] - 1 of every band.  Without stage 2 it is detection's INPUT
+ *   d_cand [n_utt][fb_stride][maxc]  stage 4: slots 0 .. min(maxc, (nch + 10) / 11 + 1) - 1 of frames 0 .. nfb[u] - 1
+ *   d_nc [n_utt]             stage 4: the most candidates a frame of the utterance has (cleared by the probe; in a Harvest call
+ *                            hv_remove_mean clears it)
+ * Buffers of stages that do not run may be null.  A refusal names the argument and writes nothing. */
+WORLD_HIP_API int world_hip_probe_harvest_candidates(WorldHipContext *ctx, int n_utt, const int *nfb, double afs, double f0_floor,
+                                                     double f0_ceil, int nch, const double *band_f0, int maxc, int fb_stride,
+                                                     int nseg, int seg_cap, int ev_cap, int ev_group, int stages,
+                                                     const double *d_seg_events, const int *d_seg_count, double *d_events,
+                                                     int *d_ev_count, double *d_raw, double *d_cand, int *d_nc);
 
 /* Multi-GPU exchange (the reference has no counterpart).  Utterances are sharded over GPUs
  * and analysed independently; a GPU's results are then packed into ONE contiguous block of records

@@ -8,6 +8,8 @@ Two interchangeable back ends with one Python surface:
   tests measure both the GPU and the reference against.
 * ``RefContour``  -- oracle/_ref/libworld_ref_contour.so, the reference's contour stage of Harvest
   on made-up candidates (oracle/harvest_contour_ref.cpp).
+* ``RefCandidates`` -- oracle/_ref/libworld_ref_candidates.so, the reference's candidate stage of Harvest
+  on made-up zero-crossing lists (oracle/harvest_candidates_ref.cpp).
 * ``RefOracle``   -- oracle/_ref/libworld_ref*.so, the UNMODIFIED reference
   compiled in place from /root/reference by oracle/Makefile (present whenever
   it was built in the container; the .so travels to the GPU box).
@@ -74,6 +76,10 @@ class PortOracle(_Base):
         if hasattr(L, "wo_harvest_contour"):
             L.wo_harvest_contour.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_double] + [_dp] * 8 + [C.POINTER(C.c_int)]
             L.wo_harvest_smooth.argtypes = [_dp, C.c_int, _dp]
+        if hasattr(L, "wo_harvest_candidates"):
+            L.wo_harvest_candidates.restype = C.c_int
+            L.wo_harvest_candidates.argtypes = [_dp, C.POINTER(C.c_int), C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double,
+                                                C.c_double, _dp, _dp, C.c_int]
         L.wo_dio.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                              C.c_int, C.c_double, _dp, _dp]
         L.wo_stonemask.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]
@@ -166,6 +172,12 @@ class PortOracle(_Base):
         f0 = _f64(f0); out = np.zeros(len(f0))
         self.lib.wo_harvest_smooth(_p(f0), len(f0), _p(out))
         return out
+
+    def harvest_candidates(self, nf, band_f0, edges=None, counts=None, raw=None, afs=8000.0, f0_floor=71.0, f0_ceil=800.0):
+        """Harvest's candidate stage on made-up lists: edges [nch, 4, ev_cap] fine edges, counts [nch, 4] (or raw [nch, nf]
+        given: detection alone) -> raw [nch, nf], cand [nf, maxc], nc"""
+        return _harvest_candidates(nf, band_f0, edges, counts, raw, lambda e, c, cap, b, nch, maxc, r, cand: (
+            self.lib.wo_harvest_candidates(e, c, cap, afs, b, nch, nf, f0_floor, f0_ceil, r, _p(cand), maxc), cand), maxc_wide=False)
 
     def dio(self, x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_period=5.0,
             speed=1, allowed_range=0.1):
@@ -307,6 +319,60 @@ class RefContour:
         f0 = _f64(f0); out = np.zeros(len(f0))
         self.lib.ref_smooth_f0(_p(f0), len(f0), _p(out))
         return out
+
+
+def _harvest_candidates(nf, band_f0, edges, counts, raw, call, maxc_wide):
+    """the argument handling PortOracle.harvest_candidates and RefCandidates.harvest_candidates share; cand rows are maxc wide,
+    or nch wide and cut to maxc (the reference's Sub2 does not check its cap)"""
+    band_f0 = _f64(band_f0)
+    nch = len(band_f0)
+    maxc = int(nch / 10.0 + 0.5) * 7
+    if edges is not None:
+        edges, counts = _f64(edges), np.ascontiguousarray(counts, dtype=np.int32)
+        assert edges.ndim == 3 and edges.shape[:2] == counts.shape == (nch, 4) and counts.max(initial=0) <= edges.shape[2]
+        raw = np.zeros((nch, nf))
+        e, c, cap = _p(edges), counts.ctypes.data_as(C.POINTER(C.c_int)), edges.shape[2]
+    else:
+        raw = np.array(_f64(raw))
+        assert raw.shape == (nch, nf)
+        e, c, cap = None, None, 0
+    cand = np.zeros((nf, nch if maxc_wide else maxc))
+    nc, cand = call(e, c, cap, _p(band_f0), nch, maxc, _p(raw), cand)
+    assert nc <= maxc
+    return dict(raw=raw, cand=np.ascontiguousarray(cand[:, :maxc]), nc=int(nc))
+
+
+class RefCandidates:
+    """oracle/_ref/libworld_ref_candidates.so: the reference's own GetF0CandidateContour, DetectOfficialF0Candidates and
+    ZeroCrossingEngine (oracle/harvest_candidates_ref.cpp includes the reference's harvest.cpp in place)"""
+    kind = "reference"
+    path = os.path.join(HERE, "_ref", "libworld_ref_candidates.so")
+
+    @classmethod
+    def available(cls):
+        return os.path.exists(cls.path)
+
+    def __init__(self):
+        if not self.available():
+            raise FileNotFoundError(self.path)
+        self.lib = C.CDLL(self.path)
+        self.lib.ref_harvest_candidates.restype = C.c_int
+        self.lib.ref_harvest_candidates.argtypes = [_dp, C.POINTER(C.c_int), C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double,
+                                                    C.c_double, C.c_int, _dp, _dp]
+        self.lib.ref_zero_crossing_engine.restype = C.c_int
+        self.lib.ref_zero_crossing_engine.argtypes = [_dp, C.c_int, C.c_double, _dp, _dp]
+
+    def harvest_candidates(self, nf, band_f0, edges=None, counts=None, raw=None, afs=8000.0, f0_floor=71.0, f0_ceil=800.0):
+        """as PortOracle.harvest_candidates"""
+        return _harvest_candidates(nf, band_f0, edges, counts, raw, lambda e, c, cap, b, nch, maxc, r, cand: (
+            self.lib.ref_harvest_candidates(e, c, cap, afs, b, nch, nf, f0_floor, f0_ceil, maxc, r, _p(cand)), cand), maxc_wide=True)
+
+    def zero_crossing_engine(self, signal, fs):
+        """ZeroCrossingEngine on a signal -> (interval locations, intervals)"""
+        signal = _f64(signal)
+        loc, val = np.zeros(len(signal)), np.zeros(len(signal))
+        n = self.lib.ref_zero_crossing_engine(_p(signal), len(signal), fs, _p(loc), _p(val))
+        return loc[:n], val[:n]
 
 
 def ref_available():

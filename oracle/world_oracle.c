@@ -392,6 +392,17 @@ int wo_frame_count(int fs, int x_length, double frame_period) {
 /* ------------------------------------------------------------------ */
 typedef struct { double *loc, *val; int n; } Intervals;
 
+/* harvest.cpp:188-190: cnt fine edges -> cnt - 1 intervals (none of fewer than two) */
+static void intervals_of_edges(const double *fine, int cnt, double fs, Intervals *out) {
+  out->n = 0;
+  if (cnt < 2) return;
+  for (int i = 0; i < cnt - 1; ++i) {
+    out->val[i] = fs / (fine[i + 1] - fine[i]);
+    out->loc[i] = (fine[i] + fine[i + 1]) / 2.0 / fs;
+  }
+  out->n = cnt - 1;
+}
+
 static void crossing_intervals(const double *s, int n, double fs, Intervals *out) {
   int *edge = ialloc(n);
   int cnt = 0;
@@ -402,11 +413,7 @@ static void crossing_intervals(const double *s, int n, double fs, Intervals *out
     double *fine = dalloc(cnt);
     for (int i = 0; i < cnt; ++i)
       fine[i] = edge[i] - s[edge[i] - 1] / (s[edge[i]] - s[edge[i] - 1]);
-    for (int i = 0; i < cnt - 1; ++i) {
-      out->val[i] = fs / (fine[i + 1] - fine[i]);
-      out->loc[i] = (fine[i] + fine[i + 1]) / 2.0 / fs;
-    }
-    out->n = cnt - 1;
+    intervals_of_edges(fine, cnt, fs, out);
     free(fine);
   }
   free(edge);
@@ -479,6 +486,29 @@ static void harvest_front_end(const double *x, int n, int y_len, int fft_size, i
   wo_rfft(fft_size, y, Yr, Yi);
 }
 
+/* harvest.cpp:240-293 : the four families' intervals of one band -> raw candidate contour */
+static void harvest_band_candidates(const Intervals fam[4], double fb, double f0_floor, double f0_ceil,
+                                    const double *tpos, int nf, double *cand) {
+  int ok = 1;
+  for (int f = 0; f < 4; ++f) if (fam[f].n - 2 <= 0) ok = 0;
+  if (!ok) {
+    for (int i = 0; i < nf; ++i) cand[i] = 0.0;
+    return;
+  }
+  double *ip[4];
+  for (int f = 0; f < 4; ++f) {
+    ip[f] = dalloc(nf);
+    wo_interp1(fam[f].loc, fam[f].val, fam[f].n, tpos, nf, ip[f]);
+  }
+  double up = fb * 1.1, lo = fb * 0.9;
+  for (int i = 0; i < nf; ++i) {
+    double c = (ip[0][i] + ip[1][i] + ip[2][i] + ip[3][i]) / 4.0;
+    if (c > up || c < lo || c > f0_ceil || c < f0_floor) c = 0.0;
+    cand[i] = c;
+  }
+  for (int f = 0; f < 4; ++f) free(ip[f]);
+}
+
 /* harvest.cpp:99-148, 240-329 : one band -> raw candidate contour */
 static void harvest_band(double fb, double fs, const double *Yr, const double *Yi,
                          int y_len, int fft_size, double f0_floor, double f0_ceil,
@@ -494,24 +524,7 @@ static void harvest_band(double fb, double fs, const double *Yr, const double *Y
 
   Intervals fam[4];
   four_families(sig, y_len, fs, fam);
-  int ok = 1;
-  for (int f = 0; f < 4; ++f) if (fam[f].n - 2 <= 0) ok = 0;
-  if (!ok) {
-    for (int i = 0; i < nf; ++i) cand[i] = 0.0;
-  } else {
-    double *ip[4];
-    for (int f = 0; f < 4; ++f) {
-      ip[f] = dalloc(nf);
-      wo_interp1(fam[f].loc, fam[f].val, fam[f].n, tpos, nf, ip[f]);
-    }
-    double up = fb * 1.1, lo = fb * 0.9;
-    for (int i = 0; i < nf; ++i) {
-      double c = (ip[0][i] + ip[1][i] + ip[2][i] + ip[3][i]) / 4.0;
-      if (c > up || c < lo || c > f0_ceil || c < f0_floor) c = 0.0;
-      cand[i] = c;
-    }
-    for (int f = 0; f < 4; ++f) free(ip[f]);
-  }
+  harvest_band_candidates(fam, fb, f0_floor, f0_ceil, tpos, nf, cand);
   free_families(fam);
   free(h); free(hr); free(hi); free(sig);
 }
@@ -886,6 +899,32 @@ static void harvest_body(const double *x, int n, int fs, int frame_period, doubl
   for (int i = 0; i < nf; ++i) { free(cands[i]); free(scores[i]); }
   free(raw); free(cands); free(scores); free(best);
   free(y); free(Yr); free(Yi); free(fb);
+}
+
+/* Harvest's candidate stage on made-up zero-crossing lists (harvest.cpp:188-190, 240-293, 348-412): edges [nch][4][ev_cap]
+ * ascending fine edges per band and family, counts [nch][4] -> raw [nch][nf] and cand [nf][maxc] at the 1 ms frames
+ * i * 1 / 1000.0; returns the most candidates a frame has.  edges == NULL: raw is given, detection alone. */
+int wo_harvest_candidates(const double *edges, const int *counts, int ev_cap, double afs, const double *band_f0, int nch,
+                          int nf, double f0_floor, double f0_ceil, double *raw, double *cand, int maxc) {
+  double *tpos = dalloc(nf);
+  for (int i = 0; i < nf; ++i) tpos[i] = i * 1 / 1000.0;
+  double **rows = (double **)malloc(sizeof(double *) * nch), **cands = (double **)malloc(sizeof(double *) * nf);
+  for (int j = 0; j < nch; ++j) rows[j] = raw + (size_t)j * nf;
+  for (int i = 0; i < nf; ++i) cands[i] = cand + (size_t)i * maxc;
+  if (edges)
+    for (int j = 0; j < nch; ++j) {
+      Intervals fam[4];
+      for (int f = 0; f < 4; ++f) {
+        int cnt = counts[j * 4 + f];
+        fam[f].loc = dalloc(cnt); fam[f].val = dalloc(cnt);
+        intervals_of_edges(edges + ((size_t)j * 4 + f) * ev_cap, cnt, afs, &fam[f]);
+      }
+      harvest_band_candidates(fam, band_f0[j], f0_floor, f0_ceil, tpos, nf, rows[j]);
+      free_families(fam);
+    }
+  int nc = harvest_detect(rows, nch, nf, maxc, cands);
+  free(rows); free(cands); free(tpos);
+  return nc;
 }
 
 /* harvest.cpp:1223-1255 */

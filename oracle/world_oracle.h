@@ -64,6 +64,12 @@ enum { WO_HC_SECTIONS,            /* voiced sections entering step 3 */
        WO_HC_EXTEND_AT_RANGE,     /* picked exactly at the allowed range */
        WO_HC_EXTEND_HIT_AFTER_3,  /* a hit after three misses */
        WO_HC_COUNTERS };
+/* Harvest's candidate stage on made-up zero-crossing lists (harvest.cpp:188-190, 240-293, 348-412): edges [nch][4][ev_cap]
+ * ascending fine edges per band and family (falling, rising, peaks, dips), counts [nch][4] -> raw [nch][nf] at the 1 ms frames
+ * and cand [nf][maxc]; returns the most candidates a frame has.  edges == NULL: raw is given, detection alone.  A frame can
+ * hold (nch - 1) / 11 candidates: maxc must not be less. */
+int  wo_harvest_candidates(const double *edges, const int *counts, int ev_cap, double afs, const double *band_f0, int nch,
+                           int nf, double f0_floor, double f0_ceil, double *raw, double *cand, int maxc);
 void wo_dio(const double *x, int x_length, int fs, double f0_floor,
             double f0_ceil, double channels_in_octave, double frame_period,
             int speed, double allowed_range, double *tpos, double *f0);

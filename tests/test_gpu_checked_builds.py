@@ -698,6 +698,31 @@ def run_harvest_contour(wh):
     return out
 
 
+# ---- Harvest's candidate stage in isolation (tests/harvest_candidates_cases.py) ---------------------------------------------------
+def run_harvest_candidates(wh):
+    """made-up zero-crossing lists through world_hip_probe_harvest_candidates: the lists the proportional guess does not bracket
+    (the eight 32-lane searches of a workgroup share their ballots two to a wavefront), the runs at the staged capacity (range[]
+    is written by lanes 0 of eight groups and read by everybody across a barrier; staged and unstaged routes side by side), five
+    ragged utterances in groups of two (the next group's lists overwrite the one before in the same workspace: a stale read
+    changes the bits) and a 300-segment compaction (the scan's second trip, the flat copy's eight loads in flight)"""
+    import torch
+    import backends
+    import harvest_candidates_cases as cases
+
+    class OnWh(backends.OnGpu, cases.Backend):
+        pass
+    be, out = OnWh(wh), []
+    for name, ev_group in (("guess misses", 40), ("cap edge", 40), ("groups", 2)):
+        g = cases.group(name)
+        for u, o in zip(g.utts, be.run_group(g, ev_group=ev_group)):
+            out += [(f"{name} {u.name} {k}", np.array(o[k], dtype=np.float64)) for k in ("raw", "cand", "nc")]
+    seg_events, seg_count, ev_cap, _ = cases.compaction_arrays("300 segments")
+    h = be.run([10], np.full(12, 100.0), seg_events=seg_events, seg_count=seg_count, ev_cap=ev_cap, stages=1)
+    out += [("300 segments events", np.array(h["events"])), ("300 segments ev_count", np.array(h["ev_count"], dtype=np.float64))]
+    torch.cuda.synchronize()
+    return out
+
+
 # ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
 DROPIN_SECONDS = (0.5, 0.2, 0.31)
 
@@ -786,6 +811,7 @@ FAMILIES = {
                    + tuple(f"fft_route_dft8<{s}, {h}>" for s in (0, 1) for h in ("false", "true")), {}),
     "d4c-select": (run_d4c_select, tuple(f"d4c_select_probe<{nt}>" for nt in (128, 256, 512, 1024)), {}),
     "harvest-contour": (run_harvest_contour, ("hv_prune",) + _CONTOUR, {}),
+    "harvest-candidates": (run_harvest_candidates, ("hv_compact_events", "hv_raw_candidates", "hv_detect"), {}),
     "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
                                                             "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
                        + _SYNTHESIS, {}),

@@ -312,6 +312,9 @@ def load_library(path=LIB_PATH):
     if hasattr(lib, "world_hip_probe_harvest_contour"):              # (added under ABI 6: looked up by name)
         lib.world_hip_probe_harvest_contour.argtypes = [vp, C.c_int, _ip, _ip, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int,
                                                         vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(lib, "world_hip_probe_harvest_candidates"):           # (added under ABI 6: looked up by name)
+        lib.world_hip_probe_harvest_candidates.argtypes = [vp, C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                           C.POINTER(C.c_double)] + [C.c_int] * 7 + [vp] * 7
     lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                              C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
     lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
@@ -1496,6 +1499,43 @@ class WorldHip:
             out["step4"].data_ptr(), sec_cap, out["sec_n"].data_ptr(), out["sec"].data_ptr(), out["basic_f0"].data_ptr(),
             out["tpos"].data_ptr(), out["f0"].data_ptr()), "probe_harvest_contour")
         out["n_frames"] = frames
+        return out
+
+    def probe_harvest_candidates(self, nfb, band_f0, seg_events=None, seg_count=None, raw=None, afs=8000.0, f0_floor=71.0,
+                                 f0_ceil=800.0, ev_cap=None, ev_group=40, stages=7):
+        """Harvest's middle alone (include/world_hip.h: world_hip_probe_harvest_candidates): seg_events [n_utt, nch * 4, nseg,
+        seg_cap] float64 and seg_count [n_utt, nch * 4, nseg] int32 made-up zero-crossing lists (stages 1, 2), or raw [n_utt, nch,
+        fb_stride] float64 made-up raw candidates (stage 4 alone), nfb a sequence of n_utt ints, band_f0 of nch floats,
+        fb_stride = (max(nfb) + 7) & ~7 -> a dict of tensors: events, ev_count (stage 1 with nseg > 1), raw, cand [n_utt,
+        fb_stride, maxc], nc [n_utt] (int32).  What the call does not write is NaN (-1 in the int tensors).  ev_cap: the
+        capacity of a final list (default: seg_cap with one segment list, nseg * seg_cap otherwise)."""
+        t = self.torch
+        nfb, band_f0 = [int(v) for v in nfb], [float(v) for v in band_f0]
+        n, nch, stride = len(nfb), len(band_f0), (max(nfb) + 7) & ~7
+        maxc = int(nch / 10.0 + 0.5) * 7
+        dev = (seg_events if seg_events is not None else raw).device
+        nan = lambda *shape: t.full(shape, float("nan"), dtype=t.float64, device=dev)
+        out, nseg, seg_cap = {}, 1, 1
+        if stages & 3:
+            assert seg_events.dtype == t.float64 and seg_count.dtype == t.int32 and seg_events.is_contiguous() and seg_count.is_contiguous()
+            assert seg_events.dim() == 4 and seg_events.shape[:3] == seg_count.shape == (n, nch * 4, seg_events.shape[2])
+            nseg, seg_cap = seg_events.shape[2:]
+        ev_cap = int(ev_cap) if ev_cap is not None else (seg_cap if nseg == 1 else nseg * seg_cap)
+        if (stages & 1) and nseg > 1:
+            out["events"], out["ev_count"] = nan(n, nch * 4, ev_cap), t.full((n, nch * 4), -1, dtype=t.int32, device=dev)
+        if stages & 2:
+            out["raw"] = nan(n, nch, stride)
+        elif stages & 4:
+            assert raw.dtype == t.float64 and raw.is_contiguous() and raw.shape == (n, nch, stride)
+            out["raw"] = raw
+        if stages & 4:
+            out["cand"], out["nc"] = nan(n, stride, maxc), t.full((n,), -1, dtype=t.int32, device=dev)
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        self._check(self.lib.world_hip_probe_harvest_candidates(
+            self._context(), n, (C.c_int * n)(*nfb), afs, f0_floor, f0_ceil, nch, (C.c_double * nch)(*band_f0), maxc, stride, nseg,
+            seg_cap, ev_cap, ev_group, stages, seg_events.data_ptr() if stages & 3 else None,
+            seg_count.data_ptr() if stages & 3 else None, ptr("events"), ptr("ev_count"), ptr("raw"), ptr("cand"), ptr("nc")),
+            "probe_harvest_candidates")
         return out
 
     # ---- multi-GPU exchange records (include/world_hip.h: world_hip_pack_results) ----

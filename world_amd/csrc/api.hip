@@ -3085,6 +3085,109 @@ int world_hip_probe_harvest_contour(WorldHipContext *c, int n_utt, const int *nf
   });
 }
 
+// Harvest's middle in isolation (harvest.hip: launch_harvest_raw -- hv_compact_events and hv_raw_candidates, the body of
+// launch_harvest's group loop behind the filter bank -- and launch_harvest_detect) on zero-crossing lists the caller made up:
+// the event lists live in a workspace for ONE group of ev_group utterances, carved as run_harvest carves it, and every group's
+// slice of the caller's lists is copied there before its launches (ev_u0 = 0, ev_group, 2 ev_group, ...).  raw, cand and nc are
+// the caller's own arrays: the kernels write what they write in the product and nothing else.  nc is cleared here; in the
+// product hv_remove_mean does that, launches earlier.
+int world_hip_probe_harvest_candidates(WorldHipContext *c, int n_utt, const int *nfb, double afs, double f0_floor, double f0_ceil,
+                                       int nch, const double *band_f0, int maxc, int fb_stride, int nseg, int seg_cap, int ev_cap,
+                                       int ev_group, int stages, const double *d_seg_events, const int *d_seg_count,
+                                       double *d_events, int *d_ev_count, double *d_raw, double *d_cand, int *d_nc) {
+  return guarded(c, [&] {
+    const char *const me = "probe_harvest_candidates";
+    if (n_utt <= 0 || n_utt > kGridY) fail("%s: n_utt = %d outside 1 .. %d", me, n_utt, kGridY);
+    if (stages <= 0 || (stages & ~7)) fail("%s: stages = %d: 1 compaction, 2 raw candidates, 4 detection", me, stages);
+    if (nch < 12 || nch > 365) fail("%s: nch = %d outside 12 .. 365", me, nch);
+    if (!nfb || !band_f0) fail("%s: null buffer (%s)", me, !nfb ? "nfb" : "band_f0");
+    for (int j = 0; j < nch; ++j)
+      if (!(band_f0[j] > 0)) fail("%s: band_f0[%d] is not positive", me, j);
+    if (maxc != mround(nch / 10.0) * 7) fail("%s: maxc = %d, Harvest's is %d (round(nch / 10) * 7)", me, maxc, mround(nch / 10.0) * 7);
+    if (!(afs > 0) || !(f0_floor > 0) || !(f0_ceil > f0_floor)) fail("%s: afs, f0_floor, f0_ceil must be positive and ascending", me);
+    if (nseg < 1) fail("%s: nseg = %d: at least one segment list", me, nseg);
+    if (seg_cap < 1) fail("%s: seg_cap = %d: a segment list holds at least one event", me, seg_cap);
+    if (ev_cap < 1) fail("%s: ev_cap = %d: an event list holds at least one event", me, ev_cap);
+    if (ev_group < 1) fail("%s: ev_group = %d: a group has at least one utterance", me, ev_group);
+    const bool direct_lists = nseg == 1;                       // run_harvest's rule: the segment lists are the final lists
+    if (direct_lists && seg_cap != ev_cap) fail("%s: seg_cap = %d, but with nseg = 1 the segment lists are the final lists of ev_cap = %d", me, seg_cap, ev_cap);
+    if ((stages & 3) == 2 && !direct_lists) fail("%s: stages = %d: %d segment lists need the compaction (1) in front of the raw candidates (2)", me, stages, nseg);
+    const bool reports_lists = (stages & 1) && !direct_lists;
+    const struct { const void *p; bool needed; const char *name; } bufs[] = {
+        {d_seg_events, (stages & 3) != 0, "seg_events"}, {d_seg_count, (stages & 3) != 0, "seg_count"}, {d_events, reports_lists, "events"},
+        {d_ev_count, reports_lists, "ev_count"}, {d_raw, (stages & 6) != 0, "raw"}, {d_cand, (stages & 4) != 0, "cand"}, {d_nc, (stages & 4) != 0, "nc"}};
+    for (const auto &b : bufs)
+      if (b.needed && !b.p) fail("%s: null buffer (%s)", me, b.name);
+    HarvestParams p{};
+    p.afs = afs; p.f0_floor = f0_floor; p.f0_ceil = f0_ceil; p.nch = nch; p.maxc = maxc;
+    p.nseg = nseg; p.seg_cap = seg_cap; p.ev_cap = ev_cap;
+    p.fft_seg = direct_lists ? 1 : 0;                          // (launch_harvest_raw reads only its sign: with one segment list the FFT bank's direct lists)
+    std::vector<int> fb(nfb, nfb + n_utt);
+    int max_fb = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (fb[u] < 1) fail("%s: nfb[%d] = %d: an utterance has at least one frame", me, u, fb[u]);
+      max_fb = std::max(max_fb, fb[u]);
+    }
+    plan_harvest_tail(c, p, n_utt, max_fb);
+    if (fb_stride != p.fb_stride) fail("%s: fb_stride = %d, the batch's is %d (max nfb rounded up to 8)", me, fb_stride, p.fb_stride);
+    const size_t B = n_utt, L = static_cast<size_t>(nch) * 4, row = p.fb_stride;
+    p.ev_group = std::min(n_utt, ev_group);
+    const size_t E = p.ev_group;
+    refuse_overlap(me,
+                   {{reports_lists ? d_events : nullptr, sizeof(double) * B * L * ev_cap, "events"},
+                    {reports_lists ? d_ev_count : nullptr, sizeof(int) * B * L, "ev_count"},
+                    {(stages & 2) ? d_raw : nullptr, sizeof(double) * B * nch * row, "raw"},
+                    {(stages & 4) ? d_cand : nullptr, sizeof(double) * B * row * maxc, "cand"}, {(stages & 4) ? d_nc : nullptr, sizeof(int) * B, "nc"}},
+                   {{(stages & 3) ? d_seg_events : nullptr, sizeof(double) * B * L * nseg * seg_cap, "seg_events"},
+                    {(stages & 3) ? d_seg_count : nullptr, sizeof(int) * B * L * nseg, "seg_count"},
+                    {(stages & 6) == 4 ? d_raw : nullptr, sizeof(double) * B * nch * row, "raw"}});
+    if (stages & 3) {                                          // a count past its list's capacity would send a kernel out of bounds
+      std::vector<int> cnt(B * L * nseg);
+      devrt::d2h(cnt.data(), d_seg_count, sizeof(int) * cnt.size(), c->stream);
+      devrt::sync(c->stream);
+      for (size_t i = 0; i < cnt.size(); ++i)
+        if (cnt[i] < 0 || cnt[i] > seg_cap) fail("%s: seg_count[%zu] = %d outside 0 .. seg_cap = %d", me, i, cnt[i], seg_cap);
+    }
+    begin_stage(c, [&](Arena &a) {                             // run_harvest's carve of the lists, for one group
+      p.events = a.take<double>(E * L * ev_cap);
+      p.ev_count = a.take<int>(E * L);
+      if (direct_lists) {
+        p.seg_events = p.events; p.seg_count = p.ev_count;
+      } else {
+        p.seg_events = a.take<double>(E * L * nseg * seg_cap);
+        p.seg_count = a.take<int>(E * L * nseg);
+      }
+    });
+    p.b.n_utt = n_utt;
+    p.nfb = upload(c, fb);
+    p.band_f0 = upload(c, band_f0, static_cast<size_t>(nch));
+    p.raw = d_raw; p.cand_a = d_cand; p.nc = d_nc;
+    std::vector<int> got;
+    if (stages & 3)
+      for (int u0 = 0; u0 < n_utt; u0 += p.ev_group) {         // launch_harvest's walk
+        HarvestParams g = p;
+        g.ev_u0 = u0;
+        const int G = std::min(p.ev_group, n_utt - u0);
+        devrt::d2d(p.seg_events, d_seg_events + u0 * L * nseg * seg_cap, sizeof(double) * G * L * nseg * seg_cap, c->stream);
+        devrt::d2d(p.seg_count, d_seg_count + u0 * L * nseg, sizeof(int) * G * L * nseg, c->stream);
+        launch_harvest_raw(g, G, max_fb, stages & 3, c->stream);
+        if (reports_lists) {                                   // ev_count[list] events of every list, no more
+          got.resize(G * L);
+          devrt::d2h(got.data(), p.ev_count, sizeof(int) * got.size(), c->stream);
+          devrt::sync(c->stream);
+          for (size_t l = 0; l < got.size(); ++l)
+            if (got[l] > 0)
+              devrt::d2d(d_events + (u0 * L + l) * ev_cap, p.events + l * ev_cap, sizeof(double) * std::min(got[l], ev_cap), c->stream);
+          devrt::d2d(d_ev_count + u0 * L, p.ev_count, sizeof(int) * got.size(), c->stream);
+        }
+      }
+    if (stages & 4) {
+      devrt::dzero(d_nc, sizeof(int) * B, c->stream);          // (hv_remove_mean's store in the product)
+      launch_harvest_detect(p, max_fb, c->stream);
+    }
+  });
+}
+
 int world_hip_pack_results(WorldHipContext *c, int n_utt, const int *n_frames, int f_stride, int bins,
                            const double *d_tpos, const double *d_f0, const double *d_spectrogram,
                            const double *d_aperiodicity, long long first_row, double *d_block) {

@@ -95,6 +95,8 @@ void launch_band_spectra(const double *d_taps, const int *d_off, const int *d_ha
                          const Tables &tab, hipStream_t stream);
 void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int max_fb, int max_frames,
                     hipStream_t stream);
+void launch_harvest_raw(const HarvestParams &g, int G, int max_fb, int stages, hipStream_t stream);    // (hv_compact_events +) hv_raw_candidates
+void launch_harvest_detect(const HarvestParams &p, int max_fb, hipStream_t stream);                    // hv_detect
 void launch_harvest_tail(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);     // hv_prune + the contour
 void launch_harvest_contour(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);
 

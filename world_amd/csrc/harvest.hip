@@ -1128,6 +1128,22 @@ __global__ void hv_prune(HarvestParams p) {
 // ---------------------------------------------------------------------------
 size_t hv_band_lds_bytes(int max_half) { return band_lds_bytes(2 * max_half + 1); }
 
+// Event lists -> raw candidates for the G utterances of one group (g.ev_u0 is the first): the body of launch_harvest's group
+// loop behind the filter bank, and what world_hip_probe_harvest_candidates runs on lists the caller made up (api.hip).
+// `stages`: 1 the compaction (under the product's condition), 2 the interpolation; launch_harvest passes both.
+void launch_harvest_raw(const HarvestParams &g, int G, int max_fb, int stages, hipStream_t stream) {
+  // one chunk per utterance: the filter bank appended straight into the final lists (seg_events == events)
+  if ((stages & 1) && !(g.fft_seg > 0 && g.nseg == 1))
+    WH_BLOCKS(hv_compact_events, dim3(g.nch * 4, G), 256, compact_lds_bytes(g.nseg), stream, g);
+  if (stages & 2)
+    WH_BLOCKS(hv_raw_candidates, dim3((g.nch + 7) / 8 * 8, (max_fb + kRawRun - 1) / kRawRun, G), kRawFrames,
+              8 * kIntervalCap * sizeof(double) + 4 * sizeof(IntervalRange), stream, g);
+}
+// raw candidates -> candidates per frame and their largest number (p.nc, which hv_remove_mean cleared)
+void launch_harvest_detect(const HarvestParams &p, int max_fb, hipStream_t stream) {
+  WH_THREADS(hv_detect, max_fb, p.b.n_utt, 1, stream, p);
+}
+
 void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int max_fb, int max_frames,
                     hipStream_t stream) {
   const int B = p.b.n_utt;
@@ -1160,12 +1176,9 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
     else if (p.fft_seg > 0)
       devrt::launch_blocks("hv_band_events_fft", hv_band_events_fft<true>, dim3(p.nch, p.nseg, G), kBandFftThreads, lds, stream, g);
     else WH_BLOCKS(hv_band_events, dim3(p.nseg, p.nch, G), kBpThreads, hv_band_lds_bytes(p.max_half), stream, g);
-    // one chunk per utterance: the kernel above appended straight into the final lists (seg_events == events)
-    if (!(p.fft_seg > 0 && p.nseg == 1)) WH_BLOCKS(hv_compact_events, dim3(p.nch * 4, G), 256, compact_lds_bytes(p.nseg), stream, g);
-    WH_BLOCKS(hv_raw_candidates, dim3((p.nch + 7) / 8 * 8, (max_fb + kRawRun - 1) / kRawRun, G), kRawFrames,
-              8 * kIntervalCap * sizeof(double) + 4 * sizeof(IntervalRange), stream, g);
+    launch_harvest_raw(g, G, max_fb, 3, stream);
   }
-  WH_THREADS(hv_detect, max_fb, B, 1, stream, p);
+  launch_harvest_detect(p, max_fb, stream);
   if (p.win_full && !p.refine_frames)
     WH_WAVES(hv_refine, max_fb, B, 1, sizeof(double) * (3 * p.refine_cap + 6 * static_cast<int>(p.afs / 1000.0) + 2), stream, p);
   else
