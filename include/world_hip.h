@@ -510,6 +510,34 @@ WORLD_HIP_API int world_hip_probe_harvest_candidates(WorldHipContext *ctx, int n
                                                      int nseg, int seg_cap, int ev_cap, int ev_group, int stages,
                                                      const double *d_seg_events, const int *d_seg_count, double *d_events,
                                                      int *d_ev_count, double *d_raw, double *d_cand, int *d_nc);
+/* Harvest's refinement in isolation (csrc/harvest.hip: hv_refine / hv_refine_frames -- OverlapF0Candidates and
+ * RefineF0Candidates, src/harvest.cpp:417-631) on a decimated signal and a candidate map the caller made up, where Harvest proper
+ * takes them from the decimation and from detection: the same kernels, grid, LDS size and tables (launch_harvest_refine).
+ *   y_len, nfb, nc (host, [n_utt])  samples (>= 1), 1 ms frames (>= 1; frame f sits at f / 1000 s) and candidates per frame
+ *                            (>= 0, 7 nc <= maxc) of every utterance
+ *   afs, f0_floor, f0_ceil   analysis rate (1000 .. 48000 Hz, not necessarily whole), the refinement gate's limits.  f0_floor also
+ *                            sizes the tables; its longest window must fit the LDS and a 2^14-point transform
+ *   maxc                     slots per frame: a multiple of 7, 7 .. 252
+ *   fb_stride, y_stride      (max nfb + 7) & ~7 and the samples per utterance slot (>= max y_len), given so that both sides state them
+ *   route                    0 what a Harvest call would run for this afs and environment (WORLD_HIP_REFINE_FRAMES,
+ *                            WORLD_HIP_REFINE_ROTATE); 1 hv_refine; 2 hv_refine_frames on the window table; 3 hv_refine_frames with
+ *                            windows built by rotation.  1 and 2 are refused where fmod(afs, 1000) != 0: there is no table
+ *   d_y [n_utt][y_stride]    the signal; samples at and beyond y_len[u] are not read (indices are clamped into 0 .. y_len - 1)
+ *   d_cand [n_utt][fb_stride][maxc]  slots 0 .. nc[u] - 1 of frames 0 .. nfb[u] - 1: 0 (none) or a finite value in
+ *                            [f0_floor, min(f0_ceil, afs / 2)] -- read back and checked, a refusal otherwise; nothing else is read
+ * Out (device): d_refined, d_score [n_utt][fb_stride][maxc].  Slot j + nc[u] m of frame f takes candidate j of frame f - m
+ * (m = 0 .. 3) or f + m - 3 (m = 4 .. 6), refined, or (0, 0) where that frame lies outside the utterance, holds no candidate or
+ * the refined value fails the gate.  Slots 0 .. 7 nc[u] - 1 of frames 0 .. nfb[u] - 1 are overwritten, nothing else is touched.
+ * The candidate domain and the kernels' margin: a candidate f0 is refined in a window of half length hw(f0) = (int)(1.5 afs / f0
+ * + 1).  The kernels' LDS holds cap = 2 hw(f0_floor) + 4 samples around a frame and the window tables reach hw(f0_floor) + 2, so
+ * a candidate below f0_floor would still be inside both while hw(f0) <= hw(f0_floor) + 1, i.e. f0 > 1.5 afs / (hw(f0_floor) + 1)
+ * (39.74 Hz for a floor of 40 Hz at 8 kHz: hw = 301, 12000 / 302); detection never produces one and the probe refuses them all.  Above afs / 2 a
+ * candidate has no harmonic (a division by zero in the reference as well).
+ * A refusal names the argument and writes nothing. */
+WORLD_HIP_API int world_hip_probe_harvest_refine(WorldHipContext *ctx, int n_utt, const int *y_len, const int *nfb, const int *nc,
+                                                 double afs, double f0_floor, double f0_ceil, int maxc, int fb_stride, int y_stride,
+                                                 int route, const double *d_y, const double *d_cand, double *d_refined,
+                                                 double *d_score);
 
 /* Multi-GPU exchange (the reference has no counterpart).  Utterances are sharded over GPUs
  * and analysed independently; a GPU's results are then packed into ONE contiguous block of records

@@ -10,6 +10,8 @@ Two interchangeable back ends with one Python surface:
   on made-up candidates (oracle/harvest_contour_ref.cpp).
 * ``RefCandidates`` -- oracle/_ref/libworld_ref_candidates.so, the reference's candidate stage of Harvest
   on made-up zero-crossing lists (oracle/harvest_candidates_ref.cpp).
+* ``RefRefine``   -- oracle/_ref/libworld_ref_refine.so, the reference's refinement stage of Harvest on a
+  made-up candidate map (oracle/harvest_refine_ref.cpp).
 * ``RefOracle``   -- oracle/_ref/libworld_ref*.so, the UNMODIFIED reference
   compiled in place from /root/reference by oracle/Makefile (present whenever
   it was built in the container; the .so travels to the GPU box).
@@ -61,6 +63,11 @@ HC_COUNTERS = ("sections", "rejected", "kept", "compacted", "merge_disjoint", "m
                "extend_at_range", "extend_hit_after_3")
 
 
+# world_oracle.h: WO_HR_*: a slot's report is hw, first, lgN, nh, idx[6], gate, zero_power; and the gate's values
+HR_HW, HR_FIRST, HR_LGN, HR_NH, HR_IDX, HR_GATE, HR_ZERO_POWER, HR_WIDTH = 0, 1, 2, 3, 4, 10, 11, 12
+HR_PASSED, HR_FLOOR, HR_CEIL, HR_SCORE, HR_EMPTY = range(5)
+
+
 class PortOracle(_Base):
     kind = "port"
 
@@ -80,6 +87,10 @@ class PortOracle(_Base):
             L.wo_harvest_candidates.restype = C.c_int
             L.wo_harvest_candidates.argtypes = [_dp, C.POINTER(C.c_int), C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double,
                                                 C.c_double, _dp, _dp, C.c_int]
+        if hasattr(L, "wo_harvest_refine"):
+            L.wo_harvest_refine.restype = None
+            L.wo_harvest_refine.argtypes = [_dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp,
+                                            C.POINTER(C.c_int)]
         L.wo_dio.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                              C.c_int, C.c_double, _dp, _dp]
         L.wo_stonemask.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]
@@ -178,6 +189,17 @@ class PortOracle(_Base):
         given: detection alone) -> raw [nch, nf], cand [nf, maxc], nc"""
         return _harvest_candidates(nf, band_f0, edges, counts, raw, lambda e, c, cap, b, nch, maxc, r, cand: (
             self.lib.wo_harvest_candidates(e, c, cap, afs, b, nch, nf, f0_floor, f0_ceil, r, _p(cand), maxc), cand), maxc_wide=False)
+
+    def harvest_refine(self, y, cand, afs=8000.0, f0_floor=71.0, f0_ceil=800.0):
+        """Harvest's refinement stage on a made-up map: y the decimated signal, cand [nf, nc] -> dict(refined, score [nf, 7 nc],
+        raw [nf, 7 nc, 2] the values before the gate, report [nf, 7 nc, HR_WIDTH] int32: world_oracle.h's WO_HR_*)"""
+        y, cand = _f64(y), _f64(cand)
+        nf, nc = cand.shape
+        refined, score = np.zeros((nf, 7 * nc)), np.zeros((nf, 7 * nc))
+        raw, report = np.zeros((nf, 7 * nc, 2)), np.zeros((nf, 7 * nc, HR_WIDTH), dtype=np.int32)
+        self.lib.wo_harvest_refine(_p(y), len(y), afs, _p(cand), nf, nc, f0_floor, f0_ceil, _p(refined), _p(score), _p(raw),
+                                   report.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(refined=refined, score=score, raw=raw, report=report)
 
     def dio(self, x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_period=5.0,
             speed=1, allowed_range=0.1):
@@ -373,6 +395,40 @@ class RefCandidates:
         loc, val = np.zeros(len(signal)), np.zeros(len(signal))
         n = self.lib.ref_zero_crossing_engine(_p(signal), len(signal), fs, _p(loc), _p(val))
         return loc[:n], val[:n]
+
+
+class RefRefine:
+    """oracle/_ref/libworld_ref_refine.so: the reference's own OverlapF0Candidates, RefineF0Candidates and GetRefinedF0
+    (oracle/harvest_refine_ref.cpp includes the reference's harvest.cpp in place)"""
+    kind = "reference"
+    path = os.path.join(HERE, "_ref", "libworld_ref_refine.so")
+
+    @classmethod
+    def available(cls):
+        return os.path.exists(cls.path)
+
+    def __init__(self):
+        if not self.available():
+            raise FileNotFoundError(self.path)
+        self.lib = C.CDLL(self.path)
+        self.lib.ref_harvest_refine.restype = None
+        self.lib.ref_harvest_refine.argtypes = [_dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp]
+        self.lib.ref_harvest_refine_one.restype = None
+        self.lib.ref_harvest_refine_one.argtypes = [_dp, C.c_int] + [C.c_double] * 5 + [_dp, _dp]
+
+    def harvest_refine(self, y, cand, afs=8000.0, f0_floor=71.0, f0_ceil=800.0):
+        """as PortOracle.harvest_refine, refined and score alone"""
+        y, cand = _f64(y), _f64(cand)
+        nf, nc = cand.shape
+        refined, score = np.zeros((nf, 7 * nc)), np.zeros((nf, 7 * nc))
+        self.lib.ref_harvest_refine(_p(y), len(y), afs, _p(cand), nf, nc, f0_floor, f0_ceil, _p(refined), _p(score))
+        return dict(refined=refined, score=score)
+
+    def refine_one(self, y, pos, f0, afs=8000.0, f0_floor=71.0, f0_ceil=800.0):
+        """GetRefinedF0 on one candidate at one position -> (refined, score)"""
+        y, out = _f64(y), np.zeros(2)
+        self.lib.ref_harvest_refine_one(_p(y), len(y), afs, pos, f0, f0_floor, f0_ceil, _p(out), _p(out[1:]))
+        return float(out[0]), float(out[1])
 
 
 def ref_available():

@@ -607,6 +607,75 @@ static void harvest_refine_one(const double *y, int y_len, double fs, double pos
   free(mw); free(dw); free(buf); free(ar); free(ai); free(br); free(bi);
 }
 
+/* harvest.cpp:434-617 once more, as a statement of its own for the refinement stage alone (wo_harvest_refine; wo_harvest keeps
+ * harvest_refine_one above, double in both builds): the discrete path -- hw, fft_size, first, nh, idx, the safe index -- in the
+ * reference's double expressions, every value -- windows, products, transform, instantaneous frequency, sums, quotients, the
+ * gate's comparisons -- in wo_real.  raw (NULL: none) takes the refined F0 and score before the gate, rep (NULL: none) the
+ * slot's WO_HR_* report. */
+static void harvest_refine_one_real(const double *y, int y_len, double fs, double pos, double f0, double f0_floor,
+                                    double f0_ceil, double *rf0, double *rscore, double *raw, int *rep) {
+  *rf0 = 0.0; *rscore = 0.0;
+  if (raw) raw[0] = raw[1] = 0.0;
+  if (rep) { for (int i = 0; i < WO_HR_REPORT; ++i) rep[i] = 0; rep[WO_HR_GATE] = WO_HR_EMPTY; }
+  if (f0 <= 0.0) return;
+  int hw = (int)(1.5 * fs / f0 + 1.0);
+  int blen = 2 * hw + 1;
+  int lgN = 2 + (int)(log(hw * 2.0 + 1.0) / K_LOG2);
+  int N = (int)pow(2.0, 2.0 + (int)(log(hw * 2.0 + 1.0) / K_LOG2));
+  double base0 = (-hw + 0) / fs;
+  int first = wo_round((pos + base0) * fs + 0.001);
+  wo_real wlen = ((wo_real)2.0 * hw + 1.0) / fs;
+  wo_real *mw = ralloc(blen), *dw = ralloc(blen), *buf = ralloc(N);
+  wo_real *ar = ralloc(N / 2 + 1), *ai = ralloc(N / 2 + 1), *br = ralloc(N / 2 + 1), *bi = ralloc(N / 2 + 1);
+  for (int i = 0; i < blen; ++i) {
+    wo_real t = ((wo_real)(first + i) - 1.0) / fs - pos;
+    mw[i] = (wo_real)0.42 + (wo_real)0.5 * cos(2.0 * K_PI * t / wlen) + (wo_real)0.08 * cos(4.0 * K_PI * t / wlen);
+  }
+  dw[0] = -mw[1] / 2.0;
+  for (int i = 1; i < blen - 1; ++i) dw[i] = -(mw[i + 1] - mw[i - 1]) / 2.0;
+  dw[blen - 1] = mw[blen - 2] / 2.0;
+  for (int i = 0; i < blen; ++i) buf[i] = y[imax(0, imin(y_len - 1, first + i - 1))] * mw[i];
+  rfft(N, buf, ar, ai);
+  for (int i = 0; i < blen; ++i) buf[i] = y[imax(0, imin(y_len - 1, first + i - 1))] * dw[i];
+  rfft(N, buf, br, bi);
+
+  int nh = imin((int)(fs / 2.0 / f0), 6);
+  if (rep) { rep[WO_HR_HW] = hw; rep[WO_HR_FIRST] = first; rep[WO_HR_LGN] = lgN; rep[WO_HR_NH] = nh; }
+  wo_real num = 0.0, den = 0.0, sc = 0.0;
+  for (int k = 0; k < nh; ++k) {
+    int idx = wo_round(f0 * N / fs * (k + 1));
+    wo_real pw = ar[idx] * ar[idx] + ai[idx] * ai[idx];
+    wo_real ni = ar[idx] * bi[idx] - ai[idx] * br[idx];
+    wo_real inst = pw == 0.0 ? (wo_real)0.0 : (wo_real)idx * fs / N + ni / pw * fs / 2.0 / K_PI;
+    wo_real amp = sqrt(pw);
+    num += amp * inst;
+    den += amp * (k + (wo_real)1.0);
+    sc += fabs((inst / (k + (wo_real)1.0) - f0) / f0);
+    if (rep) { rep[WO_HR_IDX + k] = idx; if (pw == 0.0) rep[WO_HR_ZERO_POWER]++; }
+  }
+  wo_real r = num / (den + K_TINY), s = (wo_real)1.0 / (sc / nh + K_TINY);
+  if (raw) { raw[0] = (double)r; raw[1] = (double)s; }
+  int gate = r < f0_floor ? WO_HR_FLOOR : r > f0_ceil ? WO_HR_CEIL : s < 2.5 ? WO_HR_SCORE : WO_HR_PASSED;
+  if (rep) rep[WO_HR_GATE] = gate;
+  if (gate == WO_HR_PASSED) { *rf0 = (double)r; *rscore = (double)s; }
+  free(mw); free(dw); free(buf); free(ar); free(ai); free(br); free(bi);
+}
+
+/* world_oracle.h */
+void wo_harvest_refine(const double *y, int y_len, double afs, const double *cand, int nf, int nc, double f0_floor,
+                       double f0_ceil, double *refined, double *score, double *raw, int *report) {
+  for (int f = 0; f < nf; ++f)
+    for (int m = 0; m < 7; ++m) {
+      int sf = m <= 3 ? f - m : f + (m - 3);                  /* harvest.cpp:417-429 */
+      for (int j = 0; j < nc; ++j) {
+        size_t at = (size_t)f * 7 * nc + j + (size_t)nc * m;
+        double c = sf >= 0 && sf < nf ? cand[(size_t)sf * nc + j] : 0.0;
+        harvest_refine_one_real(y, y_len, afs, f * 1.0 / 1000.0, c, f0_floor, f0_ceil, refined + at, score + at,
+                                raw ? raw + 2 * at : NULL, report ? report + WO_HR_REPORT * at : NULL);
+      }
+    }
+}
+
 /* harvest.cpp:636-650 : nearest candidate, ties resolved towards the LAST */
 static double nearest_candidate(double ref, const double *c, int nc, double allowed, double *err) {
   double best = 0.0;

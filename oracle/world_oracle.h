@@ -70,6 +70,20 @@ enum { WO_HC_SECTIONS,            /* voiced sections entering step 3 */
  * hold (nch - 1) / 11 candidates: maxc must not be less. */
 int  wo_harvest_candidates(const double *edges, const int *counts, int ev_cap, double afs, const double *band_f0, int nch,
                            int nf, double f0_floor, double f0_ceil, double *raw, double *cand, int maxc);
+/* Harvest's refinement stage on a made-up candidate map (harvest.cpp:417-631): y the decimated signal, cand [nf][nc] candidates
+ * per 1 ms frame (0: none) -> refined, score [nf][7 nc], slot j + nc m of frame f from candidate j of frame f - m (m <= 3) or
+ * f + m - 3.  The discrete path is the reference's double expressions; every value is wo_real (long double in the wide build:
+ * the yardstick of the refinement kernels; in the double build a third statement beside the reference and wo_harvest's own
+ * refinement, which is untouched).  raw [nf][7 nc][2] (NULL: none): refined F0 and score BEFORE the gate; report
+ * [nf][7 nc][WO_HR_REPORT] (NULL: none): what the slot's candidate fixed and which gate closed. */
+void wo_harvest_refine(const double *y, int y_len, double afs, const double *cand, int nf, int nc, double f0_floor,
+                       double f0_ceil, double *refined, double *score, double *raw, int *report);
+enum { WO_HR_HW, WO_HR_FIRST, WO_HR_LGN, WO_HR_NH,  /* window half length, first base index, log2 fft_size, harmonics */
+       WO_HR_IDX,                  /* .. WO_HR_IDX + 5: the harmonics' bins (0 beyond nh) */
+       WO_HR_GATE = WO_HR_IDX + 6, /* one of the five below */
+       WO_HR_ZERO_POWER,           /* harmonics whose bin has power exactly 0 */
+       WO_HR_REPORT };
+enum { WO_HR_PASSED, WO_HR_FLOOR, WO_HR_CEIL, WO_HR_SCORE, WO_HR_EMPTY };
 void wo_dio(const double *x, int x_length, int fs, double f0_floor,
             double f0_ceil, double channels_in_octave, double frame_period,
             int speed, double allowed_range, double *tpos, double *f0);

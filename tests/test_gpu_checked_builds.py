@@ -723,6 +723,30 @@ def run_harvest_candidates(wh):
     return out
 
 
+# ---- Harvest's refinement stage in isolation (tests/harvest_refine_cases.py) ------------------------------------------------------
+def run_harvest_refine(wh):
+    """made-up candidate maps through world_hip_probe_harvest_refine on every route: the "caches" group (what hv_refine_frames
+    keeps in registers and LDS from slot to slot and track to track), "edges" (windows clamped at the signal ends, the empties
+    the first and last source frames own) and "batches" (ragged rows, frame counts that leave wavefronts of a workgroup idle).
+    LDS poison is the interesting build: hv_refine's idle eighth lane group and its `more ? ... : 0` step read LDS whose
+    values must be discarded, and the frame cache is read through a clamp"""
+    import torch
+    import backends
+    import harvest_refine_cases as cases
+
+    class OnWh(backends.OnGpu, cases.Backend):
+        pass
+    be, out = OnWh(wh), []
+    for name in ("caches", "edges", "batches"):
+        g = cases.group(name)
+        for route in g.routes:
+            res = be.run(g.utts, route, g.maxc) if g.batch else [be.run([u], route, g.maxc)[0] for u in g.utts]
+            for u, o in zip(g.utts, res):
+                out += [(f"{name} {u.name} route {route} {k}", o[k]) for k in ("refined", "score")]
+    torch.cuda.synchronize()
+    return out
+
+
 # ---- the drop-in symbols at shrinking and growing lengths --------------------------------------------------------------------
 DROPIN_SECONDS = (0.5, 0.2, 0.31)
 
@@ -812,6 +836,7 @@ FAMILIES = {
     "d4c-select": (run_d4c_select, tuple(f"d4c_select_probe<{nt}>" for nt in (128, 256, 512, 1024)), {}),
     "harvest-contour": (run_harvest_contour, ("hv_prune",) + _CONTOUR, {}),
     "harvest-candidates": (run_harvest_candidates, ("hv_compact_events", "hv_raw_candidates", "hv_detect"), {}),
+    "harvest-refine": (run_harvest_refine, ("hv_refine", "hv_refine_frames"), {}),
     "dropin-lengths": (run_dropin_lengths, _HARVEST_TAIL + ("dio_candidates", "dio_track_sweeps", "sm_frame", "ct_frame", "d4c_lovetrain", "d4c_frame",
                                                             "d4c_finish", "codec_code_sp", "codec_decode_sp", "codec_code_ap", "codec_decode_ap")
                        + _SYNTHESIS, {}),
@@ -820,7 +845,7 @@ FAMILIES = {
 # Families whose calls carve nothing from the arena and keep no buffer of their own between calls (cached tables apart): a
 # second pass in the same context has nothing to refill, so the hbm build's counter need only rise in the first (the tables'
 # allocation).  Every other family must see it rise in both passes.
-NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing", "fft-routes", "d4c-select")
+NO_WORKSPACE = ("coders", "resample", "mcep", "plumbing", "fft-routes", "d4c-select", "harvest-refine")
 # profile labels that are not the kernel's own name (devrt::launch_blocks("label", kernel<...>, ...))
 LABELS = {"ct_frame_coded": "ct_frame"}
 # kernels that run only while a process-wide table is built: asserted on the first pass of the jitter library, which nothing

@@ -315,6 +315,8 @@ def load_library(path=LIB_PATH):
     if hasattr(lib, "world_hip_probe_harvest_candidates"):           # (added under ABI 6: looked up by name)
         lib.world_hip_probe_harvest_candidates.argtypes = [vp, C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
                                                            C.POINTER(C.c_double)] + [C.c_int] * 7 + [vp] * 7
+    if hasattr(lib, "world_hip_probe_harvest_refine"):               # (added under ABI 6: looked up by name)
+        lib.world_hip_probe_harvest_refine.argtypes = [vp, C.c_int, _ip, _ip, _ip, C.c_double, C.c_double, C.c_double] + [C.c_int] * 4 + [vp] * 4
     lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
                                              C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
     lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
@@ -1537,6 +1539,24 @@ class WorldHip:
             seg_count.data_ptr() if stages & 3 else None, ptr("events"), ptr("ev_count"), ptr("raw"), ptr("cand"), ptr("nc")),
             "probe_harvest_candidates")
         return out
+
+    def probe_harvest_refine(self, y, y_len, cand, nfb, nc, afs=8000.0, f0_floor=71.0, f0_ceil=800.0, route=0):
+        """Harvest's refinement alone (include/world_hip.h: world_hip_probe_harvest_refine): y [n_utt, y_stride] float64 the
+        decimated signals, cand [n_utt, fb_stride, maxc] float64 a made-up candidate map (slots below nc[u] of frames below
+        nfb[u]: 0 or a value in [f0_floor, min(f0_ceil, afs / 2)]), y_len, nfb, nc sequences of n_utt ints, fb_stride =
+        (max(nfb) + 7) & ~7 -> (refined, score), tensors shaped like cand.  What the call does not write is NaN.  route: 0 a
+        Harvest call's own, 1 hv_refine, 2 hv_refine_frames on the window table, 3 hv_refine_frames by rotation."""
+        t = self.torch
+        y_len, nfb, nc = ([int(v) for v in a] for a in (y_len, nfb, nc))
+        n = len(nfb)
+        assert y.dtype == t.float64 and cand.dtype == t.float64 and y.is_contiguous() and cand.is_contiguous()
+        assert len(y_len) == len(nc) == n and y.dim() == 2 and y.shape[0] == n and cand.dim() == 3 and cand.shape[0] == n
+        refined, score = t.full_like(cand, float("nan")), t.full_like(cand, float("nan"))
+        ints = lambda v: (C.c_int * n)(*v)
+        self._check(self.lib.world_hip_probe_harvest_refine(
+            self._context(), n, ints(y_len), ints(nfb), ints(nc), afs, f0_floor, f0_ceil, cand.shape[2], cand.shape[1], y.shape[1],
+            route, y.data_ptr(), cand.data_ptr(), refined.data_ptr(), score.data_ptr()), "probe_harvest_refine")
+        return refined, score
 
     # ---- multi-GPU exchange records (include/world_hip.h: world_hip_pack_results) ----
     def capture(self, fn):

@@ -86,6 +86,7 @@ struct HarvestBands {            // cached per (fs, f0_floor, f0_ceil)
   double *d_win_tab = nullptr;   // refinement-window angle steps per half length (hv_refine)
   int win_tab_len = 0;
   size_t win_full_entries = 0;   // (w, dw) pairs of every whole-sample-centred window behind the two tables above (0: none)
+  double win_afs = 0, win_floor = 0;   // the (analysis rate, f0_floor) those three were built for (prepare_refine_windows)
   double2 *d_spec = nullptr;     // [nch][kBandFftBins] spectra of the taps / kBandFft (FFT path of the filter bank)
   int fft_seg = 0;               // outputs per block of that path (0: filters too long, direct FIR)
   std::vector<double> band_f0;
@@ -768,28 +769,36 @@ static void prepare_bands(WorldHipContext *c, int fs, double f0_floor, double f0
   } else {
     drop_table(c, hb.d_spec);
   }
+}
+
+// The refinement stage's window tables (hv_refine, hv_refine_frames) for one analysis rate and floor, cached beside the bands:
+// run_harvest and world_hip_probe_harvest_refine both come here, the probe with an afs of its own.
+static void prepare_refine_windows(WorldHipContext *c, double afs, double f0_floor) {
+  HarvestBands &hb = c->bands;
+  if (hb.win_afs == afs && hb.win_floor == f0_floor && hb.win_tab_len > 0) return;
+  devrt::sync(c->stream);
   // GetMainWindow's angles for every window half length hv_refine can meet (harvest.cpp:446-456), d = 2/(2hw+1):
-  //   [hw][6]        sin/cos(pi d), sin/cos(pi WAVE d), 2 / window length in seconds, pi d
-  //   then [hw][WAVE] (sin, cos)(pi (lane - hw - 1) d): a lane's FIRST sample of the window when the frame centre falls on
+  //   [hw][6]        sin/cos(pi d), sin/cos(pi kWinLanes d), 2 / window length in seconds, pi d
+  //   then [hw][kWinLanes] (sin, cos)(pi (lane - hw - 1) d): a lane's FIRST sample of the window when the frame centre falls on
   //                  a whole sample (it does at 8 kHz: the decimated rate of 16 / 32 / 48 / 96 kHz input); the kernel turns
   //                  it by the residual angle for other rates.  One 16-byte load replaces a division and a sincospi per
   //                  window rebuild (70 of its ~190 instructions).
   const int hw_max = static_cast<int>(1.5 * afs / f0_floor + 1.0) + 2;
   const size_t head = (size_t)(hw_max + 1) * 6;
-  std::vector<double> wt(head + (size_t)(hw_max + 1) * WAVE * 2);
+  std::vector<double> wt(head + (size_t)(hw_max + 1) * kWinLanes * 2);
   const long double pi_l = 3.14159265358979323846264338327950288L;
   for (int hw = 0; hw <= hw_max; ++hw) {
     const double wlen_t = (2.0 * hw + 1.0) / afs;
     const double d = (1.0 / afs) * (2.0 / wlen_t);
     wt[6 * hw + 0] = sin(kPi * d); wt[6 * hw + 1] = cos(kPi * d);
-    wt[6 * hw + 2] = sin(kPi * (WAVE * d)); wt[6 * hw + 3] = cos(kPi * (WAVE * d));
+    wt[6 * hw + 2] = sin(kPi * (kWinLanes * d)); wt[6 * hw + 3] = cos(kPi * (kWinLanes * d));
     wt[6 * hw + 4] = 2.0 / ((2.0 * hw + 1.0) * (1.0 / afs));           // the kernel's two_over_t, same operations
     wt[6 * hw + 5] = kPi * d;
     const long double dl = 2.0L / (2.0L * hw + 1.0L);
-    for (int lane = 0; lane < WAVE; ++lane) {
+    for (int lane = 0; lane < kWinLanes; ++lane) {
       const long double a = pi_l * (lane - hw - 1) * dl;
-      wt[head + ((size_t)hw * WAVE + lane) * 2 + 0] = (double)sinl(a);
-      wt[head + ((size_t)hw * WAVE + lane) * 2 + 1] = (double)cosl(a);
+      wt[head + ((size_t)hw * kWinLanes + lane) * 2 + 0] = (double)sinl(a);
+      wt[head + ((size_t)hw * kWinLanes + lane) * 2 + 1] = (double)cosl(a);
     }
   }
   // Where a millisecond is a whole number of samples (8 kHz: the decimated rate of 16 / 32 / 48 / 96 kHz input) every
@@ -826,6 +835,21 @@ static void prepare_bands(WorldHipContext *c, int fs, double f0_floor, double f0
   put_table(c, hb.d_win_tab, wt);
   devrt::sync(c->stream);
   hb.win_tab_len = hw_max + 1;
+  hb.win_afs = afs; hb.win_floor = f0_floor;
+}
+// What the refinement kernels read beside the signal and the candidates (p.afs and p.f0_floor are set): the LDS doubles per
+// window, the tables above and the route.  `rotate`: build the windows by rotation where the table exists too
+// (WORLD_HIP_REFINE_ROTATE); `frames`: the frame-major kernel on the table (WORLD_HIP_REFINE_FRAMES).
+static void plan_harvest_refine(WorldHipContext *c, HarvestParams &p, bool rotate, bool frames) {
+  prepare_refine_windows(c, p.afs, p.f0_floor);
+  const HarvestBands &hb = c->bands;
+  p.refine_cap = 2 * static_cast<int>(1.5 * p.afs / p.f0_floor + 1.0) + 4;
+  p.tab = c->tab;
+  p.win_tab = hb.d_win_tab; p.win_lane = hb.d_win_tab + (size_t)hb.win_tab_len * 6;
+  p.win_full = hb.win_full_entries && !rotate
+                   ? reinterpret_cast<const double2 *>(p.win_lane + (size_t)hb.win_tab_len * kWinLanes * 2) : nullptr;
+  // the candidate-major hv_refine serves the table route; this runs the frame-major kernel there instead (same bits)
+  p.refine_frames = frames;
 }
 
 // Harvest's back half -- hv_prune and the contour kernels (launch_harvest_tail) -- as run_harvest and
@@ -884,9 +908,8 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   plan_harvest_tail(c, p, n_utt, max_fb);
   p.m_stride = (max_x + 2 * p.lag + 2 * kDecPad + 7) & ~7;
   p.ev_cap = max_y / 2 + 2;
-  p.refine_cap = 2 * static_cast<int>(1.5 * p.afs / opt->f0_floor + 1.0) + 4;
+  plan_harvest_refine(c, p, getenv("WORLD_HIP_REFINE_ROTATE") != nullptr, getenv("WORLD_HIP_REFINE_FRAMES") != nullptr);
   p.max_half = hb.max_half;
-  p.tab = c->tab;
   p.fft_seg = hb.fft_seg;
   p.fft_pre = hb.max_half - 1;
   p.band_spec = hb.d_spec;
@@ -942,11 +965,6 @@ static void run_harvest(WorldHipContext *c, int n_utt, int fs, const double *d_x
   p.nfb = upload(c, nfb);
   p.ref_fft = upload(c, rfft);
   p.band_f0 = hb.d_band_f0; p.band_half = hb.d_half; p.band_off = hb.d_off; p.band_taps = hb.d_taps;
-  p.win_tab = hb.d_win_tab; p.win_lane = hb.d_win_tab + (size_t)hb.win_tab_len * 6;
-  p.win_full = hb.win_full_entries && !getenv("WORLD_HIP_REFINE_ROTATE")
-                   ? reinterpret_cast<const double2 *>(p.win_lane + (size_t)hb.win_tab_len * WAVE * 2) : nullptr;
-  // the candidate-major hv_refine serves the table route; this runs the frame-major kernel there instead (same bits)
-  p.refine_frames = getenv("WORLD_HIP_REFINE_FRAMES") != nullptr;
   p.inkernel_consts = inkernel_consts() ? 1 : 0;
   p.tpos = d_tpos; p.f0 = d_f0;
   launch_harvest(p, max_x, max_y, max_fb, max_fr, c->stream);
@@ -3185,6 +3203,74 @@ int world_hip_probe_harvest_candidates(WorldHipContext *c, int n_utt, const int 
       devrt::dzero(d_nc, sizeof(int) * B, c->stream);          // (hv_remove_mean's store in the product)
       launch_harvest_detect(p, max_fb, c->stream);
     }
+  });
+}
+
+// Harvest's refinement in isolation (harvest.hip: launch_harvest_refine -- hv_refine or hv_refine_frames, what launch_harvest
+// runs between detection and the tail) on a decimated signal and a candidate map the caller made up.  Tables, LDS size and route
+// come from plan_harvest_refine as in run_harvest, the route from the argument instead of the environment.  The kernels read
+// the caller's y and cand and write the caller's refined and score: slots below 7 nc[u] of frames below nfb[u], nothing else.
+int world_hip_probe_harvest_refine(WorldHipContext *c, int n_utt, const int *y_len, const int *nfb, const int *nc, double afs,
+                                   double f0_floor, double f0_ceil, int maxc, int fb_stride, int y_stride, int route,
+                                   const double *d_y, const double *d_cand, double *d_refined, double *d_score) {
+  return guarded(c, [&] {
+    const char *const me = "probe_harvest_refine";
+    if (n_utt <= 0 || n_utt > kGridY) fail("%s: n_utt = %d outside 1 .. %d", me, n_utt, kGridY);
+    if (!y_len || !nfb || !nc) fail("%s: null buffer (%s)", me, !y_len ? "y_len" : !nfb ? "nfb" : "nc");
+    if (!(afs >= 1000.0) || !(afs <= 48000.0)) fail("%s: afs outside 1000 .. 48000 Hz", me);
+    if (!(f0_floor > 0) || !(f0_ceil > f0_floor) || !(f0_ceil < 1e300)) fail("%s: f0_floor, f0_ceil must be positive, ascending and finite", me);
+    if (!(f0_floor <= afs / 2.0)) fail("%s: f0_floor above afs / 2: no candidate has a harmonic below the Nyquist frequency", me);
+    if (route < 0 || route > 3) fail("%s: route = %d: 0 Harvest's own, 1 hv_refine, 2 hv_refine_frames on the table, 3 by rotation", me, route);
+    if ((route == 1 || route == 2) && fmod(afs, 1000.0) != 0.0)
+      fail("%s: route = %d needs the window table, which exists where a millisecond is a whole number of samples (afs)", me, route);
+    if (maxc < 7 || maxc > 256 || maxc % 7) fail("%s: maxc = %d is not a multiple of 7 in 7 .. 252", me, maxc);
+    const struct { const void *p; const char *name; } bufs[] = {{d_y, "y"}, {d_cand, "cand"}, {d_refined, "refined"}, {d_score, "score"}};
+    for (const auto &b : bufs)
+      if (!b.p) fail("%s: null buffer (%s)", me, b.name);
+    HarvestParams p{};
+    p.afs = afs; p.f0_floor = f0_floor; p.f0_ceil = f0_ceil; p.maxc = maxc; p.y_stride = y_stride;
+    std::vector<int> yl(y_len, y_len + n_utt), fb(nfb, nfb + n_utt), cn(nc, nc + n_utt);
+    int max_fb = 0;
+    for (int u = 0; u < n_utt; ++u) {
+      if (fb[u] < 1) fail("%s: nfb[%d] = %d: an utterance has at least one frame", me, u, fb[u]);
+      if (cn[u] < 0 || cn[u] * 7 > maxc) fail("%s: nc[%d] = %d: 7 nc slots do not fit maxc = %d", me, u, cn[u], maxc);
+      if (yl[u] < 1 || yl[u] > y_stride) fail("%s: y_len[%d] = %d outside 1 .. y_stride = %d", me, u, yl[u], y_stride);
+      max_fb = std::max(max_fb, fb[u]);
+    }
+    if (max_fb > (1 << 24)) fail("%s: nfb above 2^24 frames", me);
+    p.fb_stride = (max_fb + 7) & ~7;
+    if (fb_stride != p.fb_stride) fail("%s: fb_stride = %d, the batch's is %d (max nfb rounded up to 8)", me, fb_stride, p.fb_stride);
+    // the longest window: its transform must have twiddles, and four wavefronts' LDS must fit a CU
+    const int hw_floor = static_cast<int>(1.5 * afs / f0_floor + 1.0);
+    if (2 + (31 - __builtin_clz(static_cast<unsigned>(2 * hw_floor + 1))) > kTwLog2) fail("%s: f0_floor: a window of %d samples needs a transform above 2^%d", me, 2 * hw_floor + 1, kTwLog2);
+    const bool env_rotate = getenv("WORLD_HIP_REFINE_ROTATE") != nullptr, env_frames = getenv("WORLD_HIP_REFINE_FRAMES") != nullptr;
+    plan_harvest_refine(c, p, route == 0 ? env_rotate : route == 3, route == 0 ? env_frames : route == 2);
+    if (4 * hv_refine_lds_bytes(p) > 160 * 1024) fail("%s: f0_floor: windows of %d samples do not fit the LDS", me, 2 * hw_floor + 1);
+    const size_t B = n_utt, row = p.fb_stride, map_elems = B * row * maxc;
+    refuse_overlap(me, {{d_refined, sizeof(double) * map_elems, "refined"}, {d_score, sizeof(double) * map_elems, "score"}},
+                   {{d_y, sizeof(double) * B * y_stride, "y"}, {d_cand, sizeof(double) * map_elems, "cand"}});
+    {                                                          // a candidate outside the domain would send a kernel out of its tables
+      std::vector<double> cand(map_elems);
+      devrt::d2h(cand.data(), d_cand, sizeof(double) * map_elems, c->stream);
+      devrt::sync(c->stream);
+      const double top = std::min(f0_ceil, afs / 2.0);
+      for (size_t u = 0; u < B; ++u)
+        for (int f = 0; f < fb[u]; ++f)
+          for (int j = 0; j < cn[u]; ++j) {
+            const double v = cand[(u * row + f) * maxc + j];
+            if (!(v == 0.0 || (v >= f0_floor && v <= top)))
+              fail("%s: cand[%zu][%d][%d] = %g is neither 0 nor in f0_floor .. min(f0_ceil, afs / 2)", me, u, f, j, v);
+          }
+    }
+    begin_stage(c, [](Arena &) {});
+    p.b.n_utt = n_utt;
+    p.y_len = upload(c, yl);
+    p.nfb = upload(c, fb);
+    p.nc = const_cast<int *>(upload(c, cn));                   // (hv_detect's output in the product; the refinement reads it)
+    p.y = const_cast<double *>(d_y);
+    p.cand_a = const_cast<double *>(d_cand);
+    p.cand_b = d_refined; p.score_b = d_score;
+    launch_harvest_refine(p, max_fb, c->stream);
   });
 }
 

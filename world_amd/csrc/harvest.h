@@ -7,6 +7,7 @@ namespace world_hip {
 
 constexpr int kQuirkDoubles = 8;
 constexpr int kBandFftThreads = 256;   // threads of an hv_band_events_fft workgroup (launch_harvest)
+constexpr int kWinLanes = 64;         // lanes the rotated refinement windows are built by: a first angle each in win_lane, steps of kWinLanes samples (the wavefront; the emulation walks them in one lane)
 struct HarvestParams {
   BatchView b;
   // ---- options (HarvestOption, reference src/world/harvest.h:16-20) ----
@@ -47,8 +48,8 @@ struct HarvestParams {
                            // coefficients and angle per sample w, [4..8) sincospi(256 w), sincospi(fft_seg w) -- the phase steps of
                            // hv_band_events_fft from sample to sample and block to block, uniform over a (band, utterance)
   int inkernel_consts;     // 1: hv_band_events_fft evaluates those two pairs itself (WORLD_HIP_INKERNEL_CONSTS)
-  const double *win_tab;   // [hw][6] = sin/cos(pi d), sin/cos(pi WAVE d), 2 / window length, pi d; d = 2/(2hw+1): refinement window steps
-  const double *win_lane;  // [hw][WAVE][2] = (sin, cos)(pi (lane - hw - 1) d): a lane's first window sample at a whole-sample frame centre
+  const double *win_tab;   // [hw][6] = sin/cos(pi d), sin/cos(pi kWinLanes d), 2 / window length, pi d; d = 2/(2hw+1): refinement window steps
+  const double *win_lane;  // [hw][kWinLanes][2] = (sin, cos)(pi (lane - hw - 1) d): a lane's first window sample at a whole-sample frame centre
   const double2 *win_full; // [hw^2 + i] = (main window, its central difference)[i] of half length hw centred on a sample; nullptr:
                            // a millisecond is not a whole number of samples at the analysis rate -- the kernel rotates (win_tab / win_lane)
   int refine_frames;       // 1: refine frame-major (hv_refine_frames) on the table route too (WORLD_HIP_REFINE_FRAMES)
@@ -97,6 +98,8 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
                     hipStream_t stream);
 void launch_harvest_raw(const HarvestParams &g, int G, int max_fb, int stages, hipStream_t stream);    // (hv_compact_events +) hv_raw_candidates
 void launch_harvest_detect(const HarvestParams &p, int max_fb, hipStream_t stream);                    // hv_detect
+void launch_harvest_refine(const HarvestParams &p, int max_fb, hipStream_t stream);                    // hv_refine or hv_refine_frames
+size_t hv_refine_lds_bytes(const HarvestParams &p);        // dynamic LDS of one of its wavefronts (four to a workgroup)
 void launch_harvest_tail(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);     // hv_prune + the contour
 void launch_harvest_contour(const HarvestParams &p, int max_fb, int max_frames, hipStream_t stream);
 

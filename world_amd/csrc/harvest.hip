@@ -556,6 +556,7 @@ __global__ void hv_refine_frames(HarvestParams p) {
   // slot m == g, and one vectorised tail per track finishes all seven slots at once.
   constexpr int LH = WAVE >= 8 ? 8 : 1;                           // harmonics handled side by side
   constexpr int G = WAVE / LH;                                    // sample phases
+  constexpr int PG = 8;                                           // ... of a recurrence (G on the card; the emulation walks them in one lane)
   constexpr int kIter = (6 + LH - 1) / LH;                        // harmonic groups per lane (1 on the GPU)
   constexpr int kM = (7 + G - 1) / G;                             // deferred slots per lane (1 on the GPU)
   const int hl = lane / G, g = lane % G;
@@ -656,9 +657,18 @@ __global__ void hv_refine_frames(HarvestParams p) {
         // the first term from the host's table (exact to half an ulp), the second a rotation by an angle below 0.12 rad
         // whose sine and cosine are short series (r vanishes where a millisecond is a whole number of samples: 8 kHz).
         // (round 3: a division and a sincospi per rebuild, 70 of its ~190 instructions)
+        // (the emulation's one lane takes the card's kWinLanes lanes in turn: a rotation per sample over the whole window is
+        // a sixty-four times longer recurrence than any lane runs)
+#ifdef WORLD_EMU
+        for (int vl = 0; vl < kWinLanes && vl < blen; ++vl) {
+#else
+        static_assert(WAVE == kWinLanes, "the window tables hold a first angle per lane");
+        const int vl = lane;
+        {
+#endif
         double sa, ca;
         {
-          const double2 t0 = reinterpret_cast<const double2 *>(p.win_lane)[(size_t)hw * WAVE + lane];
+          const double2 t0 = reinterpret_cast<const double2 *>(p.win_lane)[(size_t)hw * kWinLanes + vl];
           const double rho = ((first + hw) - pos * fs) * wt[5];
           const double x2 = rho * rho;
           const double sr = rho * fma(x2, fma(x2, fma(x2, fma(x2, 1.0 / 362880.0, -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0);
@@ -666,7 +676,7 @@ __global__ void hv_refine_frames(HarvestParams p) {
           sa = fma(t0.x, cr, t0.y * sr);
           ca = fma(t0.y, cr, -(t0.x * sr));
         }
-        for (int i = lane; i < blen; i += WAVE) {
+        for (int i = vl; i < blen; i += kWinLanes) {
           const double c2a = 2.0 * ca * ca - 1.0, s2a = 2.0 * sa * ca;
           const double w = 0.42 + 0.5 * ca + 0.08 * c2a;
           double dwv;
@@ -682,6 +692,7 @@ __global__ void hv_refine_frames(HarvestParams p) {
           sa = sa * cD + ca * sD;
           ca = cn;
         }
+        }
         wave_sync();
         c_hw = hw; c_first = first;
         WH_ACC_END(1);
@@ -696,41 +707,52 @@ __global__ void hv_refine_frames(HarvestParams p) {
         if (reuse) {
           if (g == 0) { are = c_are[hi]; aim = c_aim[hi]; dre = c_dre[hi]; dim = c_dim[hi]; }
         } else if (h < nh && g < blen) {
-          // sum_n v[g+nG] e^{-i theta n}, theta = 2 pi idx G / N:  s[n] = v[n] + 2cos(theta) s[n-1] - s[n-2]
-          const double2 st = p.tab.tw[(size_t)((idx * G) & (N - 1)) << (kTwLog2 - lgN)];
+          // (PG sample phases pg: the wavefront's eight lanes of a harmonic on the card, G and g; the emulation's one lane walks
+          // the same eight in turn and adds their sums as oct_sum pairs them -- one phase over the whole window is an eight
+          // times longer recurrence at an eighth of the angle, and the score's cancellation showed it)
+#ifdef WORLD_EMU
+          double ph[4][PG];
+          for (int q = 0; q < PG; ++q) ph[0][q] = ph[1][q] = ph[2][q] = ph[3][q] = 0.0;
+          for (int pg = 0; pg < PG && pg < blen; ++pg) {
+#else
+          const int pg = g;
+          {
+#endif
+          // sum_n v[pg+nPG] e^{-i theta n}, theta = 2 pi idx PG / N:  s[n] = v[n] + 2cos(theta) s[n-1] - s[n-2]
+          const double2 st = p.tab.tw[(size_t)((idx * PG) & (N - 1)) << (kTwLog2 - lgN)];
           const double c2 = 2.0 * st.x;
           double s1 = 0, s2 = 0, t1 = 0, t2 = 0;
-          int i = g;
+          int i = pg;
           // four samples per trip: the kernel is bound by instruction issue (four waves per SIMD cover the recurrence's
           // latency), and index, compare and branch are a third of a two-sample trip
 #ifndef WORLD_EMU
-          // ... and the trips EVERY phase can take (g + 4 G t + 3 G < blen for g = G - 1 too: blen / 4G of them) run on a
+          // ... and the trips EVERY phase can take (pg + 4 PG t + 3 PG < blen for pg = PG - 1 too: blen / 4 PG of them) run on a
           // wave-uniform counter: no per-lane index, compare and exec-mask update -- 1 vector instruction of overhead per
           // 16 FP64 instead of 5 (round 6: 60 % of this kernel's vector instructions were not FP64).  Same operations,
           // same order per lane; the per-lane loops below take what is left (at most 7 samples).
           {
-            const int n_uni = blen / (4 * G);
-            const cplx *yp = yw + g;
+            const int n_uni = blen / (4 * PG);
+            const cplx *yp = yw + pg;
 #pragma unroll 1
-            for (int t = 0; t < n_uni; ++t, yp += 4 * G) {
-              const cplx p0 = yp[0], p1 = yp[G], p2 = yp[2 * G], p3 = yp[3 * G];
+            for (int t = 0; t < n_uni; ++t, yp += 4 * PG) {
+              const cplx p0 = yp[0], p1 = yp[PG], p2 = yp[2 * PG], p3 = yp[3 * PG];
               const double sa = fma(c2, s1, p0.re) - s2, ta = fma(c2, t1, p0.im) - t2;
               const double sb = fma(c2, sa, p1.re) - s1, tb = fma(c2, ta, p1.im) - t1;
               s2 = fma(c2, sb, p2.re) - sa; t2 = fma(c2, tb, p2.im) - ta;
               s1 = fma(c2, s2, p3.re) - sb; t1 = fma(c2, t2, p3.im) - tb;
             }
-            i += 4 * G * n_uni;
+            i += 4 * PG * n_uni;
           }
 #endif
-          for (; i + 3 * G < blen; i += 4 * G) {
-            const cplx p0 = yw[i], p1 = yw[i + G], p2 = yw[i + 2 * G], p3 = yw[i + 3 * G];
+          for (; i + 3 * PG < blen; i += 4 * PG) {
+            const cplx p0 = yw[i], p1 = yw[i + PG], p2 = yw[i + 2 * PG], p3 = yw[i + 3 * PG];
             const double sa = fma(c2, s1, p0.re) - s2, ta = fma(c2, t1, p0.im) - t2;
             const double sb = fma(c2, sa, p1.re) - s1, tb = fma(c2, ta, p1.im) - t1;
             s2 = fma(c2, sb, p2.re) - sa; t2 = fma(c2, tb, p2.im) - ta;
             s1 = fma(c2, s2, p3.re) - sb; t1 = fma(c2, t2, p3.im) - tb;
           }
-          for (; i + G < blen; i += 2 * G) {
-            const cplx p0 = yw[i], p1 = yw[i + G];
+          for (; i + PG < blen; i += 2 * PG) {
+            const cplx p0 = yw[i], p1 = yw[i + PG];
             const double a0 = p0.re, d0 = p0.im, a1 = p1.re, d1 = p1.im;
             const double sa = fma(c2, s1, a0) - s2, ta = fma(c2, t1, d0) - t2;
             s2 = sa; t2 = ta;
@@ -740,13 +762,21 @@ __global__ void hv_refine_frames(HarvestParams p) {
             const cplx p0 = yw[i];
             const double sa = fma(c2, s1, p0.re) - s2, ta = fma(c2, t1, p0.im) - t2;
             s2 = s1; t2 = t1; s1 = sa; t1 = ta;
-            i += G;
+            i += PG;
           }
-          // i - G is the last sample taken; its phase e^{-2 pi i idx (i-G) / N} closes the sum
-          const double2 wl = p.tab.tw[(size_t)((idx * (i - G)) & (N - 1)) << (kTwLog2 - lgN)];
+          // i - PG is the last sample taken; its phase e^{-2 pi i idx (i-PG) / N} closes the sum
+          const double2 wl = p.tab.tw[(size_t)((idx * (i - PG)) & (N - 1)) << (kTwLog2 - lgN)];
           const double A = s1 - st.x * s2, B = st.y * s2, C = t1 - st.x * t2, D = st.y * t2;
           are = A * wl.x + B * wl.y; aim = B * wl.x - A * wl.y;
           dre = C * wl.x + D * wl.y; dim = D * wl.x - C * wl.y;
+#ifdef WORLD_EMU
+            ph[0][pg] = are; ph[1][pg] = aim; ph[2][pg] = dre; ph[3][pg] = dim;
+          }
+          auto oct = [](const double (&v)[PG]) { return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[7] + v[6]) + (v[5] + v[4])); };
+          are = oct(ph[0]); aim = oct(ph[1]); dre = oct(ph[2]); dim = oct(ph[3]);
+#else
+          }
+#endif
         }
 #ifndef WORLD_EMU
         static_assert(G == 8, "oct_sum reduces over eight sample phases");
@@ -834,6 +864,7 @@ __global__ void hv_refine(HarvestParams p) {
   const int nfb = p.nfb[u];
   if (sf >= nfb) return;
   constexpr int G = WAVE >= 64 ? 8 : 1;                   // sample phases: hv_refine_frames' G
+  constexpr int PG = 8;                                   // ... of a recurrence: G on the card; the emulation's one lane walks the eight in turn
   constexpr int SL = WAVE / G;                            // shift groups (on the GPU the eighth idles)
   constexpr int kS = (7 + SL - 1) / SL * SL;
   constexpr int kH = 6;                                   // harmonics (FixF0 uses at most six)
@@ -897,7 +928,7 @@ __global__ void hv_refine(HarvestParams p) {
 #pragma unroll
     for (int h = 0; h < kH; ++h) {                              // (harmonics >= nh are formed and never read)
       idx[h] = uniform_int(mround(bins * (h + 1)));
-      c2[h] = 2.0 * p.tab.tw[(size_t)((idx[h] * G) & (N - 1)) << (kTwLog2 - lgN)].x;
+      c2[h] = 2.0 * p.tab.tw[(size_t)((idx[h] * PG) & (N - 1)) << (kTwLog2 - lgN)].x;
     }
     {
       const double2 *wf = p.win_full + (size_t)hw * hw;
@@ -916,6 +947,16 @@ __global__ void hv_refine(HarvestParams p) {
       // window sample i is signal sample first + i - 1 = ys[kb + i]; for the seven shifts the span holds it by
       // construction, the clamp keeps the idle eighth inside LDS
       const int kb = imax(0, imin(span - blen, first - 1 - org));
+      double keep[8 / G][4];
+      for (int hi = 0; hi < 8 / G; ++hi) keep[hi][0] = keep[hi][1] = keep[hi][2] = keep[hi][3] = 0.0;
+#ifdef WORLD_EMU
+      double ph[kH][4][PG];                                     // the phases' closed sums, added below as oct_sum pairs them
+      for (int h = 0; h < kH; ++h) for (int q = 0; q < PG; ++q) ph[h][0][q] = ph[h][1][q] = ph[h][2][q] = ph[h][3][q] = 0.0;
+      for (int pg = 0; pg < PG; ++pg) {
+#else
+      const int pg = g;
+      {
+#endif
       double s1[kH], s2[kH], t1[kH], t2[kH];
 #pragma unroll
       for (int h = 0; h < kH; ++h) s1[h] = s2[h] = t1[h] = t2[h] = 0.0;
@@ -928,16 +969,16 @@ __global__ void hv_refine(HarvestParams p) {
           s2[h] = s1[h]; s1[h] = sa; t2[h] = t1[h]; t1[h] = ta;
         }
       };
-      const double *xp = ys + kb + g;
-      const double2 *wp = wv + g;
-      const int n_uni = blen / G;                               // the steps every phase takes (wave-uniform counter)
+      const double *xp = ys + kb + pg;
+      const double2 *wp = wv + pg;
+      const int n_uni = blen / PG;                              // the steps every phase takes (wave-uniform counter)
 #pragma unroll 2
-      for (int t = 0; t < n_uni; ++t) step(xp[t * G], wp[t * G]);
+      for (int t = 0; t < n_uni; ++t) step(xp[t * PG], wp[t * PG]);
       // the phases that take one more sample: a step for every lane, kept by those (under a branch the join holds both
       // generations of the 24 sums: 128 registers instead of 118)
-      const bool more = g < blen - n_uni * G;
+      const bool more = pg < blen - n_uni * PG;
       {
-        const int tr = more ? n_uni * G : 0;
+        const int tr = more ? n_uni * PG : 0;
         const double xv = xp[tr];
         const double2 w = wp[tr];
         const double pa = xv * w.x, pd = xv * w.y;
@@ -949,33 +990,41 @@ __global__ void hv_refine(HarvestParams p) {
         }
       }
       const int cnt = n_uni + (more ? 1 : 0);
-      // the last sample taken, g + G (cnt - 1): its phase e^{-2 pi i idx last / N} closes the sum; then the sum over
+      // the last sample taken, pg + PG (cnt - 1): its phase e^{-2 pi i idx last / N} closes the sum; then the sum over
       // phases, and lane g keeps harmonic g's (the emulation's one lane keeps all of them)
-      const int last = g + G * (cnt - 1);
-      double keep[8 / G][4];
-      for (int hi = 0; hi < 8 / G; ++hi) keep[hi][0] = keep[hi][1] = keep[hi][2] = keep[hi][3] = 0.0;
+      const int last = pg + PG * (cnt - 1);
 #pragma unroll
       for (int h = 0; h < kH; ++h) {
         double are = 0.0, aim = 0.0, dre = 0.0, dim = 0.0;
         if (cnt > 0) {
-          const double2 st = p.tab.tw[(size_t)((idx[h] * G) & (N - 1)) << (kTwLog2 - lgN)];
+          const double2 st = p.tab.tw[(size_t)((idx[h] * PG) & (N - 1)) << (kTwLog2 - lgN)];
           const double2 wl = p.tab.tw[(size_t)((idx[h] * last) & (N - 1)) << (kTwLog2 - lgN)];
           const double A = s1[h] - st.x * s2[h], B = st.y * s2[h], C = t1[h] - st.x * t2[h], D = st.y * t2[h];
           are = A * wl.x + B * wl.y; aim = B * wl.x - A * wl.y;
           dre = C * wl.x + D * wl.y; dim = D * wl.x - C * wl.y;
         }
 #ifndef WORLD_EMU
-        static_assert(G == 8, "oct_sum reduces over eight sample phases");
+        static_assert(G == 8 && PG == G, "oct_sum reduces over eight sample phases");
         are = oct_sum(are); aim = oct_sum(aim); dre = oct_sum(dre); dim = oct_sum(dim);
-#endif
         for (int hi = 0; hi < 8 / G; ++hi) {
           if (h == g + G * hi) { keep[hi][0] = are; keep[hi][1] = aim; keep[hi][2] = dre; keep[hi][3] = dim; }
-#ifndef WORLD_EMU
           // (the pick is made here: left to the compiler it kept all 24 sums to the end and the kernel spilled)
           asm volatile("" : "+v"(keep[hi][0]), "+v"(keep[hi][1]), "+v"(keep[hi][2]), "+v"(keep[hi][3]));
-#endif
         }
+#else
+        ph[h][0][pg] = are; ph[h][1][pg] = aim; ph[h][2][pg] = dre; ph[h][3][pg] = dim;
+#endif
       }
+      }
+#ifdef WORLD_EMU
+      for (int h = 0; h < kH; ++h)
+        for (int hi = 0; hi < 8 / G; ++hi)
+          if (h == g + G * hi)
+            for (int k = 0; k < 4; ++k) {
+              const double *v = ph[h][k];
+              keep[hi][k] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[7] + v[6]) + (v[5] + v[4]));
+            }
+#endif
       // FixF0 (harvest.cpp:507-536): lane g takes harmonic h = g (+ G hi)
       double num = 0.0, den = 0.0, sc = 0.0;
       for (int hi = 0; hi < 8 / G; ++hi) {
@@ -1144,6 +1193,18 @@ void launch_harvest_detect(const HarvestParams &p, int max_fb, hipStream_t strea
   WH_THREADS(hv_detect, max_fb, p.b.n_utt, 1, stream, p);
 }
 
+// candidates (cand_a, nc) -> the overlapped and refined set and its scores (cand_b / score_b): candidate-major on the window
+// table, frame-major where the table is absent (p.win_full == nullptr: the windows are rotated) or p.refine_frames asks for
+// it.  What launch_harvest runs between detection and the tail, and all that world_hip_probe_harvest_refine runs (api.hip).
+size_t hv_refine_lds_bytes(const HarvestParams &p) {        // per wavefront
+  return p.win_full && !p.refine_frames ? sizeof(double) * (3 * p.refine_cap + 6 * static_cast<int>(p.afs / 1000.0) + 2)
+                                        : 3 * sizeof(double) * p.refine_cap;
+}
+void launch_harvest_refine(const HarvestParams &p, int max_fb, hipStream_t stream) {
+  if (p.win_full && !p.refine_frames) WH_WAVES(hv_refine, max_fb, p.b.n_utt, 1, hv_refine_lds_bytes(p), stream, p);
+  else WH_WAVES(hv_refine_frames, max_fb, p.b.n_utt, 1, hv_refine_lds_bytes(p), stream, p);
+}
+
 void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int max_fb, int max_frames,
                     hipStream_t stream) {
   const int B = p.b.n_utt;
@@ -1179,10 +1240,7 @@ void launch_harvest(const HarvestParams &p, int max_x_len, int max_y_len, int ma
     launch_harvest_raw(g, G, max_fb, 3, stream);
   }
   launch_harvest_detect(p, max_fb, stream);
-  if (p.win_full && !p.refine_frames)
-    WH_WAVES(hv_refine, max_fb, B, 1, sizeof(double) * (3 * p.refine_cap + 6 * static_cast<int>(p.afs / 1000.0) + 2), stream, p);
-  else
-    WH_WAVES(hv_refine_frames, max_fb, B, 1, 3 * sizeof(double) * p.refine_cap, stream, p);
+  launch_harvest_refine(p, max_fb, stream);
   launch_harvest_tail(p, max_fb, max_frames, stream);
 }
 
