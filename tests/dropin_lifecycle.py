@@ -29,7 +29,6 @@ def analyse():
 
 
 def slots():
-    H.lib.world_hip_dropin_stats.argtypes = [C.POINTER(C.c_ulonglong)] * 3
     a, b, c = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
     H.lib.world_hip_dropin_stats(C.byref(a), C.byref(b), C.byref(c))
     return a.value
@@ -37,7 +36,6 @@ def slots():
 
 first = analyse()
 n_before = slots()
-H.lib.world_hip_shutdown.restype = C.c_int
 rc = H.lib.world_hip_shutdown()
 n_after = slots()
 second = analyse()

@@ -306,12 +306,6 @@ def expected(group):
 
 # ---- the backend ----------------------------------------------------------------------------------------------------------
 class Backend(backends.Backend):
-    def bind(self):
-        f = self.lib.world_hip_probe_harvest_candidates
-        vp = C.c_void_p
-        f.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)] + [C.c_int] * 7 + [vp] * 7
-        return f
-
     def call(self, nfb, band_f0, seg_events=None, seg_count=None, raw=None, ev_cap=1, ev_group=40, stages=7, afs=AFS, f0_floor=40.0,
              f0_ceil=2000.0, override=None):
         """the probe -> (return code, the device arrays by name, the host copies of the inputs); seg_events [n, nch * 4, nseg,
@@ -338,7 +332,7 @@ class Backend(backends.Backend):
                  ev_cap=ev_cap, ev_group=ev_group, stages=stages)
         a.update({k: self.ptr(d.get(k)) for k in ("seg_events", "seg_count", "events", "ev_count", "raw", "cand", "nc")})
         a.update(override or {})
-        rc = self.bind()(self.ctx, *(a[k] for k in (
+        rc = self.lib.world_hip_probe_harvest_candidates(self.ctx, *(a[k] for k in (
             "n_utt", "nfb", "afs", "f0_floor", "f0_ceil", "nch", "band_f0", "maxc", "fb_stride", "nseg", "seg_cap", "ev_cap", "ev_group",
             "stages", "seg_events", "seg_count", "events", "ev_count", "raw", "cand", "nc")))
         return rc, d, keep

@@ -165,12 +165,6 @@ def expected(group):
 class Backend(backends.Backend):
     exact_ties = True        # the emulator's one lane compares the distances themselves; the GPU's packed key: GpuBackend
 
-    def bind(self):
-        f = self.lib.world_hip_probe_harvest_contour
-        ip, vp = C.POINTER(C.c_int), C.c_void_p
-        f.argtypes = [vp, C.c_int, ip, ip, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
-        return f
-
     def shapes(self, group):
         nfb = [u.nf for u in group.utts]
         frames = [int((f - 1) / group.frame_period) + 1 for f in nfb]
@@ -193,9 +187,10 @@ class Backend(backends.Backend):
         a = dict(n_utt=n, nfb=(C.c_int * n)(*nfb), nc=(C.c_int * n)(*[u.nc for u in group.utts]), maxc=maxc, fb_stride=stride,
                  frame_period=group.frame_period, f_stride=f_stride, sec_cap=sec_cap, **{k: self.ptr(v) for k, v in d.items()})
         a.update(change)
-        rc = self.bind()(self.ctx, a["n_utt"], a["nfb"], a["nc"], a["maxc"], a["fb_stride"], a["cand"], a["score"], a["frame_period"],
-                         a["f_stride"], a["pruned_cand"], a["pruned_score"], a["step2"], a["step3"], a["step4"], a["sec_cap"],
-                         a["sec_n"], a["sec"], a["basic_f0"], a["tpos"], a["f0"])
+        rc = self.lib.world_hip_probe_harvest_contour(
+            self.ctx, a["n_utt"], a["nfb"], a["nc"], a["maxc"], a["fb_stride"], a["cand"], a["score"], a["frame_period"],
+            a["f_stride"], a["pruned_cand"], a["pruned_score"], a["step2"], a["step3"], a["step4"], a["sec_cap"],
+            a["sec_n"], a["sec"], a["basic_f0"], a["tpos"], a["f0"])
         return rc, d, (cand, score)
 
     def run(self, group):

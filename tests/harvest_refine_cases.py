@@ -227,12 +227,6 @@ def expected(group, u):
 
 # ---- the backend -----------------------------------------------------------------------------------------------------------
 class Backend(backends.Backend):
-    def bind(self):
-        f = self.lib.world_hip_probe_harvest_refine
-        vp, ip = C.c_void_p, C.POINTER(C.c_int)
-        f.argtypes = [vp, C.c_int, ip, ip, ip, C.c_double, C.c_double, C.c_double] + [C.c_int] * 4 + [vp] * 4
-        return f
-
     def call(self, utts, route, maxc=None, override=None):
         """the probe on utterances of one rate and gate -> (return code, the device arrays by name, the host copies of the
         inputs); `override` replaces arguments of the C call (refusals)"""
@@ -252,8 +246,8 @@ class Backend(backends.Backend):
                  f0_ceil=utts[0].f0_ceil, maxc=maxc, fb_stride=stride, y_stride=y_stride, route=route)
         a.update({k: self.ptr(d[k]) for k in ("y", "cand", "refined", "score")})
         a.update(override or {})
-        rc = self.bind()(self.ctx, *(a[k] for k in ("n_utt", "y_len", "nfb", "nc", "afs", "f0_floor", "f0_ceil", "maxc", "fb_stride",
-                                                    "y_stride", "route", "y", "cand", "refined", "score")))
+        rc = self.lib.world_hip_probe_harvest_refine(self.ctx, *(a[k] for k in (
+            "n_utt", "y_len", "nfb", "nc", "afs", "f0_floor", "f0_ceil", "maxc", "fb_stride", "y_stride", "route", "y", "cand", "refined", "score")))
         return rc, d, keep
 
     def run(self, utts, route, maxc=None):

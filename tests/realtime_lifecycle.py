@@ -19,7 +19,6 @@ from world_amd.api import HostAPI                                    # noqa: E40
 lib_path, out = sys.argv[1], sys.argv[2]
 do_fork = len(sys.argv) > 3 and sys.argv[3] == "fork"
 H = HostAPI(lib_path)
-H.lib.world_hip_shutdown.restype = C.c_int
 fs, fft, bs, P = 16000, 1024, 64, 8
 f0, sp, ap = synth_params(fs, 60, fft, seed=9)
 chunks = [4] * 15

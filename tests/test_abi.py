@@ -50,14 +50,10 @@ def test_option_helpers_are_host_arithmetic(lib_path):
     d = DioOption(); lib.InitializeDioOption(ctypes.byref(d))
     assert (d.f0_floor, d.f0_ceil, d.channels_in_octave, d.frame_period, d.speed, d.allowed_range) == \
         (71.0, 800.0, 2.0, 5.0, 1, 0.1)
-    c = CheapTrickOption(); lib.InitializeCheapTrickOption.argtypes = [ctypes.c_int, ctypes.POINTER(CheapTrickOption)]
-    lib.InitializeCheapTrickOption(48000, ctypes.byref(c))
+    c = CheapTrickOption(); lib.InitializeCheapTrickOption(48000, ctypes.byref(c))
     assert (c.q1, c.f0_floor, c.fft_size) == (-0.15, 71.0, 2048)
     lib.InitializeCheapTrickOption(16000, ctypes.byref(c)); assert c.fft_size == 1024
-    lib.GetSamplesForHarvest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double]
     assert lib.GetSamplesForHarvest(22050, 17500, 5.0) == 159
-    lib.GetF0FloorForCheapTrick.restype = ctypes.c_double
-    lib.GetF0FloorForCheapTrick.argtypes = [ctypes.c_int, ctypes.c_int]
     assert lib.GetF0FloorForCheapTrick(48000, 2048) == 3.0 * 48000 / (2048 - 3.0)
 
 
@@ -181,10 +177,111 @@ def test_shape_limits_are_answered_on_the_host():
 def test_abi_version_and_hint_are_exported_and_consistent(lib_path):
     """round 6: the batched ABI carries a version a binding checks before it binds prototypes; the header's macro
     and the library agree; the launch-geometry hint is part of the ABI and refuses a null context"""
-    lib = ctypes.CDLL(lib_path)
+    from world_amd.api import header_abi_version, load_library
+    lib = load_library(lib_path)
     text = open(os.path.join(ROOT, "include", "world_hip.h")).read()
     want = int(re.search(r"#define\s+WORLD_HIP_ABI_VERSION\s+(\d+)", text).group(1))
-    assert lib.world_hip_abi_version() == want == 6
+    assert lib.world_hip_abi_version() == want == 6 == header_abi_version() == lib.abi_version
     assert int(re.search(r"#define\s+WORLD_HIP_HINT_SHARED_DEVICE\s+(\d+)", text).group(1)) == 1
-    lib.world_hip_set_hint.argtypes = [ctypes.c_void_p, ctypes.c_int]
     assert lib.world_hip_set_hint(None, 1) == -1
+
+
+# ---- the Python binding reads its prototypes from the header (world_amd.api.header_prototypes / bind_from_header) ----------
+def stripped_header():
+    """include/world_hip.h without comments and preprocessor lines (this file's own reading, not the binding's)"""
+    text = open(os.path.join(ROOT, "include", "world_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    return "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+
+
+def declared_arities():
+    """{name: number of parameters}, counted by commas"""
+    out = {}
+    for name, params in re.findall(r"\bWORLD_HIP_API\b[^;(]*?(\w+)\s*\(([^)]*)\)\s*;", stripped_header()):
+        out[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    return out
+
+
+def test_the_reader_finds_every_declaration():
+    from world_amd.api import header_prototypes
+    tokens = len(re.findall(r"\bWORLD_HIP_API\b", stripped_header()))     # (its two #define lines are gone)
+    protos = header_prototypes()
+    assert len(protos) == tokens >= 134
+    assert sorted(protos) == declared_symbols()
+    assert {name: len(args) for name, (_, args) in protos.items()} == declared_arities()
+
+
+def test_every_exported_symbol_is_fully_bound(lib_path):
+    from world_amd.api import header_prototypes, load_library
+    lib = load_library(lib_path)
+    arity = declared_arities()
+    for name, (restype, argtypes) in header_prototypes().items():
+        fn = getattr(lib, name)                  # (test_library_exports_every_declared_symbol: all of them are there)
+        assert fn.argtypes is not None and len(fn.argtypes) == arity[name], name
+        assert list(fn.argtypes) == argtypes and fn.restype == restype, name
+
+
+def test_pinned_prototypes_guard_the_type_map():
+    from world_amd.api import HarvestOption, header_prototypes
+    c, vp, i = ctypes, ctypes.c_void_p, ctypes.c_int
+    p = header_prototypes()
+    assert p["world_hip_harvest_batch"] == (i, [vp, i, i, vp, i, vp, c.POINTER(HarvestOption), i, vp, vp])
+    assert p["world_hip_last_error"] == (c.c_char_p, [])
+    assert p["world_hip_workspace_bytes"] == (c.c_ulonglong, [vp])
+    assert p["world_hip_mcep_alpha"] == (c.c_double, [i])
+    assert p["world_hip_destroy"] == (None, [vp])
+    assert p["world_hip_check_shape"] == (i, [i, i, c.c_char_p, i])
+    assert p["world_hip_analyze_sharded"][1][0] is i and p["world_hip_analyze_sharded"][1][11] is c.c_longlong
+    assert p["world_hip_analyze_sharded"][1].count(c.c_longlong) == 1
+    assert p["world_hip_set_error_handler"] == (None, [vp, vp])          # the function-pointer typedef
+    assert p["world_hip_realtime_rng_jump"] == (None, [vp, c.c_ulonglong, vp])
+
+
+def test_unknown_types_and_unparsable_declarations_fail_loudly():
+    from world_amd.api import header_prototypes
+    ok = "typedef struct { int a; } Opt;\nWORLD_HIP_API int fine(const Opt *o, unsigned long long n);\n"
+    assert header_prototypes(ok)["fine"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_ulonglong])
+    for text, word in ((ok + "WORLD_HIP_API int odd(int n, size_t bytes);", "size_t bytes"),
+                       (ok + "WORLD_HIP_API float odd(int n);", "float"),
+                       (ok + "WORLD_HIP_API int odd(const Unknown *p);", "Unknown"),
+                       (ok + "WORLD_HIP_API int odd(int);", "odd"),
+                       (ok + "WORLD_HIP_API int odd(void (*callback)(int), int n);", "odd"),
+                       (ok + "WORLD_HIP_API int odd(int n) { return n; }", "odd"),
+                       (ok + "WORLD_HIP_API int odd[4];", "odd")):
+        with pytest.raises(ImportError, match=re.escape(word)):
+            header_prototypes(text)
+
+
+def test_a_missing_header_says_where_it_is_expected(tmp_path, monkeypatch):
+    from world_amd import api
+    monkeypatch.setattr(api, "HEADER_PATH", str(tmp_path / "include" / "world_hip.h"))
+    monkeypatch.setattr(api, "_parsed", None)
+    with pytest.raises(ImportError, match=re.escape(str(tmp_path / "include" / "world_hip.h"))):
+        api.header_prototypes()
+
+
+def test_struct_mirrors_match_the_header(tmp_path):
+    """every ctypes.Structure of world_amd.api named like a typedef of the header: its size and every field's offset are
+    what gcc gives the header's struct (field names and order from the Python class: one the header lacks does not compile)"""
+    import subprocess
+    from world_amd import api
+    typedefs = set(re.findall(r"\}\s*(\w+)\s*;", stripped_header()))
+    mirrors = {name: cls for name, cls in vars(api).items()
+               if isinstance(cls, type) and issubclass(cls, ctypes.Structure) and name in typedefs}
+    assert len(mirrors) >= 14 and {"DioOption", "WorldHipMorphCurves", "WorldSynthesizer"} <= set(mirrors)
+    lines, want = [], {}
+    for name, cls in mirrors.items():
+        want[name] = ctypes.sizeof(cls)
+        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
+        for field, _ in cls._fields_:
+            want[f"{name}.{field}"] = getattr(cls, field).offset
+            lines.append(f'  printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "world_hip.h"\nint main(void) {\n' + "\n".join(lines) +
+                   "\n  return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    r = subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    got = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    assert got == want, {k: (got.get(k), want[k]) for k in want if got.get(k) != want[k]}

@@ -31,7 +31,6 @@ def _analyse(H, x, fs):
 
 
 def _stats(lib):
-    lib.world_hip_dropin_stats.argtypes = [C.POINTER(C.c_ulonglong)] * 3
     a, b, c = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
     lib.world_hip_dropin_stats(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
@@ -130,7 +129,6 @@ def _check_error_handler(H):
     and the library works afterwards"""
     seen = []
     cb = HANDLER(lambda fn, msg, user: seen.append((fn.decode(), msg.decode())))
-    H.lib.world_hip_set_error_handler.argtypes = [HANDLER, C.c_void_p]
     H.lib.world_hip_set_error_handler(cb, None)
     try:
         fs = 16000
@@ -177,7 +175,6 @@ def _check_pair_refusals(H):
     from world_amd.api import CheapTrickOption, WorldSynthesizer, _p, _rows
     seen = []
     cb = HANDLER(lambda fn, msg, user: seen.append((fn.decode(), msg.decode())))
-    H.lib.world_hip_set_error_handler.argtypes = [HANDLER, C.c_void_p]
     H.lib.world_hip_set_error_handler(cb, None)
     try:
         nf = 8
@@ -224,7 +221,6 @@ def _check_pair_refusals(H):
 def test_emulated_pairs_of_fs_and_fft_size_the_reference_leaves_undefined_are_refused():
     H = _emu()
     _check_pair_refusals(H)
-    H.lib.world_hip_check_shape.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
     why = C.create_string_buffer(256)
     for fs, fft, smallest in CT_REFUSED:
         assert H.lib.world_hip_check_shape(fs, fft, why, 256) == 1 and str(smallest).encode() in why.value

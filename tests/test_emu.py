@@ -151,15 +151,9 @@ def test_emulated_fft_matches_numpy():
     lock-step library: real workgroup sizes, static plans, rotation twiddles, direct tables)."""
     import ctypes as C
     from test_gpu_fft_routes import ROUTES, threads_of, to_complex, to_pairs
+    from world_amd.api import load_library
     subprocess.run(["make", "-s", "-f", os.path.join(EMU_DIR, "Makefile")], check=True)
-    L = C.CDLL(os.path.join(EMU_DIR, "libworld_emu.so"))
-    L.world_hip_create.restype = C.c_void_p
-    L.world_hip_create.argtypes = [C.c_int, C.c_void_p]
-    L.world_hip_destroy.argtypes = [C.c_void_p]
-    L.world_hip_last_error.restype = C.c_char_p
-    for f in (L.world_hip_probe_rfft, L.world_hip_probe_irfft):
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
-    L.world_hip_probe_fft.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+    L = load_library(os.path.join(EMU_DIR, "libworld_emu.so"))
     ctx = L.world_hip_create(0, None)
     try:
         rng = np.random.default_rng(3)

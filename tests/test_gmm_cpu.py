@@ -810,11 +810,8 @@ def case_vc_restatement(host):
     from world_amd import synth
     fft_size, P1 = 1024, VC_ORDER + 1
     table = np.empty((P1, fft_size // 2 + 1))
-    host.lib.world_hip_mcep_alpha.argtypes, host.lib.world_hip_mcep_alpha.restype = [C.c_int], C.c_double
     alpha = host.lib.world_hip_mcep_alpha(VC_FS)
-    fn = host.lib.world_hip_mcep_tables
-    fn.argtypes = [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
-    assert fn(fft_size, VC_ORDER, alpha, table.ctypes.data, None) == 0
+    assert host.lib.world_hip_mcep_tables(fft_size, VC_ORDER, alpha, table.ctypes.data, None) == 0
     src = []
     for seed, base in VC_UTTERANCES:
         x = synth.vowel(VC_FS, 0.5, seed=seed, base_f0=base).numpy()

@@ -378,7 +378,6 @@ def test_staging_is_counted_in_the_workspace(lib, port_oracle):
     """wire 0 stages nothing; wires 1 and 2 hold 8 + 16 nb bytes per frame below the synthesis stage's arrays"""
     fs, fft, ndim = 48000, 2048, 60
     c = case_of(port_oracle, fs, fft, ndim)
-    lib.world_hip_workspace_bytes.restype = C.c_ulonglong
     held = {}
     for wire in (0, 2):
         ctx = lib.world_hip_create(0, None)

@@ -21,8 +21,6 @@ xd = x.cuda()[None].contiguous()
 torch.cuda.synchronize()
 t_in = time.perf_counter()
 L = load_library()
-L.world_hip_noise_table_build_ms.restype = C.c_double
-L.world_hip_noise_table_build_ms.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
 ta = time.perf_counter()
 ctx = L.world_hip_create(0, None)
 tb = time.perf_counter()

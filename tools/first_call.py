@@ -45,8 +45,6 @@ hip_runtime_ms = (time.perf_counter() - t_rt) * 1e3
 t_load = time.perf_counter()
 H = HostAPI()
 L = load_library()
-L.world_hip_noise_table_build_ms.restype = C.c_double
-L.world_hip_noise_table_build_ms.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
 t_lib = time.perf_counter()
 
 

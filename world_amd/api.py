@@ -15,6 +15,7 @@ The extension must exist: importing this module on a machine where
 """
 import ctypes as C
 import os
+import re
 import weakref
 
 import numpy as np
@@ -159,19 +160,88 @@ REALTIME_SCALARS = ("current_pointer", "i", "current_pointer2", "head_pointer", 
 RT_ADD, RT_SYNTH, RT_LOCKED, RT_REFRESH = 0, 1, 2, 3
 
 
-def bind_realtime(L):
-    """argument types of the six real-time symbols on any library that has them (this one, or a reference build)"""
-    sp = C.POINTER(WorldSynthesizer)
-    L.InitializeSynthesizer.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, sp]
-    L.InitializeSynthesizer.restype = None
-    L.AddParameters.argtypes = [_dp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), sp]
-    L.RefreshSynthesizer.argtypes = [sp]
-    L.RefreshSynthesizer.restype = None
-    L.DestroySynthesizer.argtypes = [sp]
-    L.DestroySynthesizer.restype = None
-    L.IsLocked.argtypes = [sp]
-    L.Synthesis2.argtypes = [sp]
-    return L
+# -- the C boundary: prototypes are read from include/world_hip.h, the header api.hip is compiled against --
+HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "world_hip.h")
+_SCALARS = {"void": None, "int": C.c_int, "double": C.c_double, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong, "unsigned int": C.c_uint}
+# what a data pointer may point to, besides the header's own struct typedefs
+_POINTEES = set(_SCALARS) | {"char", "unsigned char", "short"}
+_parsed = None                                   # (ABI version, prototypes) of the installed header, read once per process
+
+
+def _installed_header():
+    global _parsed
+    if _parsed is None:
+        if not os.path.exists(HEADER_PATH):
+            raise ImportError(f"{HEADER_PATH} is missing: the Python binding reads its prototypes from the header, "
+                              "which travels with the package")
+        with open(HEADER_PATH) as f:
+            text = f.read()
+        _parsed = (int(re.search(r"#[ \t]*define[ \t]+WORLD_HIP_ABI_VERSION[ \t]+(\d+)", text).group(1)), header_prototypes(text))
+    return _parsed
+
+
+def header_abi_version():
+    """the header's WORLD_HIP_ABI_VERSION"""
+    return _installed_header()[0]
+
+
+def header_prototypes(text=None):
+    """{name: (restype, [argtypes])} of every WORLD_HIP_API declaration in include/world_hip.h (or in `text`).  Scalars map by
+    their C type, char * to c_char_p, a pointer to a struct this module mirrors under the same name to POINTER(mirror), every
+    other pointer (data, handles, T **, the handler typedef) to c_void_p.  Anything else is an ImportError that names it."""
+    if text is None:
+        return _installed_header()[1]
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)       # no comments,
+    src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)               # no preprocessor lines
+    structs, handlers = set(), set()                                 # the header's struct and function-pointer typedefs
+    for m in re.finditer(r"\btypedef\b([^;{]*)(?:\{[^}]*\})?([^;]*);", src):
+        decl = m.group(1) + m.group(2)
+        if "(" in decl:
+            handlers.update(re.findall(r"\(\s*\*\s*(\w+)\s*\)", decl)[:1])
+        elif decl.split()[:1] == ["struct"]:
+            structs.add(decl.split()[-1])
+
+    def ctype(decl, named, where):
+        base, stars = " ".join(decl.split("*")[0].split()), decl.count("*")
+        if named and not stars:                   # "int fs": the last word is the parameter's name
+            base = " ".join(base.split()[:-1])
+        if stars == 0 and base in _SCALARS and (base != "void" or not named):
+            return _SCALARS[base]
+        if stars == 0 and base in handlers:
+            return C.c_void_p
+        if stars == 1 and base == "char":
+            return C.c_char_p
+        mirror = globals().get(base)
+        if stars == 1 and base in structs and isinstance(mirror, type) and issubclass(mirror, C.Structure):
+            return C.POINTER(mirror)
+        if stars and (base in _POINTEES or base in structs):
+            return C.c_void_p
+        raise ImportError(f"include/world_hip.h: {where}: unknown type in '{' '.join(decl.split())}'")
+
+    out = {}
+    for m in re.finditer(r"\bWORLD_HIP_API\b([^;{}]*)[;{}]", src):
+        decl = " ".join(m.group(1).split())
+        d = re.fullmatch(r"(.*?)(\w+) ?\(([^()]*)\)", re.sub(r"\bconst\b", "", decl)) if m.group(0).endswith(";") else None
+        if not d or not d.group(1).strip():
+            raise ImportError(f"include/world_hip.h: cannot parse the declaration 'WORLD_HIP_API {decl}'")
+        ret, name, params = d.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (ctype(ret, False, name), [ctype(p, True, name) for p in params])
+    return out
+
+
+def bind_from_header(lib):
+    """restype and argtypes, from the header, on every declared symbol `lib` exports; the ones it lacks (an older build, the
+    reference's own) are skipped, so callers ask hasattr() before using a feature family"""
+    for name, (restype, argtypes) in header_prototypes().items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+bind_realtime = bind_from_header      # (tests/golden/make_golden_realtime.py binds this library or a reference build under this name)
 
 
 def run_realtime_plan(L, plan):
@@ -271,175 +341,14 @@ def load_library(path=LIB_PATH):
                           "(hipcc, gfx950). There is no non-GPU fallback.")
     _hip_runtime_first()
     lib = C.CDLL(path)
-    # the batched ABI this binding was written against (include/world_hip.h: WORLD_HIP_ABI_VERSION).  Libraries of round 5
+    # the batched ABI of the header this binding reads (include/world_hip.h: WORLD_HIP_ABI_VERSION).  Libraries of round 5
     # (tools/ab.py loads those) have the same prototypes and no version symbol; anything else is refused rather than called
     # with shifted arguments
-    abi = lib.world_hip_abi_version() if hasattr(lib, "world_hip_abi_version") else 5
-    if abi not in (5, 6):
-        raise ImportError(f"{path}: batched ABI version {abi}, this binding speaks 5-6")
+    abi, current = lib.world_hip_abi_version() if hasattr(lib, "world_hip_abi_version") else 5, header_abi_version()
+    if abi not in (5, current):
+        raise ImportError(f"{path}: batched ABI version {abi}, this binding speaks 5-{current}")
     lib.abi_version = abi
-    vp = C.c_void_p
-    lib.world_hip_create.restype = vp
-    lib.world_hip_create.argtypes = [C.c_int, vp]
-    lib.world_hip_destroy.argtypes = [vp]
-    lib.world_hip_last_error.restype = C.c_char_p
-    lib.world_hip_sync.argtypes = [vp]
-    lib.world_hip_workspace_bytes.restype = C.c_ulonglong
-    lib.world_hip_workspace_bytes.argtypes = [vp]
-    lib.world_hip_noise_table_bytes.restype = C.c_ulonglong
-    lib.world_hip_noise_table_bytes.argtypes = [vp]
-    lib.world_hip_verify_tables.argtypes = [vp]
-    lib.world_hip_harvest_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                            C.c_int, vp, vp]
-    lib.world_hip_dio_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(DioOption),
-                                        C.c_int, vp, vp]
-    lib.world_hip_stonemask_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp, vp]
-    lib.world_hip_cheaptrick_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp,
-                                               C.POINTER(CheapTrickOption), vp]
-    lib.world_hip_d4c_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp, C.c_int,
-                                        C.POINTER(D4COption), vp]
-    lib.world_hip_synthesis_batch.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_int, vp, vp, vp,
-                                              _ip, C.c_int, vp]
-    lib.world_hip_pcm16_to_double.argtypes = [vp, C.c_longlong, vp, vp]
-    lib.world_hip_set_synthesis_pulse_capacity.argtypes = [vp, C.c_int]
-    lib.world_hip_synthesis_pulses_dropped.argtypes = [vp, _ip]
-    lib.world_hip_probe_rfft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
-    lib.world_hip_probe_irfft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
-    if hasattr(lib, "world_hip_probe_fft"):                          # (added under ABI 6: looked up by name)
-        lib.world_hip_probe_fft.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
-    if hasattr(lib, "world_hip_probe_select"):                       # (added under ABI 6: looked up by name)
-        lib.world_hip_probe_select.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp]
-    if hasattr(lib, "world_hip_probe_harvest_contour"):              # (added under ABI 6: looked up by name)
-        lib.world_hip_probe_harvest_contour.argtypes = [vp, C.c_int, _ip, _ip, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int,
-                                                        vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
-    if hasattr(lib, "world_hip_probe_harvest_candidates"):           # (added under ABI 6: looked up by name)
-        lib.world_hip_probe_harvest_candidates.argtypes = [vp, C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
-                                                           C.POINTER(C.c_double)] + [C.c_int] * 7 + [vp] * 7
-    if hasattr(lib, "world_hip_probe_harvest_refine"):               # (added under ABI 6: looked up by name)
-        lib.world_hip_probe_harvest_refine.argtypes = [vp, C.c_int, _ip, _ip, _ip, C.c_double, C.c_double, C.c_double] + [C.c_int] * 4 + [vp] * 4
-    lib.world_hip_analyze_packed.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                             C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_longlong, vp, C.c_int]
-    lib.world_hip_analyze_sharded.argtypes = [C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.POINTER(vp), _ip,
-                                              C.POINTER(HarvestOption), C.POINTER(CheapTrickOption), C.POINTER(D4COption),
-                                              C.c_int, C.POINTER(vp), C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]
-    lib.world_hip_check_shape.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
-    if hasattr(lib, "world_hip_set_hint"):
-        lib.world_hip_set_hint.argtypes = [vp, C.c_int]
-    if hasattr(lib, "world_hip_probe_machine"):                      # (absent from libraries of earlier rounds: tools/ab.py loads those)
-        lib.world_hip_probe_machine.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
-    lib.world_hip_record_columns.argtypes = [C.c_int, C.c_int]
-    if hasattr(lib, "world_hip_analyze_coded"):
-        lib.world_hip_coded_columns.argtypes = [C.c_int, C.c_int]
-        lib.world_hip_analyze_coded.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                                C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_int, C.c_longlong, vp, C.c_int]
-    lib.world_hip_spectral_packed_range.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp,
-                                                    C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_int, C.c_int,
-                                                    C.c_int, C.c_longlong, vp, C.c_int]
-    lib.world_hip_cheaptrick_batch_range.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp,
-                                                     C.POINTER(CheapTrickOption), C.c_int, C.c_int, C.c_int, vp]
-    lib.world_hip_d4c_batch_range.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, _ip, C.c_int, vp, vp, C.c_int,
-                                              C.POINTER(D4COption), C.c_int, C.c_int, C.c_int, vp]
-    lib.world_hip_analyze_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                            C.POINTER(CheapTrickOption), C.POINTER(D4COption), C.c_int, vp, vp, vp, vp]
-    lib.world_hip_graph_begin.argtypes = [vp]
-    lib.world_hip_graph_end.argtypes = [vp, C.POINTER(vp)]
-    lib.world_hip_graph_launch.argtypes = [vp, vp]
-    lib.world_hip_graph_destroy.argtypes = [vp]
-    lib.world_hip_pack_results.argtypes = [vp, C.c_int, _ip, C.c_int, C.c_int, vp, vp, vp, vp, C.c_longlong, vp]
-    lib.world_hip_unpack_results.argtypes = [vp, C.c_int, _ip, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, vp, vp]
-    lib.world_hip_allgather_blocks.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_longlong), C.c_int,
-                                               C.POINTER(vp)]
-    lib.world_hip_pcm_to_double.argtypes = [vp, C.c_longlong, C.c_int, vp, vp]
-    lib.world_hip_double_to_pcm16.argtypes = [vp, C.c_longlong, vp, vp]
-    lib.world_hip_wav_layout.argtypes = [C.c_char_p, _ip, _ip, _ip, C.POINTER(C.c_longlong)]
-    lib.world_hip_wav_write_pcm16.argtypes = [C.c_char_p, C.c_int, C.c_longlong, vp]
-    lib.world_hip_code_spectral_envelope.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.world_hip_decode_spectral_envelope.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.world_hip_code_aperiodicity.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.world_hip_decode_aperiodicity.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.GetNumberOfAperiodicities.argtypes = [C.c_int]
-    lib.GetFFTSizeForCheapTrick.argtypes = [C.c_int, C.POINTER(CheapTrickOption)]
-    if hasattr(lib, "world_hip_realtime_create"):                    # (added under ABI 6: looked up by name)
-        lib.world_hip_realtime_create.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
-                                                  C.POINTER(vp)]
-        lib.world_hip_realtime_destroy.argtypes = [vp]
-        lib.world_hip_realtime_destroy.restype = None
-        lib.world_hip_realtime_add.argtypes = [vp, C.c_int, _dp, C.c_int, vp, vp, C.c_int]
-        lib.world_hip_realtime_synthesize.argtypes = [vp, vp, _ip]
-        lib.world_hip_realtime_is_locked.argtypes = [vp, C.c_int]
-        lib.world_hip_realtime_refresh.argtypes = [vp, C.c_int]
-        lib.world_hip_realtime_rng_jump.argtypes = [C.POINTER(C.c_uint32), C.c_ulonglong, C.POINTER(C.c_uint32)]
-        lib.world_hip_realtime_rng_jump.restype = None
-    if hasattr(lib, "world_hip_modify_batch"):                       # (added under ABI 6: looked up by name)
-        mp = C.POINTER(WorldHipModification)
-        lib.world_hip_f0_statistics.argtypes = [vp, C.c_int, _ip, C.c_int, vp, vp]
-        lib.world_hip_modify_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, mp, vp, vp, vp, vp]
-        lib.world_hip_resynthesis_length.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
-        lib.world_hip_resynthesize_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                                     C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, C.c_double,
-                                                     _ip, C.c_int, vp]
-    if hasattr(lib, "world_hip_modify_frames_batch"):                # (likewise)
-        mp, cp = C.POINTER(WorldHipModification), C.POINTER(WorldHipFrameCurves)
-        lib.world_hip_modify_frames_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, C.c_int, mp, cp,
-                                                      vp, vp, vp, vp, vp, vp]
-        lib.world_hip_resynthesize_frames_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _ip, C.POINTER(HarvestOption),
-                                                            C.POINTER(CheapTrickOption), C.POINTER(D4COption), mp, cp, _ip,
-                                                            C.c_int, _ip, C.c_int, vp]
-    if hasattr(lib, "world_hip_synthesis_records"):                  # (likewise)
-        lib.world_hip_synthesis_records.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_longlong, vp,
-                                                    C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp]
-        lib.world_hip_realtime_add_coded.argtypes = [vp, C.c_int, _dp, C.c_int, vp, C.c_int, vp, C.c_int]
-    if hasattr(lib, "world_hip_align_batch"):                        # (likewise)
-        lp = C.POINTER(C.c_longlong)
-        lib.world_hip_align_batch.argtypes = [vp, C.c_int, C.c_int, vp, lp, _ip, C.c_int, vp, lp, _ip, C.c_int, C.c_int,
-                                              vp, vp, vp, C.c_int, vp, vp]
-        lib.world_hip_align_workspace_cells.argtypes = []
-    if hasattr(lib, "world_hip_morph_batch"):                        # (likewise)
-        lib.world_hip_morph_length.argtypes = [C.c_int, C.c_int, C.c_double]
-        lib.world_hip_morph_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, vp, vp, vp, _ip, C.c_int, vp, vp, vp,
-                                              C.c_int, vp, vp, C.POINTER(WorldHipMorph), C.POINTER(WorldHipMorphCurves),
-                                              C.c_int, vp, vp, vp, vp, vp]
-    if hasattr(lib, "world_hip_resample_batch"):                     # (likewise)
-        op = C.POINTER(WorldHipResampleOption)
-        lib.world_hip_resample_option.argtypes = [C.c_int, op]
-        lib.world_hip_resample_option.restype = None
-        lib.world_hip_resample_length.argtypes = [C.c_int, C.c_int, C.c_int]
-        lib.world_hip_resample_shape.argtypes = [C.c_int, C.c_int, op, _ip, _ip, _ip]
-        lib.world_hip_resample_taps.argtypes = [C.c_int, C.c_int, op, vp]
-        lib.world_hip_resample_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, op, vp, C.c_int, _ip, vp, C.c_int]
-    if hasattr(lib, "world_hip_sp2mc"):                              # (likewise)
-        lib.world_hip_mcep_alpha.argtypes = [C.c_int]
-        lib.world_hip_mcep_alpha.restype = C.c_double
-        lib.world_hip_mcep_tables.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp]
-        for fn in (lib.world_hip_sp2mc, lib.world_hip_mc2sp):
-            fn.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_longlong, vp, C.c_longlong]
-    if hasattr(lib, "world_hip_mlpg_batch"):                         # (likewise)
-        ll = C.c_longlong
-        lib.world_hip_delta_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, _ip, vp, ll, vp, ll, ll, C.c_double,
-                                              vp, ll, ll]
-        lib.world_hip_mlpg_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, _ip, vp, ll, vp, ll, ll, vp, ll, ll,
-                                             C.c_int, C.c_double, vp, ll, ll]
-    if hasattr(lib, "world_hip_gmm_convert"):                        # (likewise)
-        ll, i, d = C.c_longlong, C.c_int, C.c_double
-        lib.world_hip_gmm_model_doubles.argtypes = [i, i, i]
-        lib.world_hip_gmm_model_doubles.restype = ll
-        lib.world_hip_gmm_prepare.argtypes = [i, i, i, vp, vp, vp, vp]
-        lib.world_hip_gmm_model_parts.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        lib.world_hip_gmm_convert.argtypes = [vp, i, i, i, vp, i, vp, ll, i, vp, ll, vp, ll, vp, ll, vp]
-        lib.world_hip_gmm_accumulate.argtypes = [vp, i, i, i, vp, ll, vp, ll, vp, vp, vp, vp]
-        lib.world_hip_gmm_update.argtypes = [i, i, vp, vp, vp, vp, d, d, vp, vp, vp]
-        lib.world_hip_gmm_fit.argtypes = [vp, i, i, i, vp, ll, i, d, vp, vp, vp, vp]
-        lib.world_hip_gmm_init.argtypes = [vp, i, i, i, vp, ll, vp, vp, vp]
-    if hasattr(lib, "world_hip_joint_rows_batch"):                   # (likewise)
-        ll, i, d, lp = C.c_longlong, C.c_int, C.c_double, C.POINTER(C.c_longlong)
-        lib.world_hip_frame_power_batch.argtypes = [vp, i, i, _ip, vp, ll, ll, vp, ll, vp]
-        lib.world_hip_select_frames_batch.argtypes = [vp, i, _ip, vp, ll, ll, d, vp, vp, ll, vp, ll, vp, vp, ll]
-        lib.world_hip_gather_rows_batch.argtypes = [vp, i, i, _ip, vp, ll, ll, _ip, vp, ll, d, vp, ll, ll]
-        lib.world_hip_joint_rows_batch.argtypes = [vp, i, i, i, vp, lp, _ip, ll, vp, lp, _ip, ll, _ip, vp, i, vp, _ip, ll, vp, _ip, ll,
-                                                   d, vp, lp, ll]
-    lib.world_hip_profile_enable.argtypes = [C.c_int]
-    lib.world_hip_profile_collect.argtypes = [C.c_char_p, C.c_int]
-    return lib
+    return bind_from_header(lib)
 
 
 def frame_count(fs, x_length, frame_period):
@@ -520,27 +429,7 @@ class HostAPI:
         self.path = path
         if hip_runtime:                      # False only for CPU-only libraries (the reference build)
             _hip_runtime_first()
-        self.lib = L = C.CDLL(path)
-        L.Dio.argtypes = [_dp, C.c_int, C.c_int, C.POINTER(DioOption), _dp, _dp]
-        L.Harvest.argtypes = [_dp, C.c_int, C.c_int, C.POINTER(HarvestOption), _dp, _dp]
-        L.StoneMask.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]
-        L.CheapTrick.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(CheapTrickOption),
-                                 C.POINTER(_dp)]
-        L.D4C.argtypes = [_dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.POINTER(D4COption), C.POINTER(_dp)]
-        L.GetSamplesForDIO.argtypes = [C.c_int, C.c_int, C.c_double]
-        L.GetSamplesForHarvest.argtypes = [C.c_int, C.c_int, C.c_double]
-        L.GetFFTSizeForCheapTrick.argtypes = [C.c_int, C.POINTER(CheapTrickOption)]
-        L.GetF0FloorForCheapTrick.argtypes = [C.c_int, C.c_int]
-        L.GetF0FloorForCheapTrick.restype = C.c_double
-        L.InitializeCheapTrickOption.argtypes = [C.c_int, C.POINTER(CheapTrickOption)]
-        rows = C.POINTER(_dp)
-        L.Synthesis.argtypes = [_dp, C.c_int, rows, rows, C.c_int, C.c_double, C.c_int, C.c_int, _dp]   # synthesis.h:30
-        # codec.h:33-88
-        L.GetNumberOfAperiodicities.argtypes = [C.c_int]
-        L.CodeAperiodicity.argtypes = [rows, C.c_int, C.c_int, C.c_int, rows]
-        L.DecodeAperiodicity.argtypes = [rows, C.c_int, C.c_int, C.c_int, rows]
-        L.CodeSpectralEnvelope.argtypes = [rows, C.c_int, C.c_int, C.c_int, C.c_int, rows]
-        L.DecodeSpectralEnvelope.argtypes = [rows, C.c_int, C.c_int, C.c_int, C.c_int, rows]
+        self.lib = bind_from_header(C.CDLL(path))   # (the reference's build exports the same names with the same signatures)
 
     def frame_count(self, fs, n, frame_period):
         return frame_count(fs, n, frame_period)
@@ -600,38 +489,36 @@ class HostAPI:
 
     # -- real-time synthesis (reference synthesisrealtime.h) --
     def _rt(self):
-        if not getattr(self, "_rt_bound", False):
-            bind_realtime(self.lib)
-            self._rt_bound = True
+        """the library for a raw call of a real-time symbol (they are bound with the rest)"""
         return self.lib
 
     def initialize_synthesizer(self, fs, frame_period, fft_size, buffer_size, number_of_pointers):
         s = WorldSynthesizer()
-        self._rt().InitializeSynthesizer(fs, frame_period, fft_size, buffer_size, number_of_pointers, C.byref(s))
+        self.lib.InitializeSynthesizer(fs, frame_period, fft_size, buffer_size, number_of_pointers, C.byref(s))
         return s
 
     def add_parameters(self, synth, f0, sp, ap):
         """AddParameters of one chunk; the row pointers only live for the call (this library copies the rows then)"""
         f0, sp, ap = _f64(f0), _f64(sp), _f64(ap)
-        return self._rt().AddParameters(_p(f0), len(f0), _rows(sp), _rows(ap), C.byref(synth))
+        return self.lib.AddParameters(_p(f0), len(f0), _rows(sp), _rows(ap), C.byref(synth))
 
     def synthesis2(self, synth):
         """(return value, copy of buffer[0, buffer_size))"""
-        r = self._rt().Synthesis2(C.byref(synth))
+        r = self.lib.Synthesis2(C.byref(synth))
         return r, np.ctypeslib.as_array(synth.buffer, shape=(synth.buffer_size,)).copy()
 
     def is_locked(self, synth):
-        return self._rt().IsLocked(C.byref(synth))
+        return self.lib.IsLocked(C.byref(synth))
 
     def refresh_synthesizer(self, synth):
-        self._rt().RefreshSynthesizer(C.byref(synth))
+        self.lib.RefreshSynthesizer(C.byref(synth))
 
     def destroy_synthesizer(self, synth):
-        self._rt().DestroySynthesizer(C.byref(synth))
+        self.lib.DestroySynthesizer(C.byref(synth))
 
     def realtime_plan(self, plan):
         """run_realtime_plan() on this library"""
-        return run_realtime_plan(self._rt(), plan)
+        return run_realtime_plan(self.lib, plan)
 
     # -- codec (reference codec.h) --
     def number_of_aperiodicities(self, fs):
@@ -663,14 +550,10 @@ class HostAPI:
 
     # ---- the Gaussian mixture's host arithmetic (include/world_hip.h: world_hip_gmm_prepare / _model_parts / _update) ----
     def _gmm(self, name, *args):
-        fn = getattr(self.lib, name)
-        fn.argtypes = [C.c_double if isinstance(a, float) else C.c_int if isinstance(a, int) else C.c_void_p for a in args]
-        fn.restype = C.c_longlong if name.endswith("_doubles") else C.c_int
-        return fn(*(a if isinstance(a, (int, float)) or a is None else a.ctypes.data for a in args))
+        return getattr(self.lib, name)(*(a if isinstance(a, (int, float)) or a is None else a.ctypes.data for a in args))
 
     def _gmm_check(self, rc, what):
         if rc != 0:
-            self.lib.world_hip_last_error.restype = C.c_char_p
             raise RuntimeError(f"{what}: {self.lib.world_hip_last_error().decode()}")
 
     def gmm_prepare(self, w, mu, cov, dx):
@@ -709,19 +592,7 @@ class FileAPI:
             raise ImportError(f"{path} is missing (python -m world_amd.build); there is no fallback.")
         if hip_runtime:
             _hip_runtime_first()
-        self.lib = L = C.CDLL(path)
-        rows, s = C.POINTER(_dp), C.c_char_p
-        L.wavwrite.argtypes = [_dp, C.c_int, C.c_int, C.c_int, s]
-        L.GetAudioLength.argtypes = [s]
-        L.wavread.argtypes = [s, _ip, _ip, _dp]
-        L.WriteF0.argtypes = [s, C.c_int, C.c_double, _dp, _dp, C.c_int]
-        L.ReadF0.argtypes = [s, _dp, _dp]
-        L.GetHeaderInformation.argtypes = [s, s]
-        L.GetHeaderInformation.restype = C.c_double
-        for name in ("WriteSpectralEnvelope", "WriteAperiodicity"):
-            getattr(L, name).argtypes = [s, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, rows]
-        for name in ("ReadSpectralEnvelope", "ReadAperiodicity"):
-            getattr(L, name).argtypes = [s, rows]
+        self.lib = bind_from_header(C.CDLL(path))
 
     @staticmethod
     def _s(path):
